@@ -15,6 +15,15 @@ to rank 0; --split sample gives rank r the launches i = r mod N over the whole f
 one reduce -- BASELINE.json configs[4]'s decomposition).  Scene, BVH and seeds are resident in HBM before the timed
 region.  Prints ONE JSON line on rank 0.
 
+A plain run does what the headline figure needs: set-up, one counting launch (the frame's ray count, untimed), W warm-up
+frames, K timed frames, the line.  `--full` adds what else the benchmark measures or checks, each outside the timed
+region: a context's first frame, the counting launch again in the warm state, a second build of the tree (its warm build
+time), the fast_shading leg (unless --no-fast-leg), the CPU baseline (unless --no-cpu-baseline) and, for N > 1, rank 0's
+check of the collected frame against its own render.  `--dump-outputs DIR` writes what the last timed frame computed
+(the accumulation buffer rank 0 holds after the frame's collective) to DIR/accum.npy, float32 [H, W, 3] with rows
+bottom-up as the kernels write them; above DUMP_LIMIT_BYTES a fixed, seeded sample of its pixels, DIR/accum_sample.npy
+[n, 3].  Scene and seeds are fixed, so runs with the same arguments compute on the same inputs.
+
 N > 1 (no multi-GPU node has been available to this project: the first run on one must explain itself whatever happens):
   * pre-flight: every communicator carries one collective under a 30 s deadline before anything is timed; if that fails on any rank
     with the non-blocking communicator, all ranks fall back to a blocking one once; if it fails again rank 0 prints a JSON line with
@@ -52,6 +61,8 @@ DRAIN_BELOW_DEFAULT = 64    # option drain_below as moptix_create leaves it (csr
 PREFLIGHT_TIMEOUT_MS = int(os.environ.get("MOPTIX_BENCH_PREFLIGHT_MS", "30000"))
 COMM_TIMEOUT_MS = 120000
 KERNEL_WAVES_PER_SIMD = 3   # what the trace kernel's 168 registers and 53 KB of LDS allow (csrc/packetkernel.hip)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20260      # the pixels of a sampled dump (np.random.RandomState)
 
 
 def source_hash(repo):
@@ -274,6 +285,24 @@ def other_configs(repo):
     return out
 
 
+def write_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as d/<name>.npy in float32.  When they would take more than `limit` bytes in all, an array
+    keeps a fixed, seeded sample of its rows (pixels for an [H, W, C] image), in their order, as d/<name>_sample.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    written = {}
+    for name, v in arrays.items():
+        if total > limit:
+            rows = v.reshape(-1, v.shape[-1]) if v.ndim > 1 else v.reshape(-1, 1)
+            keep = max(1, int(len(rows) * (limit / float(total))))
+            idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(len(rows), keep, replace=False))
+            v, name = rows[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), v)
+        written[name] = list(v.shape)
+    return written
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -288,6 +317,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-fast-leg", action="store_true", help="skip the untimed fast_shading comparison leg (PMC passes)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--split", choices=("tile", "sample"), default="tile", help="multi-GPU decomposition (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: first frame, warm counting launch, warm tree build, "
+                         "fast_shading leg, CPU baseline, N > 1 frame check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last frame's accumulation buffer to DIR/accum.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -337,8 +371,10 @@ class GpuFrame:
             self.ctx.set_partition(self.part_rank, self.part_n)
         self.ctx.load(hs)
         self.build_ms_cold = self.ctx.accel_info().buildMs
-        self.ctx.build_accel("Trbvh" if self.ctx.accel_info().nTriangles else "NoAccel")      # same tree again, code already loaded
-        self.build_ms_warm = self.ctx.accel_info().buildMs
+        self.build_ms_warm = None
+        if getattr(a, "full", False):
+            self.ctx.build_accel("Trbvh" if self.ctx.accel_info().nTriangles else "NoAccel")      # same tree again, code already loaded
+            self.build_ms_warm = self.ctx.accel_info().buildMs
         W, H = a.width, a.height
         self.accum = torch.zeros(H * W * 3, dtype=torch.float32, device=self.device)
         self.ctx.accum_bind(self.accum.data_ptr())
@@ -536,6 +572,13 @@ class GpuFrame:
             j = self.frame_no % 2
             self._finish(j); self._finish(1 - j)
 
+    def outputs(self):
+        """--dump-outputs, after flush(): what a caller of the timed path holds after the last frame -- the accumulation buffer of the
+        context that rendered it, the whole frame on rank 0 once the frame's collective has run."""
+        j = (self.frame_no - 1) % 2 if self.pipeline else 0
+        self.sync()
+        return {"accum": self.accums[j].view(self.a.height, self.a.width, 3).cpu().numpy()}
+
     def reset_kernel_time(self):
         for c in self.ctxs:
             c.kernel_time(reset=True)
@@ -576,8 +619,9 @@ class GpuFrame:
         v = self.ctx.get_option("kernel_variant_used")
         return {"kernel_variant": v, "bvh_nodes": int(info.nNodes), "bvh_depth": int(info.treeDepth),
                 "path_slots_per_workgroup": self.ctx.get_option("path_slots") if v == 4 else 512,
-                # the context's first build loads the builder's code objects (~5 ms): both numbers, the warm one is the builder's
-                "bvh_build_ms": round(float(self.build_ms_warm), 3), "bvh_build_ms_first_in_context": round(float(self.build_ms_cold), 3),
+                # the context's first build loads the builder's code objects (~5 ms): both numbers, the warm one (--full) is the builder's
+                "bvh_build_ms": round(float(self.build_ms_warm), 3) if self.build_ms_warm is not None else None,
+                "bvh_build_ms_first_in_context": round(float(self.build_ms_cold), 3),
                 "kernel": "pt_packetkernel (trace)" if v == 4 else "pt_queuekernel (trace)"}
 
     def parallelism(self):
@@ -691,7 +735,7 @@ def run_rank(a, frame_cls=GpuFrame):
                 give_up("the ranks cannot complete a collective (pre-flight, %d ms deadline; non-blocking and blocking communicator both tried)" % PREFLIGHT_TIMEOUT_MS,
                         ["rank %d: %s" % (i, t or "ok") for i, t in enumerate(said)])
 
-    first_ms = fr.first_frame() if hasattr(fr, "first_frame") and world == 1 and not os.environ.get("MOPTIX_BENCH_PIPELINE") else None
+    first_ms = fr.first_frame() if a.full and hasattr(fr, "first_frame") and world == 1 and not os.environ.get("MOPTIX_BENCH_PIPELINE") else None
     my_rays, my_bytes = fr.count()
     tot = torch.tensor([float(my_rays), float(my_bytes)], dtype=torch.float64, device=dev)
     if use_dist:
@@ -719,12 +763,13 @@ def run_rank(a, frame_cls=GpuFrame):
             if not any("ms_per_step" in r for r in results.values()):
                 break
             continue
+        frame_out = None
         try:
             if True:
                 for _ in range(a.warmup):
                     fr.step()
                 fr.flush()
-                if mi == 0 and a.warmup > 0 and hasattr(fr, "first_frame"):
+                if a.full and mi == 0 and a.warmup > 0 and hasattr(fr, "first_frame"):
                     fr.count()                                          # the counted launch again, in the state the timed frames are in
                 fr.reset_kernel_time()
                 barrier()
@@ -734,6 +779,8 @@ def run_rank(a, frame_cls=GpuFrame):
                 fr.flush()
                 barrier()
                 dt = time.perf_counter() - t0
+                # --dump-outputs: rank 0's copy of the last timed frame, taken before anything else renders into its buffers
+                frame_out = fr.outputs() if a.dump_outputs and rank == 0 and hasattr(fr, "outputs") else None
         except Exception as e:                                          # a collective that hit its deadline (MOPTIX_ERR_COMM), a HIP error ...
             failed = "%s: %s" % (type(e).__name__, e)
         said = everyone(failed)
@@ -756,8 +803,9 @@ def run_rank(a, frame_cls=GpuFrame):
         if use_dist and world > 1:
             dist.all_gather(per_rank, mine)
         per_rank = [[float(x) for x in t.tolist()] for t in per_rank]
-        results[mode] = {"ms_per_step": dt / a.steps * 1e3, "dt": dt, "kms": kms, "nlaunch": nlaunch, "reduce_ms": reduce_ms, "per_rank": per_rank}
-        if mi == 0 and hasattr(fr, "verify_frame"):
+        results[mode] = {"ms_per_step": dt / a.steps * 1e3, "dt": dt, "kms": kms, "nlaunch": nlaunch, "reduce_ms": reduce_ms, "per_rank": per_rank,
+                         "outputs": frame_out}
+        if a.full and mi == 0 and hasattr(fr, "verify_frame"):
             try:
                 frame_check = fr.verify_frame()
             except Exception as e:
@@ -773,7 +821,7 @@ def run_rank(a, frame_cls=GpuFrame):
             fr.set_mode("one_frame")
         except Exception:
             pass
-    fast = None if a.no_fast_leg else fr.fast_leg(total_rays)
+    fast = fr.fast_leg(total_rays) if a.full and not a.no_fast_leg else None
 
     if rank == 0:
         W, H = a.width, a.height
@@ -833,8 +881,10 @@ def run_rank(a, frame_cls=GpuFrame):
         }
         if fast is not None:
             out["fast_shading_mode"] = fast
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(W, H, a.cpu_seconds)
+        if a.dump_outputs and best.get("outputs") is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "arrays": write_outputs(a.dump_outputs, best["outputs"]), "mode": mode}
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

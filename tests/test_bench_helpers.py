@@ -137,12 +137,12 @@ def test_gpus_2_launcher_path_on_cpu(tmp_path, split):
         assert np.allclose(got, ref, rtol=0, atol=2e-6 * spp)
 
 
-def _stub_two_ranks(tmp_path, extra_env, split="tile"):
+def _stub_two_ranks(tmp_path, extra_env, split="tile", extra=()):
     w, h, spp = 40, 24, 2
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["BENCH_STUB_FRAME"] = str(tmp_path / "frame.npy"); env["OMP_NUM_THREADS"] = "2"
     env.update(extra_env)
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--width", str(w), "--height", str(h), "--spp", str(spp), "--scene", "spheres", "--no-cpu-baseline", "--split", split]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--width", str(w), "--height", str(h), "--spp", str(spp), "--scene", "spheres", "--no-cpu-baseline", "--split", split] + list(extra)
     code = ("import sys; sys.path.insert(0, %r); import bench; sys.exit(bench.launch_workers(2, %r, script=%r))"
             % (REPO, argv, os.path.join(REPO, "tests", "bench_stub_worker.py")))
     out_file = tmp_path / "out.txt"
@@ -182,3 +182,95 @@ def test_two_ranks_on_cpu_preflight_falls_back_once_then_gives_up_with_a_line(tm
     assert rc != 0 and len(lines) == 1, text[-2000:]
     d = lines[0]
     assert d["value"] is None and "pre-flight" in d["error"] and d["config"]["ranks"]["diagnosis"][0].endswith("ok") and "rank 1" in d["config"]["ranks"]["diagnosis"][1]
+
+
+def _one_rank(monkeypatch, tmp_path, capsys, extra):
+    """bench.run_rank with one rank on CPU, the stand-in renderer of tests/bench_stub_worker.py, every leg of the run recorded."""
+    import bench_stub_worker as S
+    calls = []
+
+    class Frame(S.StubFrame):
+        def step(self):
+            calls.append("step")
+            return super().step()
+
+        def count(self):
+            calls.append("count")
+            return super().count()
+
+        def first_frame(self):
+            calls.append("first_frame")
+            return 1.0
+
+        def fast_leg(self, total_rays):
+            calls.append("fast_leg")
+            return {"value": 1.0}
+
+        def verify_frame(self):
+            calls.append("verify_frame")
+            return None
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MOPTIX_BENCH_FORCE_DIST", "MOPTIX_BENCH_PIPELINE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("BENCH_STUB_FRAME", str(tmp_path / "frame.npy"))
+    monkeypatch.setenv("OMP_NUM_THREADS", "2")
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: calls.append("cpu_baseline") or {"value": 1.0})
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--width", "40", "--height", "24", "--spp", "2", "--scene", "spheres"] + list(extra)
+    bench.run_rank(bench.parse_args(argv), Frame)
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), calls
+
+
+def test_plain_run_does_only_what_the_headline_needs(monkeypatch, tmp_path, capsys):
+    d, calls = _one_rank(monkeypatch, tmp_path, capsys, [])
+    assert calls == ["count"] + ["step"] * 5                            # one counting launch, W warm-up + K timed frames
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in d
+    assert "cpu_baseline" not in d and "fast_shading_mode" not in d and "outputs" not in d
+    assert d["config"]["first_frame_kernel_ms"] is None
+
+
+def test_full_run_adds_the_side_legs(monkeypatch, tmp_path, capsys):
+    d, calls = _one_rank(monkeypatch, tmp_path, capsys, ["--full"])
+    assert calls == ["first_frame", "count"] + ["step"] * 2 + ["count"] + ["step"] * 3 + ["verify_frame", "fast_leg", "cpu_baseline"]
+    assert d["steps"] == 3 and d["cpu_baseline"] == {"value": 1.0} and d["fast_shading_mode"] == {"value": 1.0}
+    assert d["config"]["first_frame_kernel_ms"] == 1.0
+    _, calls = _one_rank(monkeypatch, tmp_path, capsys, ["--full", "--no-cpu-baseline", "--no-fast-leg"])
+    assert "cpu_baseline" not in calls and "fast_leg" not in calls and "first_frame" in calls
+
+
+def test_dump_outputs_writes_the_last_timed_frame(monkeypatch, tmp_path, capsys):
+    out = tmp_path / "dump"
+    d, calls = _one_rank(monkeypatch, tmp_path, capsys, ["--dump-outputs", str(out)])
+    assert calls == ["count"] + ["step"] * 5
+    got = np.load(out / "accum.npy")
+    assert got.dtype == np.float32 and got.shape == (24, 40, 3) and got.any()
+    assert np.array_equal(got, np.load(tmp_path / "frame.npy"))      # what the last step rendered
+    assert d["outputs"]["arrays"] == {"accum": [24, 40, 3]}
+    from common import M, hostsim_render
+    ref, _ = hostsim_render(M.HostScene("spheres", 40, 24), M.launch_seeds(2))
+    assert np.array_equal(got, ref)                                   # same inputs as any other run with these arguments
+
+
+def test_dump_outputs_samples_past_the_size_limit(tmp_path):
+    img = np.arange(30 * 20 * 3, dtype=np.float32).reshape(30, 20, 3)
+    w = bench.write_outputs(str(tmp_path / "a"), {"accum": img}, limit=img.nbytes // 4)
+    assert w == {"accum_sample": [150, 3]} and not (tmp_path / "a" / "accum.npy").exists()
+    s = np.load(tmp_path / "a" / "accum_sample.npy")
+    assert s.dtype == np.float32 and s.nbytes <= img.nbytes // 4
+    rows = img.reshape(-1, 3)
+    idx = (s[:, 0] / 3).astype(int)                                   # each sampled row is a whole pixel of the frame, in order
+    assert np.array_equal(s, rows[idx]) and (np.diff(idx) > 0).all()
+    bench.write_outputs(str(tmp_path / "b"), {"accum": img}, limit=img.nbytes // 4)
+    assert np.array_equal(s, np.load(tmp_path / "b" / "accum_sample.npy"))     # fixed seed: the same pixels every run
+    assert bench.write_outputs(str(tmp_path / "c"), {"accum": img}) == {"accum": [30, 20, 3]}
+
+
+def test_gpus_2_dump_outputs_on_cpu(tmp_path):
+    """Two ranks (the CPU stand-in): rank 0 writes the collected frame of the last timed step."""
+    rc, lines, text = _stub_two_ranks(tmp_path, {}, extra=["--dump-outputs", str(tmp_path / "dump")])
+    assert rc == 0 and len(lines) == 1, text[-2000:]
+    got = np.load(tmp_path / "dump" / "accum.npy")
+    assert np.array_equal(got, np.load(tmp_path / "frame.npy")) and lines[0]["outputs"]["arrays"] == {"accum": [24, 40, 3]}

@@ -606,3 +606,29 @@ def test_the_known_grazing_hit_is_tree_dependent_and_nothing_else(gpu_ctx):
     assert int((d > 1e-5).sum()) == 1 and rmse(g128 / 2, o / 2) <= 1e-3
     keep = d <= 1e-5
     assert rmse((g128 / 2)[keep], (o / 2)[keep]) <= RMSE_TIGHT
+
+
+def test_bench_dump_outputs_is_the_frame_the_library_renders(gpu_ctx, tmp_path):
+    """`bench.py --dump-outputs DIR`, plain and with --full (whose side legs render into the same buffer after the timed frames): DIR/accum.npy is
+    the last timed frame, bit for bit the accumulation buffer the library gives for the same scene and seeds."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from common import REPO
+    W, H, spp = 160, 90, 4
+    got = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        d = tmp_path / name
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", str(W),
+                            "--height", str(H), "--spp", str(spp), "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2000:])
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["outputs"]["arrays"] == {"accum": [H, W, 3]}
+        assert ("fast_shading_mode" in line) == (name == "full")
+        got[name] = np.load(d / "accum.npy")
+    gpu_ctx.load(M.HostScene("file:coffee", W, H))
+    gpu_ctx.accum_clear()
+    gpu_ctx.render(M.launch_seeds(spp))
+    ref = gpu_ctx.accum_read()
+    assert ref.any() and np.array_equal(got["plain"], ref) and np.array_equal(got["full"], ref)

@@ -149,7 +149,7 @@ def test_bench_py_two_ranks_on_one_gpu(split, pipeline):
     import bench
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(bench.free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--width", "320", "--height", "180", "--spp", "8", "--no-cpu-baseline", "--no-fast-leg", "--split", split]
+           "--width", "320", "--height", "180", "--spp", "8", "--no-cpu-baseline", "--no-fast-leg", "--split", split, "--full"]
     p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

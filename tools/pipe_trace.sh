@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 ROOT=$(pwd); O=$ROOT/gpurun_out/r05f; mkdir -p $O
 export MOPTIX_BENCH_PIPELINE=1
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/pipe -- python3 $ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-fast-leg > $O/pipe.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/pipe -- python3 $ROOT/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-fast-leg > $O/pipe.log 2>&1)
 python3 - <<PY
 import csv, glob
 rows = []

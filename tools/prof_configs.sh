@@ -15,7 +15,7 @@ for cfg in ${CONFIGS:-c2 c4 c5}; do
     c4) A="--scene dining_standin --iarg 6 --width 1920 --height 1080 --spp 16";;
     c5) A="--scene million_standin --iarg 1000000 --width 1920 --height 1080 --spp 16";;
   esac
-  P="$A --steps 2 --warmup 1 --no-cpu-baseline --no-fast-leg"
+  P="$A --full --steps 2 --warmup 1 --no-cpu-baseline --no-fast-leg"
   run $cfg kt "$P" --kernel-trace --stats
   run $cfg sq "$P" --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY
   run $cfg ta "$P" --kernel-trace --pmc TA_TA_BUSY_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE
@@ -24,7 +24,7 @@ for cfg in ${CONFIGS:-c2 c4 c5}; do
   run $cfg l2 "$P" --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum
   python3 tools/make_traffic_json.py $OUT/$cfg $OUT/${TAG}_traffic_$cfg.json "$A" > $OUT/${cfg}_traffic.log 2>&1
   cp $OUT/${TAG}_traffic_$cfg.json profiles/${TAG}_traffic_$cfg.json       # (on the box: the line below replays it)
-  python3 bench.py $A --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/line_$cfg.json
+  python3 bench.py $A --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/line_$cfg.json
   for f in $(find $OUT/$cfg/kt -name "*kernel_stats.csv"); do echo "== $cfg kernel stats"; head -6 $f | cut -c1-200; done
   echo "== $cfg line"; cut -c1-600 $OUT/line_$cfg.json
 done

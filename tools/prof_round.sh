@@ -15,7 +15,7 @@ fi
 if [ $STEP = all ] || [ $STEP = bench ]; then
   bash tools/prof_bench.sh $TAG > $O/prof_bench.log 2>&1; tail -5 $O/prof_bench.log
   cp gpurun_out/prof_bench_$TAG/traffic.json profiles/traffic.json          # (on the box) so that the line below replays this device code's counters
-  timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench_line.json
+  timeout 900 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench_line.json
 fi
 if [ $STEP = all ] || [ $STEP = configs ]; then
   bash tools/prof_configs.sh $TAG > $O/configs.log 2>&1; tail -12 $O/configs.log | cut -c1-300
