@@ -295,6 +295,40 @@ int moptix_accum_bind(moptix_context ctx, void* devPtr);
  * optionally clearing the accumulator. dstHost: W*H*3 bytes, row 0 = top. */
 int moptix_resolve_rgb8(moptix_context ctx, float nAccumulation, int clearBuffer, uint8_t* dstHost);
 
+/* ---- first-hit AOVs (new): guide layers for a denoiser, depth and ids for compositing / picking / masks ----------------
+ * For every pixel of the WHOLE frame (whatever moptix_set_partition says) and each seed s of the call, the primary ray the beauty
+ * pass traces for (pixel, s) -- the same origin on the lens, the same jitter -- is traced to its closest hit (rule D5: nearest t,
+ * then the lower primitive id), and per-pixel float32 sums are added to, in seed order:
+ *   buffer         per sample                                                                        on a miss
+ *   albedo (3)     colour of the hit's program: Lambertian / metal / glass -> albedo; Disney         bgColor
+ *                  non-glass -> Cdlin (srgb2lin of the texel when textured); Disney glass -> the
+ *                  tint of its refraction (colour or raw texel); light -> clamp(emission, 0, 1)
+ *   normal (3)     faceforward(shading normal, -d, geometric normal): world space, facing the camera (0,0,0)
+ *   depth (1)      t of the hit (distance along the normalised direction from the lens point)       nothing
+ *   hits (1)       1                                                                                 nothing
+ *   primId, matId  (int32) primitive id (spheres, quads, triangles in upload order, as               -1
+ *                  moptix_debug_trace reports it) and material of the hit -- from the first sample
+ *                  after a clear only
+ * Layout as the accumulation buffer: row 0 = bottom row, RGB triples interleaved.  Calls accumulate until moptix_aov_clear: seed
+ * lists A then B give the bits of one call with A + B; moptix_aov_samples counts the seeds added since the clear (divide by it;
+ * depth by hits).  A change of frame size in moptix_set_params clears them.  The buffers are allocated at the first AOV call.
+ * An AOV call changes nothing else: not the accumulation buffer, the depth history that orders work items ("tile_major"), the
+ * node-format verdict, moptix_kernel_time / moptix_reduce_time or the counters of a counted render.  The 64-byte nodes are walked
+ * where the tree has them, the 128-byte ones where it has not or where option "node_format" is 128 (same hits: rule D5; the one
+ * documented tree-dependent grazing hit applies, see the options below).
+ *   moptix_render_aovs  blocking; adds nSeeds samples (MOPTIX_ERR_STATE before params + build_accel)
+ *   moptix_aov_read     copies the buffers to host memory: W*H*3 floats (albedo, normal), W*H floats (depth, hits), W*H int32
+ *                       (primId, matId); NULL members are skipped
+ *   moptix_aov_bind     caller-owned device memory (e.g. torch tensors) of the same sizes instead of the own buffers; a NULL member
+ *                       keeps the own buffer of that AOV, a NULL argument restores all of them.  The sample count restarts at 0 and
+ *                       the bound memory is taken as it is: call moptix_aov_clear before the first render into it. */
+typedef struct moptix_aov_buffers { float *albedo, *normal, *depth, *hits; int32_t *primId, *matId; } moptix_aov_buffers;
+int moptix_render_aovs(moptix_context ctx, const int32_t* seeds, int32_t nSeeds);
+int moptix_aov_clear(moptix_context ctx);
+int moptix_aov_samples(moptix_context ctx, uint64_t* out);
+int moptix_aov_read(moptix_context ctx, const moptix_aov_buffers* dstHost);
+int moptix_aov_bind(moptix_context ctx, const moptix_aov_buffers* dstDevice);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --
  * and the number of its launches since the last reset */

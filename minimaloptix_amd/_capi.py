@@ -100,6 +100,12 @@ class RenderResult(C.Structure):
                 ("nFaces", C.c_uint64), ("nNodes", C.c_uint32), ("treeDepth", C.c_uint32)]
 
 
+class AovBuffers(C.Structure):
+    """moptix_aov_buffers: host (moptix_aov_read) or device (moptix_aov_bind) pointers; NULL members are skipped / keep the own buffer."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
+                ("primId", C.c_void_p), ("matId", C.c_void_p)]
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -111,6 +117,7 @@ DEVICE_SYMBOLS = [
     "moptix_resolve_rgb8", "moptix_kernel_time", "moptix_reduce_time", "moptix_debug_read_accel", "moptix_debug_read_nodes64", "moptix_debug_trace",
     "moptix_comm_unique_id", "moptix_comm_init", "moptix_comm_destroy", "moptix_gather_tiles", "moptix_reduce_frame",
     "moptix_packed_tile_floats", "moptix_pack_tiles", "moptix_unpack_tiles",
+    "moptix_render_aovs", "moptix_aov_clear", "moptix_aov_samples", "moptix_aov_read", "moptix_aov_bind",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
@@ -181,6 +188,11 @@ def device_lib():
         L.moptix_packed_tile_floats.argtypes = [vp, i32, C.POINTER(C.c_uint64)]
         L.moptix_pack_tiles.argtypes = [vp, i32, i32, vp]
         L.moptix_unpack_tiles.argtypes = [vp, i32, i32, vp]
+        L.moptix_render_aovs.argtypes = [vp, i32p, i32]
+        L.moptix_aov_clear.argtypes = [vp]
+        L.moptix_aov_samples.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.moptix_aov_read.argtypes = [vp, C.POINTER(AovBuffers)]
+        L.moptix_aov_bind.argtypes = [vp, C.POINTER(AovBuffers)]
         _dev = L
     return _dev
 

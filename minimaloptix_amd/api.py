@@ -318,6 +318,61 @@ class Context:
     def unpack_tiles(self, rank, nranks, src_device_ptr):
         self._chk(self._L.moptix_unpack_tiles(self._h, int(rank), int(nranks), C.c_void_p(src_device_ptr)))
 
+    # ---- first-hit AOVs (include/moptix.h "first-hit AOVs") ----
+    AOV_NAMES = ("albedo", "normal", "depth", "hits", "primId", "matId")
+    AOV_CHANNELS = dict(albedo=3, normal=3, depth=1, hits=1, primId=1, matId=1)
+
+    def render_aovs(self, seeds):
+        """Adds one first-hit sample per seed to every pixel's AOV sums (whole frame; blocking)."""
+        s, p = self._seeds(seeds)
+        self._chk(self._L.moptix_render_aovs(self._h, p, len(s)))
+
+    def aov_clear(self):
+        self._chk(self._L.moptix_aov_clear(self._h))
+
+    def aov_samples(self):
+        n = C.c_uint64()
+        self._chk(self._L.moptix_aov_samples(self._h, C.byref(n)))
+        return int(n.value)
+
+    def aov_read(self):
+        """{name: (H, W, k) array} in the accumulation buffer's row order (row 0 = bottom): albedo, normal (k = 3), depth, hits
+        (float32, k = 1), primId, matId (int32, k = 1)."""
+        out = {n: np.empty((self.height, self.width, self.AOV_CHANNELS[n]), np.int32 if n in ("primId", "matId") else np.float32)
+               for n in self.AOV_NAMES}
+        b = K.AovBuffers(*[out[n].ctypes.data for n in self.AOV_NAMES])
+        self._chk(self._L.moptix_aov_read(self._h, C.byref(b)))
+        return out
+
+    def aov_bind(self, tensors):
+        """tensors: {name: torch tensor on this context's device, contiguous, (H, W, k) of float32 (int32 for the ids)}; a missing
+        name keeps the context's own buffer, None restores all of them.  Call aov_clear() before the first render into them."""
+        if tensors is None:
+            self._chk(self._L.moptix_aov_bind(self._h, None))
+            return
+        ptrs = []
+        for n in self.AOV_NAMES:
+            t = tensors.get(n)
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not t.is_contiguous() or t.numel() != self.height * self.width * self.AOV_CHANNELS[n]:
+                raise ValueError("aov_bind: %s must be a contiguous tensor of %d x %d x %d elements" % (n, self.height, self.width, self.AOV_CHANNELS[n]))
+            if str(t.dtype) != ("torch.int32" if n in ("primId", "matId") else "torch.float32"):
+                raise ValueError("aov_bind: %s has dtype %s" % (n, t.dtype))
+            ptrs.append(t.data_ptr())
+        b = K.AovBuffers(*ptrs)
+        self._chk(self._L.moptix_aov_bind(self._h, C.byref(b)))
+
+    def aov_means(self):
+        """albedo / samples, normal / samples, depth / hits (inf where hits == 0), as (H, W, k) float32 arrays."""
+        a = self.aov_read()
+        n = np.float32(max(1, self.aov_samples()))
+        hits = a["hits"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            depth = np.where(hits > 0, a["depth"] / np.where(hits > 0, hits, np.float32(1)), np.float32(np.inf)).astype(np.float32)
+        return dict(albedo=(a["albedo"] / n).astype(np.float32), normal=(a["normal"] / n).astype(np.float32), depth=depth)
+
     def debug_read_accel(self):
         a = self.accel_info()
         nodes = np.zeros((max(1, a.nNodes), 32), np.uint32)     # Node128 = 32 words

@@ -41,6 +41,7 @@ ncclResult_t ncclCommAbort(ncclComm_t comm);
 #include <vector>
 
 #include "../../include/moptix.h"
+#include "aovkernel.h"
 #include "lbvh.h"
 #include "megakernel.h"
 #include "pt_upload.h"
@@ -134,6 +135,12 @@ struct moptix_context_t {
   // multi-GPU (one process per GPU): RCCL communicator of this rank + staging for the tile gather
   ncclComm_t comm = nullptr; int commRank = 0, commRanks = 1;
   DevBuf<float> dTileSend, dTileRecv;
+  // first-hit AOVs (moptix_render_aovs): allocated at the first AOV call; a bound member (moptix_aov_bind) replaces the own buffer
+  DevBuf<float> dAovAlbedo, dAovNormal, dAovDepth, dAovHits; DevBuf<int> dAovPrim, dAovMat;
+  moptix_aov_buffers aovBound{};
+  size_t aovPixels = 0;              // frame size the AOV buffers hold (0 = to be (re)allocated and cleared at the next AOV call)
+  uint64_t aovSamples = 0;           // seeds added since the clear
+  DevBuf<int> dAovSeeds, dAovWork, dAovOverflow;
 };
 
 namespace {
@@ -699,6 +706,8 @@ int moptix_destroy(moptix_context c) {
   c->dTileCost.release(); c->dTileCostSorted.release(); c->dTileOrder.release(); c->dTileIota.release(); c->dSortTmp.release();
   c->dAccum.release(); c->dSeeds.release(); c->dWork.release(); c->dCounters.release(); c->dOverflow.release(); c->dRgb8.release();
   c->dTileSend.release(); c->dTileRecv.release();
+  c->dAovAlbedo.release(); c->dAovNormal.release(); c->dAovDepth.release(); c->dAovHits.release(); c->dAovPrim.release(); c->dAovMat.release();
+  c->dAovSeeds.release(); c->dAovWork.release(); c->dAovOverflow.release();
   if (c->comm) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -730,6 +739,7 @@ int moptix_set_params(moptix_context c, const moptix_params* p) {
   if (!c->haveParams || resized) c->formatDecided = false;
   c->params = *p; c->haveParams = true;
   if (resized && !c->accumBound) { c->accumPixels = 0; }
+  if (resized) { c->aovPixels = 0; c->aovSamples = 0; }      // the AOVs are reallocated and cleared at the next AOV call
   return MOPTIX_OK;
 }
 
@@ -1143,6 +1153,123 @@ int moptix_debug_trace(moptix_context c, const float* rays, int32_t n, float* ou
   if (dP) (void)hipFree(dP);
   if (dOvf) (void)hipFree(dOvf);
   if (e != hipSuccess) return hipFail(c, e, "debug trace");
+  return MOPTIX_OK;
+}
+
+// ---- first-hit AOVs (aovkernel.hip, pt_aov.h) -------------------------------------------------------------------------------
+
+}  // extern "C"
+namespace {
+moptix_aov_buffers aov_ptrs(moptix_context c) {
+  const moptix_aov_buffers& b = c->aovBound;
+  return moptix_aov_buffers{ b.albedo ? b.albedo : c->dAovAlbedo.p, b.normal ? b.normal : c->dAovNormal.p, b.depth ? b.depth : c->dAovDepth.p,
+                             b.hits ? b.hits : c->dAovHits.p, b.primId ? b.primId : c->dAovPrim.p, b.matId ? b.matId : c->dAovMat.p };
+}
+int aov_zero(moptix_context c) {
+  const size_t px = c->aovPixels;
+  const moptix_aov_buffers p = aov_ptrs(c);
+  HIPCHK(c, hipMemsetAsync(p.albedo, 0, sizeof(float) * 3 * px, c->stream), "clear AOVs");
+  HIPCHK(c, hipMemsetAsync(p.normal, 0, sizeof(float) * 3 * px, c->stream), "clear AOVs");
+  HIPCHK(c, hipMemsetAsync(p.depth, 0, sizeof(float) * px, c->stream), "clear AOVs");
+  HIPCHK(c, hipMemsetAsync(p.hits, 0, sizeof(float) * px, c->stream), "clear AOVs");
+  HIPCHK(c, hipMemsetAsync(p.primId, 0xff, sizeof(int) * px, c->stream), "clear AOVs");      // -1
+  HIPCHK(c, hipMemsetAsync(p.matId, 0xff, sizeof(int) * px, c->stream), "clear AOVs");
+  c->aovSamples = 0;
+  return MOPTIX_OK;
+}
+// The AOV buffers for the current frame size: allocated at the first AOV call (contexts that never ask for AOVs hold none), and
+// cleared when the frame size changed since they were.
+int ensure_aov(moptix_context c) {
+  const size_t px = (size_t)c->params.width * c->params.height;
+  const moptix_aov_buffers& b = c->aovBound;
+  if (!b.albedo) HIPCHK(c, c->dAovAlbedo.ensure(3 * px), "alloc AOVs");
+  if (!b.normal) HIPCHK(c, c->dAovNormal.ensure(3 * px), "alloc AOVs");
+  if (!b.depth) HIPCHK(c, c->dAovDepth.ensure(px), "alloc AOVs");
+  if (!b.hits) HIPCHK(c, c->dAovHits.ensure(px), "alloc AOVs");
+  if (!b.primId) HIPCHK(c, c->dAovPrim.ensure(px), "alloc AOVs");
+  if (!b.matId) HIPCHK(c, c->dAovMat.ensure(px), "alloc AOVs");
+  if (c->aovPixels == px) return MOPTIX_OK;
+  c->aovPixels = px;
+  return aov_zero(c);
+}
+}  // namespace
+extern "C" {
+
+int moptix_render_aovs(moptix_context c, const int32_t* seeds, int32_t nSeeds) {
+  int rc = check_ready(c);
+  if (rc != MOPTIX_OK) return rc;
+  if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;     // a beauty batch still in flight finishes (and is timed) first
+  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  if (nSeeds == 0) { HIPCHK(c, hipStreamSynchronize(c->stream), "sync"); return MOPTIX_OK; }
+  if ((long long)((c->params.width + 7) / 8) * ((c->params.height + 7) / 8) > 0x7fffffffLL) return fail(c, MOPTIX_ERR_LIMIT, "frame too large");
+  AovArgs a;
+  memset(&a, 0, sizeof(a));
+  fill_view(c, a.scene);                                  // the whole frame: partition and node-format verdict are not consulted
+  const bool node64 = c->bvh.nodes64 != nullptr && c->optNodeFormat != 128 && a.scene.rootRef != kEmptyRef;
+  a.scene.nodes64 = node64 ? c->bvh.nodes64 : nullptr;
+  std::vector<int> staged(seeds, seeds + nSeeds);
+  HIPCHK(c, c->dAovSeeds.upload(staged, c->stream), "upload AOV seeds");
+  a.seeds = c->dAovSeeds.p; a.nSeeds = nSeeds;
+  a.writeIds = c->aovSamples == 0 ? 1 : 0;
+  const moptix_aov_buffers p = aov_ptrs(c);
+  a.albedo = p.albedo; a.normal = p.normal; a.depth = p.depth; a.hits = p.hits; a.primId = p.primId; a.matId = p.matId;
+  const size_t ovf = aovkernel_overflow_ints(c->numCUs, c->bvh.stackBound);
+  if (ovf > 0 && a.scene.rootRef != kEmptyRef) {
+    HIPCHK(c, c->dAovOverflow.ensure(ovf), "alloc AOV stack overflow area");
+    a.stackOverflow = c->dAovOverflow.p;
+  }
+  HIPCHK(c, c->dAovWork.ensure(1), "alloc AOV tile counter");
+  HIPCHK(c, launch_aovkernel(c->stream, a, c->numCUs, c->dAovWork.p, node64), "launch AOV kernel");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "AOV kernel");     // also: `staged` dies here
+  c->aovSamples += (uint64_t)nSeeds;
+  return MOPTIX_OK;
+}
+
+int moptix_aov_clear(moptix_context c) {
+  if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  if ((rc = aov_zero(c)) != MOPTIX_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  return MOPTIX_OK;
+}
+
+int moptix_aov_samples(moptix_context c, uint64_t* out) {
+  if (!c || !out) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  *out = c->aovSamples;
+  return MOPTIX_OK;
+}
+
+int moptix_aov_read(moptix_context c, const moptix_aov_buffers* dst) {
+  if (!c || !dst) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  const size_t px = c->aovPixels;
+  const moptix_aov_buffers p = aov_ptrs(c);
+  if (dst->albedo) HIPCHK(c, hipMemcpyAsync(dst->albedo, p.albedo, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  if (dst->normal) HIPCHK(c, hipMemcpyAsync(dst->normal, p.normal, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  if (dst->depth) HIPCHK(c, hipMemcpyAsync(dst->depth, p.depth, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  if (dst->hits) HIPCHK(c, hipMemcpyAsync(dst->hits, p.hits, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  if (dst->primId) HIPCHK(c, hipMemcpyAsync(dst->primId, p.primId, sizeof(int) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  if (dst->matId) HIPCHK(c, hipMemcpyAsync(dst->matId, p.matId, sizeof(int) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  return MOPTIX_OK;
+}
+
+int moptix_aov_bind(moptix_context c, const moptix_aov_buffers* dstDevice) {
+  if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  c->aovBound = dstDevice ? *dstDevice : moptix_aov_buffers{};
+  c->aovSamples = 0;                 // the bound memory is taken as it is (moptix_aov_clear zeroes it)
   return MOPTIX_OK;
 }
 

@@ -19,6 +19,7 @@ static void usage() {
           "usage: moptix_render [--scene spheres|coffee|cornell_quads|random_spheres|random_spheres_256|dining_standin|million_standin|coffee_pot_standin|<file scene>]\n"
           "                     [--spp N] [--width W] [--height H] [--seed S] [--scenes DIR/] [--out PREFIX] [--outdir DIR]\n"
           "                     [--autosave] [--device D] [--random-seeds] [--strict-missing]\n"
+          "                     [--aov]  also PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm: first-hit AOVs of the same seeds (rank 0)\n"
           "       multi-GPU (one process per GPU, tile split + RCCL gather to rank 0, which writes the image):\n"
           "                     [--spawn N]  start N ranks of this program, rank r on device r, and wait for them\n"
           "                     [--spawn-same-device]  ... every rank on --device (a one-GPU box; needs a transport that accepts it,\n"
@@ -29,7 +30,7 @@ static void usage() {
 int main(int argc, char** argv) {
   std::string scene = "spheres", prefix = "frame", scenes = "scenes/", outdir = ".";
   unsigned spp = 32, width = 1920, height = 1080, seed = 0;
-  int device = 0; bool autosave = false, randomSeeds = false, strict = false;
+  int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false;
   int rank = 0, ranks = 1, spawn = 0, spawnTimeout = 600; bool spawnSame = false; std::string commFile;
   for (int i = 1; i < argc; i++) {
     auto need = [&](const char* n) { if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", n); exit(2); } return argv[++i]; };
@@ -51,6 +52,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--autosave")) autosave = true;
     else if (!strcmp(argv[i], "--random-seeds")) randomSeeds = true;
     else if (!strcmp(argv[i], "--strict-missing")) strict = true;
+    else if (!strcmp(argv[i], "--aov")) aov = true;
     else { usage(); return 2; }
   }
   if (spawn > 0) {
@@ -120,6 +122,7 @@ int main(int argc, char** argv) {
     else { usage(); return 2; }
     app.renderScene(autosave, prefix);
     if (!autosave && rank == 0) app.saveCurrentFrame(false, prefix);
+    if (aov && rank == 0) app.saveAovs(prefix);               // whole frame, on rank 0's context alone: no collective
     fprintf(stderr, "render %.3f ms (device), BVH build %.3f ms, %u nodes, depth %u\n", app.lastRenderMs,
             app.lastAccel.buildMs, app.lastAccel.nNodes, app.lastAccel.treeDepth);
   } catch (const std::exception& e) {

@@ -114,6 +114,7 @@ void MinimalOptiX::renderScene(bool autoSave, std::string fileNamePrefix) {
   moptix_kernel_time(context, nullptr, nullptr, 1);
   std::vector<int32_t> seeds(nSuperSampling);
   for (uint i = 0; i < nSuperSampling; ++i) seeds[i] = randSeed();   // :545 one seed per launch
+  lastSeeds = seeds;
   uint checkpoint = 1;
   uint done = 0;
   while (done < nSuperSampling) {
@@ -147,6 +148,25 @@ void MinimalOptiX::saveCurrentFrame(bool popUpDialog, std::string fileNamePrefix
   std::string fileName = outputDir + "/" + (fileNamePrefix.empty() ? std::string("frame") : fileNamePrefix) + ".png";
   if (!writePNG(fileName, canvas.data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + fileName);
   if (verbose) fprintf(stderr, "Image saved to %s\n", fileName.c_str());
+}
+
+void MinimalOptiX::saveAovs(std::string fileNamePrefix) {
+  check(moptix_aov_clear(context), "AOV clear");
+  check(moptix_render_aovs(context, lastSeeds.data(), (int32_t)lastSeeds.size()), "render AOVs");
+  const size_t px = (size_t)fixedWidth * fixedHeight;
+  std::vector<float> albedo(3 * px), normal(3 * px), depth(px), hits(px), depth3(3 * px);
+  moptix_aov_buffers b = { albedo.data(), normal.data(), depth.data(), hits.data(), nullptr, nullptr };
+  check(moptix_aov_read(context, &b), "read AOVs");
+  uint64_t n = 0;
+  check(moptix_aov_samples(context, &n), "AOV samples");
+  const float fn = (float)(n > 0 ? n : 1);
+  for (size_t i = 0; i < 3 * px; i++) { albedo[i] = albedo[i] / fn; normal[i] = normal[i] / fn; }
+  for (size_t i = 0; i < px; i++) depth3[3 * i] = depth3[3 * i + 1] = depth3[3 * i + 2] = hits[i] > 0.f ? depth[i] / hits[i] : 0.f;
+  const std::string base = outputDir + "/" + (fileNamePrefix.empty() ? std::string("frame") : fileNamePrefix);
+  for (auto& f : { std::make_pair(std::string("_albedo.pfm"), &albedo), std::make_pair(std::string("_normal.pfm"), &normal), std::make_pair(std::string("_depth.pfm"), &depth3) }) {
+    if (!writePFM(base + f.first, f.second->data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + base + f.first);
+    if (verbose) fprintf(stderr, "AOV saved to %s\n", (base + f.first).c_str());
+  }
 }
 
 // MinimalOptiX.cpp:587-592

@@ -81,6 +81,12 @@ public:
 
   int randSeed();                     // utils_host.cpp:118-122 (next launch seed)
 
+  // first-hit AOVs (new; include/moptix.h): after renderScene(), the primary rays of the same seeds (whole frame) -> PREFIX_albedo.pfm,
+  // PREFIX_normal.pfm (means over the seeds) and PREFIX_depth.pfm (mean depth of the samples that hit, 0 where none did, in three equal
+  // channels) in outputDir
+  std::vector<int32_t> lastSeeds;     // the launch seeds of the last renderScene()
+  void saveAovs(std::string fileNamePrefix);
+
 private:
   uint launchCounter = 0;
   void check(int rc, const char* what);
