@@ -329,6 +329,55 @@ int moptix_aov_samples(moptix_context ctx, uint64_t* out);
 int moptix_aov_read(moptix_context ctx, const moptix_aov_buffers* dstHost);
 int moptix_aov_bind(moptix_context ctx, const moptix_aov_buffers* dstDevice);
 
+/* ---- denoiser (new): edge-aware a-trous filter guided by the first-hit AOVs -------------------------------------------------
+ * The edge-avoiding a-trous wavelet transform (Dammertz et al. 2010) with SVGF's luminance-variance edge stop (Schied et al. 2017),
+ * spatial part only.  Inputs per pixel p (row 0 = bottom, the accumulation buffer's layout), S = moptix_aov_samples:
+ *   C_p = accum_p / nAccumulation      the beauty mean (nAccumulation as in moptix_resolve_rgb8)
+ *   A_p = albedo_p / S,  N_p = normalize(normal_p / S) (0 where that is 0),  Z_p = depth_p / hits_p
+ * p is a geometry pixel iff hits_p > 0.  A background pixel (hits 0) outputs C_p bit for bit and is never a tap.
+ * Demodulation (demodulate = 1): the filter works on I_p = C_p / max(A_p, 1e-3) per channel and outputs I'_p * max(A_p, 1e-3);
+ * demodulate = 0 (the default): I = C.  The albedo AOV is the first hit's program colour, which on coffee's metal, glass and
+ * near-zero albedo channels is far from what the beauty reflects: demodulated, 4 spp there come out 3.7x worse than undenoised
+ * (DESIGN.md "Denoiser").
+ * Prepass: luminance l(I) = 0.2126 r + 0.7152 g + 0.0722 b.  Variance v_p = E[l^2] - E[l]^2 (biased) of l over the geometry pixels
+ * of the 3x3 window, clamped at 0.  Depth gradient g_p = max over the two axes of |Z+ - Z-| / 2 (both neighbours geometry),
+ * |Z_n - Z_p| (one of them), 0 (none).
+ * Iteration i = 0 .. L-1, step = 2^i, taps q = p + step (dx, dy), dx, dy in -2..2; taps outside the frame or on background skipped:
+ *   w   = h(dx) h(dy) w_n w_z w_l,  h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *   w_n = max(0, N_p . N_q)^normalPower  (integer power by binary exponentiation, least significant bit first:
+ *         r = 1, b = x; loop { if (n & 1) r = r * b; n >>= 1; if (n == 0) stop; b = b * b; } -- no powf)
+ *   w_z = exp(-|Z_p - Z_q| / (sigmaDepth * step (|dx| + |dy|) * g_p + 1e-4))
+ *   w_l = exp(-|l_p - l_q| / (sigmaLuminance * sqrt(G3(v)_p) + 1e-4)),  G3 = the 3x3 (1/4, 1/2, 1/4) blur of v over geometry pixels
+ *   I'_p = sum w I_q / sum w,  v'_p = sum w^2 v_q / (sum w)^2
+ *   the centre tap has w = h(0)^2 = 9/64 (its w_n, w_z, w_l are 1), so sum w > 0 even where N_p cancelled to 0; taps are summed in
+ *   row-major order (dy outer, dx inner) with plain adds.
+ * iterations = 0 returns C bit for bit (no demodulation).  Arithmetic: the contract of csrc/pt_math.h (AC1-AC5, no contraction);
+ * exp is exp_ac (csrc/pt_denoise.h: Cody-Waite reduction by ln 2 with fma, a fixed polynomial, 2^k from its bits; 0 below x = -87,
+ * exactly 1 at 0); no libm transcendental, so that host and device give the same bits.
+ * Ranges: iterations 0..8 (default 5), normalPower 1..256 (128), demodulate 0 / 1 (0), sigmaLuminance >= 0 (4), sigmaDepth >= 0 (1),
+ * finite; nAccumulation > 0.  Bad values -> MOPTIX_ERR_INVALID.
+ *   moptix_denoise_defaults  the defaults above; pure host (works without a device)
+ *   moptix_denoise           blocking, on the context's stream (moptix_set_stream).  MOPTIX_ERR_STATE before moptix_set_params or
+ *                            while moptix_aov_samples is 0 (e.g. after a frame-size change, until AOVs are rendered again).  Reads
+ *                            the accumulation buffer and the AOVs wherever they are bound and changes nothing else: not those
+ *                            buffers or the AOV sample count, the depth history, the node-format verdict, moptix_kernel_time /
+ *                            moptix_reduce_time.  Scratch and output are allocated at the first call, freed by a frame-size change
+ *                            and by moptix_destroy.
+ *   moptix_denoise_read      copies the output to host memory: W*H*3 floats in the accumulation buffer's layout (MOPTIX_ERR_STATE
+ *                            when nothing was denoised since the last frame-size change)
+ *   moptix_denoise_bind      caller-owned device memory of W*H*3 floats that later calls write instead of the own buffer; NULL
+ *                            restores the own buffer.  The binding survives a frame-size change: the caller sizes the memory.
+ * Tile split (moptix_set_partition): the accumulation buffer holds this rank's tiles only -- call the denoiser on the destination rank
+ * of moptix_gather_tiles, after the gather. */
+typedef struct moptix_denoise_params {
+  int32_t iterations, normalPower, demodulate;
+  float sigmaLuminance, sigmaDepth;
+} moptix_denoise_params;
+int moptix_denoise_defaults(moptix_denoise_params* out);
+int moptix_denoise(moptix_context ctx, const moptix_denoise_params* p, float nAccumulation);
+int moptix_denoise_read(moptix_context ctx, float* dstHost);
+int moptix_denoise_bind(moptix_context ctx, float* dstDevice);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --
  * and the number of its launches since the last reset */

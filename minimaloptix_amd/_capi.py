@@ -106,6 +106,12 @@ class AovBuffers(C.Structure):
                 ("primId", C.c_void_p), ("matId", C.c_void_p)]
 
 
+class DenoiseParams(C.Structure):
+    """moptix_denoise_params (include/moptix.h "denoiser")."""
+    _fields_ = [("iterations", C.c_int32), ("normalPower", C.c_int32), ("demodulate", C.c_int32),
+                ("sigmaLuminance", C.c_float), ("sigmaDepth", C.c_float)]
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -118,6 +124,7 @@ DEVICE_SYMBOLS = [
     "moptix_comm_unique_id", "moptix_comm_init", "moptix_comm_destroy", "moptix_gather_tiles", "moptix_reduce_frame",
     "moptix_packed_tile_floats", "moptix_pack_tiles", "moptix_unpack_tiles",
     "moptix_render_aovs", "moptix_aov_clear", "moptix_aov_samples", "moptix_aov_read", "moptix_aov_bind",
+    "moptix_denoise_defaults", "moptix_denoise", "moptix_denoise_read", "moptix_denoise_bind",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
@@ -193,6 +200,10 @@ def device_lib():
         L.moptix_aov_samples.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.moptix_aov_read.argtypes = [vp, C.POINTER(AovBuffers)]
         L.moptix_aov_bind.argtypes = [vp, C.POINTER(AovBuffers)]
+        L.moptix_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
+        L.moptix_denoise.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float]
+        L.moptix_denoise_read.argtypes = [vp, f32p]
+        L.moptix_denoise_bind.argtypes = [vp, vp]
         _dev = L
     return _dev
 

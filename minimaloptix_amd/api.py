@@ -373,6 +373,35 @@ class Context:
             depth = np.where(hits > 0, a["depth"] / np.where(hits > 0, hits, np.float32(1)), np.float32(np.inf)).astype(np.float32)
         return dict(albedo=(a["albedo"] / n).astype(np.float32), normal=(a["normal"] / n).astype(np.float32), depth=depth)
 
+    # ---- denoiser (include/moptix.h "denoiser") ----
+    def denoise_defaults(self):
+        """moptix_denoise_defaults as a dict: iterations, normal_power, sigma_luminance, sigma_depth, demodulate."""
+        p = K.DenoiseParams()
+        self._chk(self._L.moptix_denoise_defaults(C.byref(p)))
+        return dict(iterations=int(p.iterations), normal_power=int(p.normalPower), sigma_luminance=float(p.sigmaLuminance),
+                    sigma_depth=float(p.sigmaDepth), demodulate=bool(p.demodulate))
+
+    def denoise(self, n_accumulation, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0, demodulate=False):
+        """The accumulation buffer's mean (accum / n_accumulation) filtered under the guidance of the AOVs (render_aovs first);
+        blocking.  Returns an (H, W, 3) float32 array in accum_read's row order (row 0 = bottom)."""
+        p = K.DenoiseParams(int(iterations), int(normal_power), 1 if demodulate else 0, float(sigma_luminance), float(sigma_depth))
+        self._chk(self._L.moptix_denoise(self._h, C.byref(p), float(n_accumulation)))
+        out = np.empty((self.height, self.width, 3), np.float32)
+        self._chk(self._L.moptix_denoise_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise_bind(self, tensor):
+        """tensor: torch float32 tensor on this context's device, contiguous, H*W*3 elements, that later denoise calls write; None
+        restores the context's own output buffer."""
+        if tensor is None:
+            self._chk(self._L.moptix_denoise_bind(self._h, None))
+            return
+        if not tensor.is_contiguous() or tensor.numel() != self.height * self.width * 3:
+            raise ValueError("denoise_bind: must be a contiguous tensor of %d x %d x 3 elements" % (self.height, self.width))
+        if str(tensor.dtype) != "torch.float32":
+            raise ValueError("denoise_bind: dtype %s" % tensor.dtype)
+        self._chk(self._L.moptix_denoise_bind(self._h, C.c_void_p(tensor.data_ptr())))
+
     def debug_read_accel(self):
         a = self.accel_info()
         nodes = np.zeros((max(1, a.nNodes), 32), np.uint32)     # Node128 = 32 words

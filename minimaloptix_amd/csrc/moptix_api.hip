@@ -42,6 +42,7 @@ ncclResult_t ncclCommAbort(ncclComm_t comm);
 
 #include "../../include/moptix.h"
 #include "aovkernel.h"
+#include "denoisekernel.h"
 #include "lbvh.h"
 #include "megakernel.h"
 #include "pt_upload.h"
@@ -141,6 +142,11 @@ struct moptix_context_t {
   size_t aovPixels = 0;              // frame size the AOV buffers hold (0 = to be (re)allocated and cleared at the next AOV call)
   uint64_t aovSamples = 0;           // seeds added since the clear
   DevBuf<int> dAovSeeds, dAovWork, dAovOverflow;
+  // denoiser (moptix_denoise): scratch and output allocated at the first call, freed by a frame-size change; a bound output
+  // (moptix_denoise_bind) replaces the own one
+  DevBuf<pt::v4> dDnColA, dDnColB, dDnGuide, dDnSide; DevBuf<float> dDnOut;
+  float* dnBound = nullptr;
+  size_t dnPixels = 0;               // frame size of the last denoise call (0: none since the last frame-size change)
 };
 
 namespace {
@@ -155,6 +161,11 @@ int hipFail(moptix_context c, hipError_t e, const char* what) {
 #define HIPCHK(c, x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hipFail((c), e_, (what)); } while (0)
 
 float* accum_ptr(moptix_context c) { return c->accumBound ? c->accumBound : c->dAccum.p; }
+
+void dn_release(moptix_context c) {
+  c->dDnColA.release(); c->dDnColB.release(); c->dDnGuide.release(); c->dDnSide.release(); c->dDnOut.release();
+  c->dnPixels = 0;
+}
 
 int ensure_accum(moptix_context c) {
   const size_t px = (size_t)c->params.width * c->params.height;
@@ -708,6 +719,7 @@ int moptix_destroy(moptix_context c) {
   c->dTileSend.release(); c->dTileRecv.release();
   c->dAovAlbedo.release(); c->dAovNormal.release(); c->dAovDepth.release(); c->dAovHits.release(); c->dAovPrim.release(); c->dAovMat.release();
   c->dAovSeeds.release(); c->dAovWork.release(); c->dAovOverflow.release();
+  dn_release(c);
   if (c->comm) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -740,6 +752,7 @@ int moptix_set_params(moptix_context c, const moptix_params* p) {
   c->params = *p; c->haveParams = true;
   if (resized && !c->accumBound) { c->accumPixels = 0; }
   if (resized) { c->aovPixels = 0; c->aovSamples = 0; }      // the AOVs are reallocated and cleared at the next AOV call
+  if (resized) dn_release(c);                                // the denoiser's scratch and output are reallocated at its next call
   return MOPTIX_OK;
 }
 
@@ -1270,6 +1283,76 @@ int moptix_aov_bind(moptix_context c, const moptix_aov_buffers* dstDevice) {
   if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
   c->aovBound = dstDevice ? *dstDevice : moptix_aov_buffers{};
   c->aovSamples = 0;                 // the bound memory is taken as it is (moptix_aov_clear zeroes it)
+  return MOPTIX_OK;
+}
+
+// ---- denoiser (denoisekernel.hip, pt_denoise.h) -----------------------------------------------------------------------------
+
+int moptix_denoise_defaults(moptix_denoise_params* out) {
+  if (!out) return fail(nullptr, MOPTIX_ERR_INVALID, "null argument");
+  out->iterations = 5; out->normalPower = 128; out->demodulate = 0;
+  out->sigmaLuminance = 4.0f; out->sigmaDepth = 1.0f;
+  return MOPTIX_OK;
+}
+
+int moptix_denoise(moptix_context c, const moptix_denoise_params* p, float nAccumulation) {
+  if (!c || !p) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  if (!(nAccumulation > 0.0f) || !__builtin_isfinite(nAccumulation)) return fail(c, MOPTIX_ERR_INVALID, "nAccumulation must be > 0");
+  if (p->iterations < 0 || p->iterations > 8) return fail(c, MOPTIX_ERR_INVALID, "iterations in [0,8]");
+  if (p->normalPower < 1 || p->normalPower > 256) return fail(c, MOPTIX_ERR_INVALID, "normalPower in [1,256]");
+  if (p->demodulate != 0 && p->demodulate != 1) return fail(c, MOPTIX_ERR_INVALID, "demodulate is 0 or 1");
+  if (!(p->sigmaLuminance >= 0.0f) || !__builtin_isfinite(p->sigmaLuminance) || !(p->sigmaDepth >= 0.0f) || !__builtin_isfinite(p->sigmaDepth))
+    return fail(c, MOPTIX_ERR_INVALID, "sigmas must be finite and >= 0");
+  if (c->poisoned) return fail(c, MOPTIX_ERR_COMM, "this context is unusable: kernels of an aborted collective never left its stream");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "moptix_set_params has not been called");
+  if (c->aovSamples == 0) return fail(c, MOPTIX_ERR_STATE, "no AOV samples: moptix_render_aovs first");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;       // a beauty batch still in flight finishes (and is timed) first
+  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  const size_t px = (size_t)c->params.width * c->params.height;
+  if (px > 0x7fffffffULL) return fail(c, MOPTIX_ERR_LIMIT, "frame too large");
+  HIPCHK(c, c->dDnColA.ensure(px), "alloc denoiser");
+  HIPCHK(c, c->dDnColB.ensure(px), "alloc denoiser");
+  HIPCHK(c, c->dDnGuide.ensure(px), "alloc denoiser");
+  HIPCHK(c, c->dDnSide.ensure(px), "alloc denoiser");
+  if (!c->dnBound) HIPCHK(c, c->dDnOut.ensure(3 * px), "alloc denoiser output");
+  DenoiseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.k.width = (int)c->params.width; a.k.height = (int)c->params.height; a.k.normalPower = p->normalPower;
+  a.k.sigmaLuminance = p->sigmaLuminance; a.k.sigmaDepth = p->sigmaDepth;
+  const moptix_aov_buffers b = aov_ptrs(c);
+  a.accum = accum_ptr(c); a.albedo = b.albedo; a.normal = b.normal; a.depth = b.depth; a.hits = b.hits;
+  a.nAccumulation = nAccumulation; a.nSamples = (float)c->aovSamples;
+  a.iterations = p->iterations; a.demodulate = p->iterations > 0 ? p->demodulate : 0;
+  a.colA = c->dDnColA.p; a.colB = c->dDnColB.p; a.guide = c->dDnGuide.p; a.side = c->dDnSide.p;
+  a.out = c->dnBound ? c->dnBound : c->dDnOut.p;
+  HIPCHK(c, launch_denoise(c->stream, a), "launch denoiser");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "denoiser");
+  c->dnPixels = px;
+  return MOPTIX_OK;
+}
+
+int moptix_denoise_read(moptix_context c, float* dstHost) {
+  if (!c || !dstHost) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
+  const size_t px = (size_t)c->params.width * c->params.height;
+  if (c->dnPixels != px) return fail(c, MOPTIX_ERR_STATE, "nothing denoised at this frame size");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  const float* src = c->dnBound ? c->dnBound : c->dDnOut.p;
+  if (!src) return fail(c, MOPTIX_ERR_STATE, "the own output buffer holds nothing (it was bound when the denoiser last ran)");
+  HIPCHK(c, hipMemcpyAsync(dstHost, src, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read denoiser output");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  return MOPTIX_OK;
+}
+
+int moptix_denoise_bind(moptix_context c, float* dstDevice) {
+  if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  c->dnBound = dstDevice;
   return MOPTIX_OK;
 }
 

@@ -20,6 +20,8 @@ static void usage() {
           "                     [--spp N] [--width W] [--height H] [--seed S] [--scenes DIR/] [--out PREFIX] [--outdir DIR]\n"
           "                     [--autosave] [--device D] [--random-seeds] [--strict-missing]\n"
           "                     [--aov]  also PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm: first-hit AOVs of the same seeds (rank 0)\n"
+          "                     [--denoise [--denoise-iterations L]]  also PREFIX_denoised.pfm / .png: the frame through the AOV-guided\n"
+          "                              a-trous denoiser (default parameters, L = 0..8 iterations, default 5), on rank 0 after the gather\n"
           "       multi-GPU (one process per GPU, tile split + RCCL gather to rank 0, which writes the image):\n"
           "                     [--spawn N]  start N ranks of this program, rank r on device r, and wait for them\n"
           "                     [--spawn-same-device]  ... every rank on --device (a one-GPU box; needs a transport that accepts it,\n"
@@ -30,7 +32,8 @@ static void usage() {
 int main(int argc, char** argv) {
   std::string scene = "spheres", prefix = "frame", scenes = "scenes/", outdir = ".";
   unsigned spp = 32, width = 1920, height = 1080, seed = 0;
-  int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false;
+  int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false, denoise = false;
+  int denoiseIterations = 5;
   int rank = 0, ranks = 1, spawn = 0, spawnTimeout = 600; bool spawnSame = false; std::string commFile;
   for (int i = 1; i < argc; i++) {
     auto need = [&](const char* n) { if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", n); exit(2); } return argv[++i]; };
@@ -53,6 +56,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--random-seeds")) randomSeeds = true;
     else if (!strcmp(argv[i], "--strict-missing")) strict = true;
     else if (!strcmp(argv[i], "--aov")) aov = true;
+    else if (!strcmp(argv[i], "--denoise")) denoise = true;
+    else if (!strcmp(argv[i], "--denoise-iterations")) denoiseIterations = atoi(need("--denoise-iterations"));
     else { usage(); return 2; }
   }
   if (spawn > 0) {
@@ -103,6 +108,7 @@ int main(int argc, char** argv) {
     app.fixedWidth = width; app.fixedHeight = height; app.nSuperSampling = spp;
     app.baseSeed = seed; app.reproducibleSeeds = !randomSeeds; app.skipMissingMeshes = !strict;
     app.baseSceneFolder = scenes; app.outputDir = outdir;
+    app.denoise = denoise; app.denoiseIterations = denoiseIterations;
     app.setupContext();
     if (scene == "spheres") app.sceneId = MinimalOptiX::SCENE_SPHERES;
     else if (scene == "coffee") app.sceneId = MinimalOptiX::SCENE_COFFEE;

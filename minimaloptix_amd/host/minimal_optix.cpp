@@ -1,5 +1,6 @@
 #include "minimal_optix.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -130,6 +131,7 @@ void MinimalOptiX::renderScene(bool autoSave, std::string fileNamePrefix) {
     }
   }
   if (multi) check(moptix_gather_tiles(context, 0), "gather tiles");      // the frame's one exchange: every rank's tiles to rank 0
+  if (denoise && rank == 0) saveDenoised(fileNamePrefix);      // before the resolve below clears accuBuffer
   updateContent((float)nSuperSampling, true);                   // :555 (ranks > 0: clears their accuBuffer; their canvas is partial)
   if (autoSave) saveCurrentFrame(false, fileNamePrefix);        // :556-558
   uint64_t n = 0;
@@ -167,6 +169,31 @@ void MinimalOptiX::saveAovs(std::string fileNamePrefix) {
     if (!writePFM(base + f.first, f.second->data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + base + f.first);
     if (verbose) fprintf(stderr, "AOV saved to %s\n", (base + f.first).c_str());
   }
+}
+
+void MinimalOptiX::saveDenoised(std::string fileNamePrefix) {
+  check(moptix_aov_clear(context), "AOV clear");
+  check(moptix_render_aovs(context, lastSeeds.data(), (int32_t)lastSeeds.size()), "render AOVs");
+  moptix_denoise_params p;
+  check(moptix_denoise_defaults(&p), "denoise defaults");
+  p.iterations = denoiseIterations;
+  check(moptix_denoise(context, &p, (float)nSuperSampling), "denoise");
+  const size_t px = (size_t)fixedWidth * fixedHeight;
+  std::vector<float> out(3 * px);
+  check(moptix_denoise_read(context, out.data()), "read denoised");
+  std::vector<uint8_t> rgb(3 * px);
+  for (size_t i = 0; i < px; i++) {
+    const size_t row = i / fixedWidth, col = i % fixedWidth;
+    uint8_t* dst = rgb.data() + 3 * ((fixedHeight - 1 - row) * fixedWidth + col);
+    for (int c = 0; c < 3; c++) {
+      const float v = std::min(std::max(out[3 * i + c], 0.0f), 1.0f);
+      dst[c] = (uint8_t)(((uint32_t)(v * 65535.0f + 0.5f)) >> 8);      // as k_resolve_rgb8 (updateContent)
+    }
+  }
+  const std::string base = outputDir + "/" + (fileNamePrefix.empty() ? std::string("frame") : fileNamePrefix) + "_denoised";
+  if (!writePFM(base + ".pfm", out.data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + base + ".pfm");
+  if (!writePNG(base + ".png", rgb.data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + base + ".png");
+  if (verbose) fprintf(stderr, "Denoised image saved to %s.pfm / .png\n", base.c_str());
 }
 
 // MinimalOptiX.cpp:587-592

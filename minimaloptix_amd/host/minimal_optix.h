@@ -87,6 +87,14 @@ public:
   std::vector<int32_t> lastSeeds;     // the launch seeds of the last renderScene()
   void saveAovs(std::string fileNamePrefix);
 
+  // denoiser (new; include/moptix.h): with denoise set, renderScene() calls saveDenoised on rank 0 after the gather, while accuBuffer
+  // still holds the frame (its resolve clears it): the AOVs of the same seeds (whole frame), moptix_denoise with the defaults and
+  // denoiseIterations -> PREFIX_denoised.pfm (rows bottom-up, as accuBuffer) and PREFIX_denoised.png (top row first,
+  // u8(clamp(v, 0, 1) * 255) as updateContent) in outputDir
+  bool denoise = false;
+  int denoiseIterations = 5;
+  void saveDenoised(std::string fileNamePrefix);
+
 private:
   uint launchCounter = 0;
   void check(int rc, const char* what);
