@@ -1,0 +1,163 @@
+// api_context.h -- the context record behind moptix_context and the helpers the api_*.hip files share.  Private to them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/moptix.h"
+#include "lbvh.h"
+#include "megakernel.h"
+
+struct ncclComm;      // RCCL's communicator (api_comm.hip is the only file that sees RCCL's declarations)
+
+namespace pt { namespace api {
+
+template <class T> struct DevBuf {
+  T* p = nullptr; size_t n = 0;
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    if (p) { (void)hipFree(p); p = nullptr; n = 0; }
+    hipError_t e = hipMalloc((void**)&p, sizeof(T) * (count ? count : 1));
+    if (e == hipSuccess) n = count ? count : 1;
+    return e;
+  }
+  hipError_t upload(const std::vector<T>& v, hipStream_t s) {
+    hipError_t e = ensure(v.size());
+    if (e != hipSuccess || v.empty()) return e;
+    return hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+// moptix_set_option / moptix_get_option (api_core.hip kOptions: names, accepted values, what a change invalidates)
+struct Options {
+  int exitThreshold = 16, leafSize = 4, blocksPerCU = 3;
+  int kernelVariant = -1;         // -1 = the library's own choice per launch (api_render.hip plan_launch), else the caller's: 0, 3 or 4
+  int tileMajor = 3;              // all samples of a pixel back to back, pixels with the deepest paths of earlier launches first
+  int starveLanes = 16, sampleBufMB = 16384, leafThreshold = 16, swapLanes = 32;
+  int watchdogMs = 600000;
+  int nodeFormat = 0;             // the node record the packet kernel fetches (pt_types.h): 64, 128, or 0 = whichever costs this scene less (choose_node_format)
+  int fastShading = 0;
+  int builder = 1;
+  int analyticQueue = -1;         // -1 = by primitive count
+  int autoPacket = 1;
+  int commBlocking = 0;           // 1 = plain ncclCommInitRank even where a non-blocking communicator is available
+  int commTimeoutMs = 120000;     // deadline of a collective's completion (comm_wait); the first collective of a communicator also sets its links up
+  int shadowRule = 1;             // 1 = a shadow ray is decided by its nearest any-hit surface (default), 0 = SURVEY A2's order-independent rule
+  int slotsInUse = -1;            // -1 = chosen per launch from its size
+  int drainBelow = 64;            // a workgroup of the packet kernel with this many paths left hands them to the drain kernel (0 = off)
+  int auxDepth = 16;              // variant 4: depth from which a path's shadow rays get slots of their own (0 = off)
+};
+
+}}  // namespace pt::api
+
+struct moptix_context_t {
+  template <class T> using DevBuf = pt::api::DevBuf<T>;
+
+  // ---- device, stream, error, frame (api_core.hip) ----
+  int device = 0;
+  int numCUs = 256;
+  hipStream_t stream = nullptr; bool ownStream = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+  std::string err;
+  bool poisoned = false;             // a dead collective's kernels are still on the stream (comm_teardown): every call fails from here on
+  moptix_params params{}; bool haveParams = false;
+  int rank = 0, nRanks = 1;          // moptix_set_partition
+  pt::api::Options opt;
+
+  // ---- scene (api_core.hip): host staging (copied from the caller, as OptiX copies on setUserData / map+memcpy), its device copy, the tree ----
+  std::vector<pt::DevMaterial> mats;
+  std::vector<pt::DevSphere> spheres; std::vector<int> sphereMat;
+  std::vector<pt::DevQuad> quads;
+  std::vector<pt::DevLight> lights;
+  std::vector<float> facePos, faceNrm; std::vector<int> faceHasNrm, faceMat;
+  std::vector<pt::TriUV> faceUV; bool anyUV = false;
+  struct HostTexture { int width, height; std::vector<float> rgba; };
+  std::vector<HostTexture> textures;
+  bool sceneDirty = true, accelBuilt = false;
+  DevBuf<pt::DevMaterial> dMats; DevBuf<pt::DevSphere> dSpheres; DevBuf<int> dSphereMat; DevBuf<pt::DevQuad> dQuads; DevBuf<pt::DevLight> dLights;
+  DevBuf<float> dFacePos, dFaceNrm; DevBuf<int> dFaceHasNrm, dFaceMat;
+  DevBuf<pt::TriUV> dFaceUV; DevBuf<float> dTexels; DevBuf<pt::DevTexture> dTextures;
+  pt::LbvhResult bvh;
+  double glassFaceShare = 0.0;       // triangles whose material is glass (no next-event estimation at their hits), set by build_accel
+  void release_scene() {
+    dMats.release(); dSpheres.release(); dSphereMat.release(); dQuads.release(); dLights.release();
+    dFacePos.release(); dFaceNrm.release(); dFaceHasNrm.release(); dFaceMat.release();
+    dFaceUV.release(); dTexels.release(); dTextures.release();
+    pt::lbvh_free(&bvh);
+  }
+
+  // ---- accumulation buffer and 8-bit resolve (api_core.hip) ----
+  DevBuf<float> dAccum; float* accumBound = nullptr; size_t accumPixels = 0;
+  DevBuf<uint8_t> dRgb8;
+
+  // ---- beauty launches (api_render.hip) ----
+  int nodeFormatUsed = 128;          // the verdict for this build (get_option "node_format_used")
+  bool formatDecided = false;
+  unsigned long long probeCounts[4] = { 0, 0, 0, 0 };     // node steps, triangle tests of the probe rays under Node128; the same under Node64
+  int lastVariant = -1;              // what the last render ran (get_option "kernel_variant_used")
+  int countedSpanUs = -1, countedTailUs = -1;   // last counted launch: first wave in -> last wave out, and the part of it after the last work item was handed out
+  double kernelMs = 0.0, reduceMs = 0.0; uint64_t nLaunches = 0;
+  bool asyncPending = false;
+  std::vector<int> seedStaging;
+  DevBuf<int> dSeeds; DevBuf<int> dWork; DevBuf<unsigned long long> dCounters; DevBuf<int> dOverflow;
+  DevBuf<uint8_t> dPoolCold; DevBuf<float> dSampleBuf;
+  void release_render() {
+    dSeeds.release(); dWork.release(); dCounters.release(); dOverflow.release(); dPoolCold.release(); dSampleBuf.release();
+    tiles.release();
+  }
+  // which units (pixels or 8x8 tiles) had the deepest paths in earlier launches: they are handed out first (LaunchArgs::tileOrder)
+  struct TileHistory {
+    long long units = -1;            // units the history holds (-1 = none: the next launch starts it afresh)
+    DevBuf<unsigned int> cost, costSorted; DevBuf<int> order, iota; DevBuf<uint8_t> sortTmp;
+    void forget() { units = -1; }
+    void release() { cost.release(); costSorted.release(); order.release(); iota.release(); sortTmp.release(); units = -1; }
+  } tiles;
+
+  // ---- multi-GPU, one process per GPU (api_comm.hip): RCCL communicator of this rank + staging for the tile gather ----
+  struct Comm {
+    ncclComm* handle = nullptr; int rank = 0, ranks = 1;
+    bool nonBlocking = false;        // the communicator was made with config.blocking = 0 (calls may return ncclInProgress: comm_settle)
+    DevBuf<float> tileSend, tileRecv;
+  } comm;                            // released by pt::api::comm_release
+
+  // ---- first-hit AOVs (api_aov.hip): allocated at the first AOV call; a bound member (moptix_aov_bind) replaces the own buffer ----
+  struct Aov {
+    DevBuf<float> albedo, normal, depth, hits; DevBuf<int> primId, matId;
+    moptix_aov_buffers bound{};
+    size_t pixels = 0;               // frame size the AOV buffers hold (0 = to be (re)allocated and cleared at the next AOV call)
+    uint64_t samples = 0;            // seeds added since the clear
+    DevBuf<int> seeds, work, overflow;
+    void frame_resized() { pixels = 0; samples = 0; }      // the AOVs are reallocated and cleared at the next AOV call
+    void release() {
+      albedo.release(); normal.release(); depth.release(); hits.release(); primId.release(); matId.release();
+      seeds.release(); work.release(); overflow.release();
+    }
+  } aov;
+
+  // ---- denoiser (api_denoise.hip): scratch and output allocated at the first call, freed by a frame-size change; a bound output
+  // (moptix_denoise_bind) replaces the own one ----
+  struct Denoise {
+    DevBuf<pt::v4> colA, colB, guide, side; DevBuf<float> out;
+    float* bound = nullptr;
+    size_t pixels = 0;               // frame size of the last denoise call (0: none since the last frame-size change)
+    void release() { colA.release(); colB.release(); guide.release(); side.release(); out.release(); pixels = 0; }
+  } dn;
+};
+
+namespace pt { namespace api {
+
+// the error text goes to the context, or (no context: moptix_create, moptix_comm_unique_id) to the library's own
+int fail(moptix_context c, int code, const std::string& msg);
+int hipFail(moptix_context c, hipError_t e, const char* what);
+#define HIPCHK(c, x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pt::api::hipFail((c), e_, (what)); } while (0)
+
+int check_ready(moptix_context c);                   // params set, tree built, stream alive
+float* accum_ptr(moptix_context c);
+int ensure_accum(moptix_context c);
+void fill_view(moptix_context c, SceneView& v);
+moptix_aov_buffers aov_ptrs(moptix_context c);       // api_aov.hip: bound or own, member by member
+void comm_release(moptix_context c);                 // api_comm.hip: destroys the communicator, frees the staging
+
+}}  // namespace pt::api

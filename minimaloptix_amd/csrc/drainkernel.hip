@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
         const v4 thrIn = slot_load(&cs->thr), radIn = slot_load(&cs->rad);
         const v4 na = slot_load(&cs->spare[0]), nb = slot_load(&cs->spare[1]);
         const int fl = f2i(nb.w);
-        if (CNT) atomicAdd(a.counters + 813, 1ull);
+        if (CNT) atomicAdd(a.counters + kCntDrainTaken, 1ull);
         const int nSh = (fl >> kPendShift) & 3;
         v4 wh = mk4(0.f, 0.f, 0.f, 0.f), wb = mk4(1.f, 1.f, 1.f, 1.f);
         if (fl & kHitValid) wh = slot_load(&cs->hit);
@@ -205,11 +205,11 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
       on_result_packet<CNT, FAST, PacketSink>(sc, ps, pk, res, att, ct, sink);
       if (ps.mode == M_NEW_SAMPLE) {
         if (CNT) {      // finish-time histogram of the counting build, on the packet kernel's clock (its first wave's start)
-          const unsigned long long b = min(255ull, (__builtin_amdgcn_s_memrealtime() - a.counters[36]) / 100000ull);
-          atomicAdd(a.counters + 40 + b, 1ull); atomicMax(a.counters + 296 + b, (unsigned long long)ps.depth); atomicAdd(a.counters + 552 + b, (unsigned long long)ps.depth);
+          const unsigned long long b = min((unsigned long long)(kCntTailBuckets - 1), (__builtin_amdgcn_s_memrealtime() - a.counters[kCntFirstWaveIn]) / 100000ull);
+          atomicAdd(a.counters + kCntTailCount + b, 1ull); atomicMax(a.counters + kCntTailMaxDepth + b, (unsigned long long)ps.depth); atomicAdd(a.counters + kCntTailDepthSum + b, (unsigned long long)ps.depth);
         }
         store_sample(a, ps.item, ps.accum);
-        if (CNT) atomicAdd(a.counters + 814, 1ull);
+        if (CNT) atomicAdd(a.counters + kCntDrainFinished, 1ull);
         if (a.tileCost != nullptr && ps.depth >= kDeepPath) atomicMax(a.tileCost + ((ps.item % a.nItems) >> a.unitShift), (unsigned int)ps.depth);
         ps.mode = M_DONE;
       }
@@ -388,17 +388,17 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[9] = { wave_sum32(ct.samples), wave_sum32(ct.primaryRays), wave_sum32(ct.bounceRays), wave_sum32(ct.shadowRays),
+    const uint32_t v[kCntPerLane] = { wave_sum32(ct.samples), wave_sum32(ct.primaryRays), wave_sum32(ct.bounceRays), wave_sum32(ct.shadowRays),
                             wave_sum32(ct.nodeFetches), wave_sum32(ct.triTests), wave_sum32(ct.closestHits), wave_sum32(ct.lightLoads),
                             wave_sum32(ct.analyticTests) };
     for (int i = 0; i < kCensusRegions; i++) {
       const uint32_t cl = wave_sum32(ct.censusLanes[i]), cw = wave_sum32(ct.censusWaves[i]);
-      if (lane == 0 && cw != 0u) { atomicAdd(&c[816 + i], (unsigned long long)cl); atomicAdd(&c[816 + kCensusRegions + i], (unsigned long long)cw); }
+      if (lane == 0 && cw != 0u) { atomicAdd(&c[kCntCensusLanes + i], (unsigned long long)cl); atomicAdd(&c[kCntCensusWaves + i], (unsigned long long)cw); }
     }
     if (lane == 0) {
-      for (int i = 0; i < 9; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
-      atomicAdd(&c[9], (unsigned long long)rounds); atomicAdd(&c[10], (unsigned long long)roundLanes);
-      atomicMax(&c[38], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
+      for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
+      atomicAdd(&c[kCntTraversalSteps], (unsigned long long)rounds); atomicAdd(&c[kCntActiveLaneSteps], (unsigned long long)roundLanes);
+      atomicMax(&c[kCntLastWaveOut], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
     }
   }
 }

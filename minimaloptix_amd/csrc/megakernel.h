@@ -1,6 +1,7 @@
 // megakernel.h -- launch interface of megakernel.hip
 #pragma once
 #include <hip/hip_runtime.h>
+#include "pt_counters.h"
 #include "pt_types.h"
 
 namespace pt {
@@ -17,7 +18,7 @@ struct LaunchArgs {
   int exitThreshold;                // leave the traversal loop below this many active lanes
   int leafThreshold;                // run the leaf pass once this many lanes are parked at a leaf
   int* stackOverflow;               // per-thread spill area for trees deeper than the LDS stack (or null)
-  unsigned long long* counters;     // 16 x u64 (counting build only)
+  unsigned long long* counters;     // kCntTotal x u64, laid out by pt_counters.h (counting build only)
   // variants 3 and 4 (queuekernel.hip, packetkernel.hip)
   void* poolCold;                   // path-slot records in HBM
   int starveLanes;                  // run a partial batch once this many lanes of the wave have nothing to traverse
@@ -107,6 +108,19 @@ int packetkernel_slots();             // path slots per workgroup (variant 4)
 size_t packetkernel_cold_bytes(int nBlocks);
 size_t packetkernel_overflow_ints(int nBlocks, int ovfDepth);
 hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading);
+// What the launch plan (api_render.hip) asks of a trace kernel that keeps its paths in slots: the stack entries a slot has in LDS, the bytes of
+// slot records and the ints of stack overflow that nBlocks workgroups need, and the launch itself.  (launch_megakernel has no slots and sizes
+// its overflow area per thread: it stays a special case there.)
+struct TraceKernel {
+  const char* launchWhat;
+  int (*lds_stack_entries)();
+  size_t (*cold_bytes)(int nBlocks);
+  size_t (*overflow_ints)(int nBlocks, int ovfDepth);
+  hipError_t (*launch)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading);
+};
+inline constexpr TraceKernel kQueueKernel = { "launch queue megakernel", queuekernel_lds_stack_entries, queuekernel_cold_bytes, queuekernel_overflow_ints, launch_queuekernel };
+inline constexpr TraceKernel kLeanQueueKernel = { "launch queue megakernel (lean)", queuekernel_lds_stack_entries_lean, queuekernel_cold_bytes_lean, queuekernel_overflow_ints_lean, launch_queuekernel_lean };
+inline constexpr TraceKernel kPacketKernel = { "launch packet megakernel", packetkernel_lds_stack_entries, packetkernel_cold_bytes, packetkernel_overflow_ints, launch_packetkernel };
 // drainkernel.hip: finishes the paths the packet kernel's workgroups handed over (LaunchArgs::drainList); same stream, right after it
 hipError_t launch_drainkernel(hipStream_t stream, const LaunchArgs& a, int nCUs, bool counted, bool fastShading);
 size_t drain_list_ints(int nBlocks, int drainBelow);      // ints behind LaunchArgs::workCounter + kDrainList

@@ -145,13 +145,13 @@ __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs 
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[9] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
+    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
                             wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
                             wave_sum(ct.analyticTests) };
     if (lane == 0) {
-      for (int i = 0; i < 9; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
-      atomicAdd(&c[9], (unsigned long long)waveSteps);
-      atomicAdd(&c[10], (unsigned long long)activeLaneSteps);
+      for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
+      atomicAdd(&c[kCntTraversalSteps], (unsigned long long)waveSteps);
+      atomicAdd(&c[kCntActiveLaneSteps], (unsigned long long)activeLaneSteps);
     }
   }
 }

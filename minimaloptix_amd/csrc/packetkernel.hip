@@ -31,7 +31,7 @@
 //   * this file is compiled twice (Makefile): as it stands for the 64-byte-node instantiations, with LLVM's max-ilp scheduling, and through
 //     packetkernel_n128.hip (PT_PK_N128) for the 128-byte-node ones with the default strategy -- each is a few per cent slower under the other's.
 //
-// Limits (moptix_api.hip falls back to variant 3 otherwise): at most kPacketShadows lights, no Disney material on an
+// Limits (api_render.hip plan_launch falls back to variant 3 otherwise): at most kPacketShadows lights, no Disney material on an
 // analytic primitive (shadow rays then need the brute-force lists at every ray start).
 #include <hip/hip_runtime.h>
 
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(
   // Paths in flight = slots in use; by Little's law a ray spends (slots in use) / (rays per second) in the scheduler,
   // about 70 us with all 512 slots of every pool, so a path that bounces to the depth cap (about 1000 dependent rays)
   // takes 70-90 ms however short the launch is.  A short launch (one rank's share of a multi-GPU frame) therefore
-  // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, moptix_api.hip).
+  // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, api_render.hip plan_launch).
   const bool auxOn = SHARED && a.auxDepth > 0 && sc.rootRef >= 0;
   const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? (SHARED ? a.slotsInUse : max(64, a.slotsInUse / kWaves)) : NS;
   {
@@ -558,11 +558,11 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(
     for (;;) {
       if (have && ps.mode == M_NEW_SAMPLE) {
         if (CNT) {      // finish-time histogram (1 ms buckets): how many samples end when, and how deep they were
-          const unsigned long long b = min(255ull, (__builtin_amdgcn_s_memrealtime() - rtStart) / 100000ull);
-          atomicAdd(a.counters + 40 + b, 1ull); atomicMax(a.counters + 296 + b, (unsigned long long)ps.depth); atomicAdd(a.counters + 552 + b, (unsigned long long)ps.depth);
+          const unsigned long long b = min((unsigned long long)(kCntTailBuckets - 1), (__builtin_amdgcn_s_memrealtime() - rtStart) / 100000ull);
+          atomicAdd(a.counters + kCntTailCount + b, 1ull); atomicMax(a.counters + kCntTailMaxDepth + b, (unsigned long long)ps.depth); atomicAdd(a.counters + kCntTailDepthSum + b, (unsigned long long)ps.depth);
         }
         store_sample(a, ps.item, ps.accum);
-        if (CNT) atomicAdd(a.counters + 815, 1ull);
+        if (CNT) atomicAdd(a.counters + kCntPacketFinished, 1ull);
         if (a.tileCost != nullptr && ps.depth >= kDeepPath) atomicMax(a.tileCost + ((ps.item % a.nItems) >> a.unitShift), (unsigned int)ps.depth);
         ps.mode = M_NEW_PIXEL;
       }
@@ -582,7 +582,7 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(
         } else {  // M_NEW_PIXEL: next (pixel, sample) work item
           int k = atomicAdd(a.workCounter, 1);
           k = (k >= a.nWork) ? -1 : handout_to_item(a, k);
-          if (CNT && k < 0) atomicMin(a.counters + 37, (unsigned long long)__builtin_amdgcn_s_memrealtime());   // first time the items ran out
+          if (CNT && k < 0) atomicMin(a.counters + kCntItemsRanOut, (unsigned long long)__builtin_amdgcn_s_memrealtime());   // first time the items ran out
           int s;
           if (k < 0) { ps.mode = M_DONE; }
           else if (item_to_pixel(a, k, s, ps.pixel)) { ps.item = k; begin_sample<CNT>(sc, ps, a.seeds[s], ct); packet_primary(pk); }
@@ -857,39 +857,39 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(
         int* dl = a.workCounter + kDrainList;
         const int idx = atomicAdd(dl + (deep ? kDrainDeepN : kDrainOtherN), 1);
         dl[deep ? kDrainEntries + idx : kDrainEntries + dl[kDrainCap] - 1 - idx] = gpool * NS + slot;
-        if (CNT) atomicAdd(a.counters + 812, 1ull);
+        if (CNT) atomicAdd(a.counters + kCntHandedOver, 1ull);
       }
     }
   }
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[9] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
+    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
                             wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
                             wave_sum(ct.analyticTests) };
     const uint32_t rw[4] = { wave_sum(rows[0]), wave_sum(rows[1]), wave_sum(rows[2]), wave_sum(rows[3]) };
     for (int i = 0; i < kCensusRegions; i++) {
       const uint32_t cl = wave_sum(ct.censusLanes[i]), cw = wave_sum(ct.censusWaves[i]);
-      if (lane == 0 && cw != 0u) { atomicAdd(&c[816 + i], (unsigned long long)cl); atomicAdd(&c[816 + kCensusRegions + i], (unsigned long long)cw); }
+      if (lane == 0 && cw != 0u) { atomicAdd(&c[kCntCensusLanes + i], (unsigned long long)cl); atomicAdd(&c[kCntCensusWaves + i], (unsigned long long)cw); }
     }
     if (lane == 0) {
-      for (int i = 0; i < 9; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
-      atomicAdd(&c[9], (unsigned long long)nodeSteps + leafPasses);
-      atomicAdd(&c[10], (unsigned long long)nodeLanes + leafLanes);
-      atomicAdd(&c[11], (unsigned long long)batches);
-      atomicAdd(&c[12], (unsigned long long)batchLanes);
-      atomicAdd(&c[14], (unsigned long long)idleSpins);
-      atomicAdd(&c[16], tBatch); atomicAdd(&c[17], tSwap); atomicAdd(&c[18], tNode); atomicAdd(&c[19], tLeaf);
-      atomicAdd(&c[21], __builtin_amdgcn_s_memtime() - tStart);
-      atomicAdd(&c[22], (unsigned long long)leafPasses); atomicAdd(&c[23], (unsigned long long)leafLanes);
-      atomicMax(&c[38], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
-      atomicMin(&c[36], rtStart);
-      atomicAdd(&c[24], tLocal); atomicAdd(&c[25], tLock); atomicAdd(&c[26], tTxn); atomicAdd(&c[27], tIdle);
-      atomicAdd(&c[39], nodeRuns); atomicAdd(&c[15], ringBacklog); atomicAdd(&c[13], leafBacklog);
-      atomicAdd(&c[33], nIterResult); atomicAdd(&c[34], nIterLights); atomicAdd(&c[35], nIterGen);
-      atomicAdd(&c[808], (unsigned long long)rw[0]); atomicAdd(&c[809], (unsigned long long)rw[1]);
-      atomicAdd(&c[810], (unsigned long long)rw[2]); atomicAdd(&c[811], (unsigned long long)rw[3]);
-      atomicAdd(&c[28], tBLoad); atomicAdd(&c[29], tBRun); atomicAdd(&c[30], tBStore); atomicAdd(&c[31], nTxn); atomicAdd(&c[32], nIter);
+      for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
+      atomicAdd(&c[kCntTraversalSteps], (unsigned long long)nodeSteps + leafPasses);
+      atomicAdd(&c[kCntActiveLaneSteps], (unsigned long long)nodeLanes + leafLanes);
+      atomicAdd(&c[kCntShadeBatches], (unsigned long long)batches);
+      atomicAdd(&c[kCntShadeBatchLanes], (unsigned long long)batchLanes);
+      atomicAdd(&c[kCntIdleSpins], (unsigned long long)idleSpins);
+      atomicAdd(&c[kCntTBatch], tBatch); atomicAdd(&c[kCntTSwap], tSwap); atomicAdd(&c[kCntTNode], tNode); atomicAdd(&c[kCntTLeaf], tLeaf);
+      atomicAdd(&c[kCntTWave], __builtin_amdgcn_s_memtime() - tStart);
+      atomicAdd(&c[kCntLeafPasses], (unsigned long long)leafPasses); atomicAdd(&c[kCntLeafLanes], (unsigned long long)leafLanes);
+      atomicMax(&c[kCntLastWaveOut], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
+      atomicMin(&c[kCntFirstWaveIn], rtStart);
+      atomicAdd(&c[kCntTLocal], tLocal); atomicAdd(&c[kCntTLock], tLock); atomicAdd(&c[kCntTTxn], tTxn); atomicAdd(&c[kCntTIdle], tIdle);
+      atomicAdd(&c[kCntNodeRuns], nodeRuns); atomicAdd(&c[kCntRingBacklog], ringBacklog); atomicAdd(&c[kCntLeafBacklog], leafBacklog);
+      atomicAdd(&c[kCntIterResult], nIterResult); atomicAdd(&c[kCntIterLights], nIterLights); atomicAdd(&c[kCntIterNewItem], nIterGen);
+      atomicAdd(&c[kCntSlotRows], (unsigned long long)rw[0]); atomicAdd(&c[kCntSlotRows + 1], (unsigned long long)rw[1]);
+      atomicAdd(&c[kCntSlotRows + 2], (unsigned long long)rw[2]); atomicAdd(&c[kCntSlotRows + 3], (unsigned long long)rw[3]);
+      atomicAdd(&c[kCntTBatchLoad], tBLoad); atomicAdd(&c[kCntTBatchRun], tBRun); atomicAdd(&c[kCntTBatchStore], tBStore); atomicAdd(&c[kCntTransactions], nTxn); atomicAdd(&c[kCntIterations], nIter);
     }
   }
 }
@@ -926,7 +926,7 @@ hipError_t PT_PK_LAUNCH(hipStream_t stream, const LaunchArgs& a, int nBlocks, bo
 #ifndef PT_PK_N128
 hipError_t launch_packetkernel_n128(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading);
 hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading) {
-  // moptix_api.hip fill_view: the option node_format decides whether the scene view carries the 64-byte nodes
+  // api_core.hip fill_view: the option node_format decides whether the scene view carries the 64-byte nodes
   return a.scene.nodes64 != nullptr ? launch_packetkernel_n64(stream, a, nBlocks, counted, fastShading) : launch_packetkernel_n128(stream, a, nBlocks, counted, fastShading);
 }
 #endif

@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
   // Paths in flight = slots in use; by Little's law a ray spends (slots in use) / (rays per second) in the scheduler,
   // about 70 us with all 512 slots of every pool, so a path that bounces to the depth cap (about 1000 dependent rays)
   // takes 70-90 ms however short the launch is.  A short launch (one rank's share of a multi-GPU frame) therefore
-  // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, moptix_api.hip).
+  // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, api_render.hip plan_launch).
   const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? (SHARED ? a.slotsInUse : max(64, a.slotsInUse / kWaves)) : NS;
   {
     const int first = SHARED ? threadIdx.x : lane, step = SHARED ? kBlockThreads : 64;
@@ -409,8 +409,8 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
     for (;;) {
       if (have && ps.mode == M_NEW_SAMPLE) {
         if (CNT) {      // finish-time histogram (1 ms buckets): how many samples end when, and how deep they were
-          const unsigned long long b = min(255ull, (__builtin_amdgcn_s_memrealtime() - rtStart) / 100000ull);
-          atomicAdd(a.counters + 40 + b, 1ull); atomicMax(a.counters + 296 + b, (unsigned long long)ps.depth); atomicAdd(a.counters + 552 + b, (unsigned long long)ps.depth);
+          const unsigned long long b = min((unsigned long long)(kCntTailBuckets - 1), (__builtin_amdgcn_s_memrealtime() - rtStart) / 100000ull);
+          atomicAdd(a.counters + kCntTailCount + b, 1ull); atomicMax(a.counters + kCntTailMaxDepth + b, (unsigned long long)ps.depth); atomicAdd(a.counters + kCntTailDepthSum + b, (unsigned long long)ps.depth);
         }
         store_sample(a, ps.item, ps.accum);
         if (a.tileCost != nullptr && ps.depth >= kDeepPath) atomicMax(a.tileCost + ((ps.item % a.nItems) >> a.unitShift), (unsigned int)ps.depth);
@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
         } else {  // M_NEW_PIXEL: next (pixel, sample) work item
           int k = atomicAdd(a.workCounter, 1);
           k = (k >= a.nWork) ? -1 : handout_to_item(a, k);
-          if (CNT && k < 0) atomicMin(a.counters + 37, (unsigned long long)__builtin_amdgcn_s_memrealtime());   // first time the items ran out
+          if (CNT && k < 0) atomicMin(a.counters + kCntItemsRanOut, (unsigned long long)__builtin_amdgcn_s_memrealtime());   // first time the items ran out
           int s;
           if (k < 0) { ps.mode = M_DONE; }
           else if (item_to_pixel(a, k, s, ps.pixel)) { ps.item = k; begin_sample<CNT>(sc, ps, a.seeds[s], ct); }
@@ -621,25 +621,25 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[9] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
+    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
                             wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
                             wave_sum(ct.analyticTests) };
     if (lane == 0) {
-      for (int i = 0; i < 9; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
-      atomicAdd(&c[9], (unsigned long long)nodeSteps + leafPasses);
-      atomicAdd(&c[10], (unsigned long long)nodeLanes + leafLanes);
-      atomicAdd(&c[11], (unsigned long long)batches);
-      atomicAdd(&c[12], (unsigned long long)batchLanes);
-      atomicAdd(&c[14], (unsigned long long)idleSpins);
-      atomicAdd(&c[16], tBatch); atomicAdd(&c[17], tSwap); atomicAdd(&c[18], tNode); atomicAdd(&c[19], tLeaf);
-      atomicAdd(&c[21], __builtin_amdgcn_s_memtime() - tStart);
-      atomicAdd(&c[22], (unsigned long long)leafPasses); atomicAdd(&c[23], (unsigned long long)leafLanes);
-      atomicMax(&c[38], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
-      atomicMin(&c[36], rtStart);
-      atomicAdd(&c[24], tLocal); atomicAdd(&c[25], tLock); atomicAdd(&c[26], tTxn); atomicAdd(&c[27], tIdle);
-      atomicAdd(&c[39], nodeRuns); atomicAdd(&c[15], ringBacklog); atomicAdd(&c[13], leafBacklog);
-      atomicAdd(&c[33], nIterResult); atomicAdd(&c[34], nIterLights); atomicAdd(&c[35], nIterGen);
-      atomicAdd(&c[28], tBLoad); atomicAdd(&c[29], tBRun); atomicAdd(&c[30], tBStore); atomicAdd(&c[31], nTxn); atomicAdd(&c[32], nIter);
+      for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
+      atomicAdd(&c[kCntTraversalSteps], (unsigned long long)nodeSteps + leafPasses);
+      atomicAdd(&c[kCntActiveLaneSteps], (unsigned long long)nodeLanes + leafLanes);
+      atomicAdd(&c[kCntShadeBatches], (unsigned long long)batches);
+      atomicAdd(&c[kCntShadeBatchLanes], (unsigned long long)batchLanes);
+      atomicAdd(&c[kCntIdleSpins], (unsigned long long)idleSpins);
+      atomicAdd(&c[kCntTBatch], tBatch); atomicAdd(&c[kCntTSwap], tSwap); atomicAdd(&c[kCntTNode], tNode); atomicAdd(&c[kCntTLeaf], tLeaf);
+      atomicAdd(&c[kCntTWave], __builtin_amdgcn_s_memtime() - tStart);
+      atomicAdd(&c[kCntLeafPasses], (unsigned long long)leafPasses); atomicAdd(&c[kCntLeafLanes], (unsigned long long)leafLanes);
+      atomicMax(&c[kCntLastWaveOut], (unsigned long long)__builtin_amdgcn_s_memrealtime());   // last wave out
+      atomicMin(&c[kCntFirstWaveIn], rtStart);
+      atomicAdd(&c[kCntTLocal], tLocal); atomicAdd(&c[kCntTLock], tLock); atomicAdd(&c[kCntTTxn], tTxn); atomicAdd(&c[kCntTIdle], tIdle);
+      atomicAdd(&c[kCntNodeRuns], nodeRuns); atomicAdd(&c[kCntRingBacklog], ringBacklog); atomicAdd(&c[kCntLeafBacklog], leafBacklog);
+      atomicAdd(&c[kCntIterResult], nIterResult); atomicAdd(&c[kCntIterLights], nIterLights); atomicAdd(&c[kCntIterNewItem], nIterGen);
+      atomicAdd(&c[kCntTBatchLoad], tBLoad); atomicAdd(&c[kCntTBatchRun], tBRun); atomicAdd(&c[kCntTBatchStore], tBStore); atomicAdd(&c[kCntTransactions], nTxn); atomicAdd(&c[kCntIterations], nIter);
     }
   }
 }

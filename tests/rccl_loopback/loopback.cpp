@@ -1,5 +1,5 @@
 // rccl_loopback -- TEST INFRASTRUCTURE, not part of the product: the RCCL entry points libmoptix.so binds (nine + the two optional ones)
-// (csrc/moptix_api.hip RcclApi), implemented over POSIX shared memory + hipMemcpy, so that the N > 1 branches of
+// (csrc/api_comm.hip RcclApi), implemented over POSIX shared memory + hipMemcpy, so that the N > 1 branches of
 // moptix_gather_tiles / moptix_reduce_frame (pack -> send; grouped receives -> unpack; reduce) run as N processes on a ONE-GPU box.
 // RCCL itself refuses a communicator whose ranks share a device ("Duplicate GPU detected", init.cc), and no multi-GPU box has been
 // available to this project; what this exercises is everything on OUR side of the ncclXxx calls, not RCCL or xGMI.

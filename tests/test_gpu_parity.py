@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 RMSE_TOL = 1e-3        # BASELINE.json north_star
 RMSE_TIGHT = 2e-6      # what the arithmetic contract actually delivers (float association only)
-DRAIN_DEFAULT = 64     # option drain_below as moptix_create leaves it (csrc/moptix_api.hip optDrainBelow)
+DRAIN_DEFAULT = 64     # option drain_below as moptix_create leaves it (csrc/api_context.h Options::drainBelow)
 
 CASES = [
     ("spheres", dict(farg=0.5), (160, 90), 4),

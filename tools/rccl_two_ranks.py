@@ -40,7 +40,7 @@ def rank_main(rank, n, same, idfile, outdir):
     ctx.comm_init(uid, rank, n)
     if os.environ.get("RCCL_TWO_RANKS_DEAD_PEER"):
         # a peer that joins the communicator and then never calls the collective: rank 0's gather must come back with
-        # MOPTIX_ERR_COMM after "comm_timeout_ms" (csrc/moptix_api.hip comm_wait), not block for good
+        # MOPTIX_ERR_COMM after "comm_timeout_ms" (csrc/api_comm.hip comm_wait), not block for good
         if rank != 0:
             time.sleep(4.0)
             return

@@ -30,5 +30,5 @@ for tag, defs in (("pa", []), ("pb", ["-DPT_WAVES_PER_SIMD=4", "-DPT_KP=88"])):
     obj = os.path.join(REPO, "build_probe", "pk_%s.o" % tag)
     subprocess.check_call(base + defs + ["-c", probe, "-o", obj])
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(REPO, "minimaloptix_amd", "lib", "libmoptix_%s.so" % tag)] +
-                          [os.path.join(REPO, "build", o) for o in ("moptix_api.o", "megakernel.o", "queuekernel.o", "lbvh.o")] + [obj, "-ldl", "-Wl,-rpath,/opt/rocm/lib"])
+                          [os.path.join(REPO, "build", o) for o in ("api_core.o", "api_render.o", "api_aov.o", "api_denoise.o", "api_comm.o", "megakernel.o", "queuekernel.o", "lbvh.o")] + [obj, "-ldl", "-Wl,-rpath,/opt/rocm/lib"])
     print("built libmoptix_%s.so" % tag)
