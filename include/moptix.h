@@ -331,7 +331,7 @@ int moptix_aov_bind(moptix_context ctx, const moptix_aov_buffers* dstDevice);
 
 /* ---- denoiser (new): edge-aware a-trous filter guided by the first-hit AOVs -------------------------------------------------
  * The edge-avoiding a-trous wavelet transform (Dammertz et al. 2010) with SVGF's luminance-variance edge stop (Schied et al. 2017),
- * spatial part only.  Inputs per pixel p (row 0 = bottom, the accumulation buffer's layout), S = moptix_aov_samples:
+ * spatial part (the temporal part is moptix_denoise_temporal below).  Inputs per pixel p (row 0 = bottom, the accumulation buffer's layout), S = moptix_aov_samples:
  *   C_p = accum_p / nAccumulation      the beauty mean (nAccumulation as in moptix_resolve_rgb8)
  *   A_p = albedo_p / S,  N_p = normalize(normal_p / S) (0 where that is 0),  Z_p = depth_p / hits_p
  * p is a geometry pixel iff hits_p > 0.  A background pixel (hits 0) outputs C_p bit for bit and is never a tap.
@@ -377,6 +377,71 @@ int moptix_denoise_defaults(moptix_denoise_params* out);
 int moptix_denoise(moptix_context ctx, const moptix_denoise_params* p, float nAccumulation);
 int moptix_denoise_read(moptix_context ctx, float* dstHost);
 int moptix_denoise_bind(moptix_context ctx, float* dstDevice);
+
+/* ---- denoiser: temporal accumulation with reprojection (new) ------------------------------------------------------------------
+ * moptix_denoise_temporal does what moptix_denoise does with SVGF's temporal stage in front of the a-trous iterations and a history
+ * kept in the context between calls.  Per call (frame k), with C, A, N, Z, hits decoded as above (demodulation as there; iterations =
+ * 0 runs without demodulation, as moptix_denoise) and primId, matId from the AOV buffers; W, H the frame size:
+ * 1 World point.  Geometry pixel p = (x, y): u = (x + 0.5) / W, v = (y + 0.5) / H,
+ *     t = ((scrLowerLeftCorner + u * horizontal) + v * vertical) - origin per component, d = normalize(t), P = fma(Z_p, d, origin):
+ *     the pinhole ray through the pixel centre (with lensRadius > 0 an approximation that the validity tests below absorb).
+ * 2 Object motion.  primId_p < nSpheres (ids are spheres, quads, triangles in upload order): P' = P - (center_now - center_prev) of
+ *     that sphere per component, else P' = P.  "prev" centres and camera are those the context held (its host copy of the spheres, the
+ *     camera of moptix_set_params) at the end of the previous moptix_denoise_temporal call; moptix_update_spheres is not hooked.
+ * 3 Projection into the previous camera (o', LL', H', V').  a = LL' - o', b = H', c = V', r = P' - o'; Cramer's rule on
+ *     r = s a + (s u') b + (s v') c with the triple products written as dots with cross(b, c), cross(c, a), cross(a, b) (AC1, AC2):
+ *     det = dot(a, cross(b, c)), sn = dot(r, cross(b, c)), s = sn / det; det == 0 or not s > 0 -> no history;
+ *     u' = dot(r, cross(c, a)) / sn, v' = dot(r, cross(a, b)) / sn; previous continuous pixel (fx, fy) = (u' W - 0.5, v' H - 0.5),
+ *     expected previous depth Z' = length(r).  Where the previous camera is this one bit for bit (origin, horizontal, vertical,
+ *     scrLowerLeftCorner) and the pixel's object motion is (0, 0, 0), (fx, fy) = (x, y) and Z' = Z_p exactly: a static pixel maps onto
+ *     itself.  No history unless -1 < fx < W and -1 < fy < H.  Motion vector of the pixel: (x - fx, y - fy); (0, 0) without history.
+ * 4 Taps and validity.  x0 = floor(fx), tx = fx - x0 (y alike); taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), in this
+ *     order, with weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.  A tap q counts iff its weight is > 0, it is inside the
+ *     frame, was a geometry pixel in the previous frame, matId_prev(q) == matId_p, N_p . N_prev(q) >= normalThreshold and
+ *     |Z_prev(q) - Z'| <= depthTolerance * Z'.  Sums over the counted taps with plain adds: sw = sum w, sum w I_q per channel,
+ *     sum w m1_q, sum w m2_q; each is divided by sw once (renormalisation).  No counted tap, or sw < 1e-2 -> disocclusion.
+ * 5 Accumulate.  h = min(min over counted taps of h_q + 1, maxHistory); h = 1 on disocclusion and on a background pixel.
+ *     alpha_h = max(1 / h, alpha) (1 / h one binary32 division); I_acc = I_prev + alpha_h * (I - I_prev) per channel; the luminance
+ *     moments m1, m2 of l = l(I), l * l likewise with max(1 / h, alphaMoments).  Disocclusion: I_acc = I, m1 = l, m2 = l * l.  The history
+ *     is this PRE-FILTER accumulation.
+ * 6 Variance.  h >= varianceFrames: v = max(0, m2 - m1 * m1); otherwise the prepass's 3x3 spatial estimate, taken on I_acc.  The depth
+ *     gradient g is the prepass's.
+ * 7 Filter and output.  The L iterations and the final pass of moptix_denoise on {I_acc, v}, into the denoiser's output:
+ *     moptix_denoise_read / moptix_denoise_bind serve both entries.  iterations = 0 outputs I_acc.  Background pixels output C bit for
+ *     bit, keep h = 1 and never serve as taps.
+ * 8 History life.  Stored after each call: {I_acc, h}, {m1, m2}, the frame's {N, Z} and matId, the camera, the sphere centres.  Dropped
+ *     -- the next call behaves as a first frame, every pixel h = 1 -- by moptix_temporal_reset, a change of frame size, a different
+ *     sphere count, moptix_clear_scene, and a change of the demodulation in effect (demodulate, or iterations going to or from 0 with
+ *     demodulate = 1).  The first call after a drop gives, for varianceFrames > 1, the bits of moptix_denoise with the same parameters.
+ * Arithmetic as the denoiser's (csrc/pt_temporal.h states every operation in order).  Ranges: alpha, alphaMoments in [0, 1] (0.2, 0.2),
+ * depthTolerance >= 0 (0.2), normalThreshold in [-1, 1] (0.5), finite; maxHistory 1..65536 (32), varianceFrames 1..65536 (4).  Bad
+ * values -> MOPTIX_ERR_INVALID; state errors and the other argument checks as moptix_denoise.
+ *   moptix_temporal_defaults  the defaults above; pure host
+ *   moptix_denoise_temporal   blocking, on the context's stream.  Like moptix_denoise it reads the accumulation buffer and the AOVs
+ *                             (primId and matId too) wherever they are bound and changes nothing else in the context.  The history
+ *                             (two sets of three float4 per pixel) is allocated at the first call, freed by a frame-size change and
+ *                             by moptix_destroy.
+ *   moptix_temporal_reset     drops the history
+ *   moptix_temporal_info      frames = calls since the last drop; of the last call: geometry pixels, geometry pixels that found
+ *                             history, geometry pixels that did not (disoccluded; all of them in a first frame), and the mean h over
+ *                             the geometry pixels (integer sums reduced on the device)
+ *   moptix_temporal_read      of the last call: motion vectors (W*H*2 floats, x then y) and history lengths h (W*H floats), in the
+ *                             accumulation buffer's pixel order; NULL members are skipped (MOPTIX_ERR_STATE when there was no call
+ *                             since the last frame-size change) */
+typedef struct moptix_temporal_params {
+  float alpha, alphaMoments, depthTolerance, normalThreshold;
+  int32_t maxHistory, varianceFrames;
+} moptix_temporal_params;
+typedef struct moptix_temporal_stats {
+  uint64_t frames, geometryPixels, historyPixels, disoccludedPixels;
+  float meanHistory;
+} moptix_temporal_stats;
+typedef struct moptix_temporal_buffers { float *motion, *history; } moptix_temporal_buffers;
+int moptix_temporal_defaults(moptix_temporal_params* out);
+int moptix_denoise_temporal(moptix_context ctx, const moptix_denoise_params* p, const moptix_temporal_params* t, float nAccumulation);
+int moptix_temporal_reset(moptix_context ctx);
+int moptix_temporal_info(moptix_context ctx, moptix_temporal_stats* out);
+int moptix_temporal_read(moptix_context ctx, const moptix_temporal_buffers* dstHost);
 
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --

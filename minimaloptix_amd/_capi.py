@@ -112,6 +112,23 @@ class DenoiseParams(C.Structure):
                 ("sigmaLuminance", C.c_float), ("sigmaDepth", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    """moptix_temporal_params (include/moptix.h "denoiser: temporal accumulation")."""
+    _fields_ = [("alpha", C.c_float), ("alphaMoments", C.c_float), ("depthTolerance", C.c_float), ("normalThreshold", C.c_float),
+                ("maxHistory", C.c_int32), ("varianceFrames", C.c_int32)]
+
+
+class TemporalStats(C.Structure):
+    """moptix_temporal_stats: what moptix_temporal_info reports."""
+    _fields_ = [("frames", C.c_uint64), ("geometryPixels", C.c_uint64), ("historyPixels", C.c_uint64), ("disoccludedPixels", C.c_uint64),
+                ("meanHistory", C.c_float)]
+
+
+class TemporalBuffers(C.Structure):
+    """moptix_temporal_buffers: host pointers for moptix_temporal_read; NULL members are skipped."""
+    _fields_ = [("motion", C.c_void_p), ("history", C.c_void_p)]
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -125,6 +142,7 @@ DEVICE_SYMBOLS = [
     "moptix_packed_tile_floats", "moptix_pack_tiles", "moptix_unpack_tiles",
     "moptix_render_aovs", "moptix_aov_clear", "moptix_aov_samples", "moptix_aov_read", "moptix_aov_bind",
     "moptix_denoise_defaults", "moptix_denoise", "moptix_denoise_read", "moptix_denoise_bind",
+    "moptix_temporal_defaults", "moptix_denoise_temporal", "moptix_temporal_reset", "moptix_temporal_info", "moptix_temporal_read",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
@@ -204,6 +222,11 @@ def device_lib():
         L.moptix_denoise.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float]
         L.moptix_denoise_read.argtypes = [vp, f32p]
         L.moptix_denoise_bind.argtypes = [vp, vp]
+        L.moptix_temporal_defaults.argtypes = [C.POINTER(TemporalParams)]
+        L.moptix_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_float]
+        L.moptix_temporal_reset.argtypes = [vp]
+        L.moptix_temporal_info.argtypes = [vp, C.POINTER(TemporalStats)]
+        L.moptix_temporal_read.argtypes = [vp, C.POINTER(TemporalBuffers)]
         _dev = L
     return _dev
 

@@ -402,6 +402,51 @@ class Context:
             raise ValueError("denoise_bind: dtype %s" % tensor.dtype)
         self._chk(self._L.moptix_denoise_bind(self._h, C.c_void_p(tensor.data_ptr())))
 
+    # ---- temporal accumulation (include/moptix.h "denoiser: temporal accumulation") ----
+    def temporal_defaults(self):
+        """moptix_temporal_defaults as a dict: alpha, alpha_moments, depth_tolerance, normal_threshold, max_history, variance_frames."""
+        p = K.TemporalParams()
+        self._chk(self._L.moptix_temporal_defaults(C.byref(p)))
+        return dict(alpha=float(p.alpha), alpha_moments=float(p.alphaMoments), depth_tolerance=float(p.depthTolerance),
+                    normal_threshold=float(p.normalThreshold), max_history=int(p.maxHistory), variance_frames=int(p.varianceFrames))
+
+    def denoise_temporal(self, n_accumulation, temporal=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
+                         demodulate=False):
+        """denoise() with the temporal stage in front: last call's accumulation is reprojected through the AOVs (depth, normal, ids),
+        the camera of set_params and the spheres as update_spheres left them, and blended with this frame.  temporal: a dict with
+        some of temporal_defaults()'s keys (the rest keep their defaults).  Returns an (H, W, 3) float32 array as denoise()."""
+        t = self.temporal_defaults()
+        for k, v in (temporal or {}).items():
+            if k not in t:
+                raise ValueError("denoise_temporal: unknown temporal parameter %r" % k)
+            t[k] = v
+        tp = K.TemporalParams(float(t["alpha"]), float(t["alpha_moments"]), float(t["depth_tolerance"]), float(t["normal_threshold"]),
+                              int(t["max_history"]), int(t["variance_frames"]))
+        p = K.DenoiseParams(int(iterations), int(normal_power), 1 if demodulate else 0, float(sigma_luminance), float(sigma_depth))
+        self._chk(self._L.moptix_denoise_temporal(self._h, C.byref(p), C.byref(tp), float(n_accumulation)))
+        out = np.empty((self.height, self.width, 3), np.float32)
+        self._chk(self._L.moptix_denoise_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def temporal_reset(self):
+        """Drops the history: the next denoise_temporal call is a first frame."""
+        self._chk(self._L.moptix_temporal_reset(self._h))
+
+    def temporal_info(self):
+        """dict: frames since the last drop; of the last call geometry_pixels, history_pixels, disoccluded_pixels, mean_history."""
+        s = K.TemporalStats()
+        self._chk(self._L.moptix_temporal_info(self._h, C.byref(s)))
+        return dict(frames=int(s.frames), geometry_pixels=int(s.geometryPixels), history_pixels=int(s.historyPixels),
+                    disoccluded_pixels=int(s.disoccludedPixels), mean_history=float(s.meanHistory))
+
+    def temporal_read(self):
+        """Of the last denoise_temporal call: dict(motion=(H, W, 2) float32 pixel motion vectors, history=(H, W) float32 lengths)."""
+        motion = np.empty((self.height, self.width, 2), np.float32)
+        history = np.empty((self.height, self.width), np.float32)
+        b = K.TemporalBuffers(motion.ctypes.data, history.ctypes.data)
+        self._chk(self._L.moptix_temporal_read(self._h, C.byref(b)))
+        return dict(motion=motion, history=history)
+
     def debug_read_accel(self):
         a = self.accel_info()
         nodes = np.zeros((max(1, a.nNodes), 32), np.uint32)     # Node128 = 32 words

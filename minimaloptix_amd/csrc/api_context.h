@@ -144,6 +144,30 @@ struct moptix_context_t {
     size_t pixels = 0;               // frame size of the last denoise call (0: none since the last frame-size change)
     void release() { colA.release(); colB.release(); guide.release(); side.release(); out.release(); pixels = 0; }
   } dn;
+
+  // ---- temporal accumulation (api_temporal.hip): the history of moptix_denoise_temporal, two sets that swap roles per call; allocated
+  // at the first call, freed by a frame-size change.  The filter itself runs in the denoiser's scratch and writes the denoiser's output ----
+  struct Temporal {
+    DevBuf<pt::v4> col[2], guide[2], mom[2];   // {I_acc, h}, {N, Z}, {m1, m2, matId, -} (csrc/pt_temporal.h)
+    DevBuf<pt::v4> motion;                     // per sphere: centre now - centre at the previous call
+    DevBuf<float> motionOut, historyOut;       // last call's motion vectors (W*H*2) and history lengths (W*H)
+    DevBuf<unsigned long long> counters;       // TemporalCounters
+    DevBuf<unsigned int> partials;             // four words per 16x16 workgroup of the reproject kernel
+    std::vector<pt::v4> motionHost;            // staging of `motion`: outlives the asynchronous upload
+    int cur = 0;                               // the set the last call wrote
+    bool have = false;                         // a history to reproject from (false: the next call is a first frame)
+    uint32_t width = 0, height = 0; int nSpheres = 0, demodulate = 0;     // what the history was made with
+    moptix_cam_params cam{}; std::vector<pt::v3> centres;                 // snapshot at the end of the last call
+    uint64_t frames = 0;                       // calls since the last drop
+    size_t pixels = 0;                         // frame size of the last call's motion vectors / history lengths (0: none)
+    unsigned long long last[4] = { 0, 0, 0, 0 };
+    void drop() { have = false; frames = 0; }
+    void release() {
+      for (int i = 0; i < 2; i++) { col[i].release(); guide[i].release(); mom[i].release(); }
+      motion.release(); motionOut.release(); historyOut.release(); counters.release(); partials.release();
+      drop(); pixels = 0;
+    }
+  } tp;
 };
 
 namespace pt { namespace api {

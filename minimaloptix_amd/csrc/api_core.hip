@@ -109,7 +109,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release();
+  c->aov.release(); c->dn.release(); c->tp.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -143,6 +143,7 @@ int moptix_set_params(moptix_context c, const moptix_params* p) {
   if (resized && !c->accumBound) { c->accumPixels = 0; }
   if (resized) c->aov.frame_resized();
   if (resized) c->dn.release();                                // the denoiser's scratch and output are reallocated at its next call
+  if (resized) c->tp.release();                                // and the temporal history with them
   return MOPTIX_OK;
 }
 
@@ -152,6 +153,7 @@ int moptix_clear_scene(moptix_context c) {
   c->facePos.clear(); c->faceNrm.clear(); c->faceHasNrm.clear(); c->faceMat.clear();
   c->faceUV.clear(); c->anyUV = false; c->textures.clear();
   c->sceneDirty = true; c->accelBuilt = false;
+  c->tp.drop();                                                // the temporal history belongs to the scene that made it
   return MOPTIX_OK;
 }
 

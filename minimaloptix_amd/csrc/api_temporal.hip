@@ -1,0 +1,164 @@
+// api_temporal.hip -- temporal accumulation in front of the denoiser (temporalkernel.hip, pt_temporal.h): the moptix_temporal_* entry
+// points and moptix_denoise_temporal of include/moptix.h.  The history lives in the context (api_context.h Temporal); the filter runs
+// in the denoiser's scratch and writes the denoiser's output, which moptix_denoise_read / moptix_denoise_bind serve for both entries.
+#include <cstring>
+
+#include "api_context.h"
+#include "temporalkernel.h"
+
+using namespace pt;
+using namespace pt::api;
+
+namespace {
+
+v3 to3(const moptix_float3& f) { return mk3(f.x, f.y, f.z); }
+TpCamera to_camera(const moptix_cam_params& c) {
+  TpCamera t; t.origin = to3(c.origin); t.horizontal = to3(c.horizontal); t.vertical = to3(c.vertical); t.lowerLeft = to3(c.scrLowerLeftCorner);
+  return t;
+}
+
+bool finite_in(float v, float lo, float hi) { return __builtin_isfinite(v) && v >= lo && v <= hi; }
+
+const char* bad_temporal_params(const moptix_temporal_params* t) {
+  if (!finite_in(t->alpha, 0.0f, 1.0f) || !finite_in(t->alphaMoments, 0.0f, 1.0f)) return "alpha and alphaMoments in [0,1]";
+  if (!__builtin_isfinite(t->depthTolerance) || !(t->depthTolerance >= 0.0f)) return "depthTolerance must be finite and >= 0";
+  if (!finite_in(t->normalThreshold, -1.0f, 1.0f)) return "normalThreshold in [-1,1]";
+  if (t->maxHistory < 1 || t->maxHistory > 65536) return "maxHistory in [1,65536]";
+  if (t->varianceFrames < 1 || t->varianceFrames > 65536) return "varianceFrames in [1,65536]";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int moptix_temporal_defaults(moptix_temporal_params* out) {
+  if (!out) return fail(nullptr, MOPTIX_ERR_INVALID, "null argument");
+  out->alpha = 0.2f; out->alphaMoments = 0.2f; out->depthTolerance = 0.2f; out->normalThreshold = 0.5f;
+  out->maxHistory = 32; out->varianceFrames = 4;
+  return MOPTIX_OK;
+}
+
+int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, const moptix_temporal_params* t, float nAccumulation) {
+  // the checks of the arguments themselves come first: they need no context (a NULL one then fails as a null argument)
+  if (!p || !t) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  if (!(nAccumulation > 0.0f) || !__builtin_isfinite(nAccumulation)) return fail(c, MOPTIX_ERR_INVALID, "nAccumulation must be > 0");
+  if (p->iterations < 0 || p->iterations > 8) return fail(c, MOPTIX_ERR_INVALID, "iterations in [0,8]");
+  if (p->normalPower < 1 || p->normalPower > 256) return fail(c, MOPTIX_ERR_INVALID, "normalPower in [1,256]");
+  if (p->demodulate != 0 && p->demodulate != 1) return fail(c, MOPTIX_ERR_INVALID, "demodulate is 0 or 1");
+  if (!(p->sigmaLuminance >= 0.0f) || !__builtin_isfinite(p->sigmaLuminance) || !(p->sigmaDepth >= 0.0f) || !__builtin_isfinite(p->sigmaDepth))
+    return fail(c, MOPTIX_ERR_INVALID, "sigmas must be finite and >= 0");
+  if (const char* why = bad_temporal_params(t)) return fail(c, MOPTIX_ERR_INVALID, why);
+  if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
+  if (c->poisoned) return fail(c, MOPTIX_ERR_COMM, "this context is unusable: kernels of an aborted collective never left its stream");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "moptix_set_params has not been called");
+  if (c->aov.samples == 0) return fail(c, MOPTIX_ERR_STATE, "no AOV samples: moptix_render_aovs first");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;       // a beauty batch still in flight finishes (and is timed) first
+  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  const size_t px = (size_t)c->params.width * c->params.height;
+  if (px > 0x7fffffffULL) return fail(c, MOPTIX_ERR_LIMIT, "frame too large");
+  moptix_context_t::Temporal& s = c->tp;
+  const int demodulate = p->iterations > 0 ? p->demodulate : 0;
+  const int nSpheres = (int)c->spheres.size();
+  if (!tp_history_kept(s.have, (int)s.width, (int)s.height, s.nSpheres, s.demodulate, (int)c->params.width, (int)c->params.height, nSpheres, demodulate))
+    s.drop();
+  HIPCHK(c, c->dn.colA.ensure(px), "alloc denoiser");
+  HIPCHK(c, c->dn.colB.ensure(px), "alloc denoiser");
+  HIPCHK(c, c->dn.side.ensure(px), "alloc denoiser");
+  if (!c->dn.bound) HIPCHK(c, c->dn.out.ensure(3 * px), "alloc denoiser output");
+  for (int i = 0; i < 2; i++) {
+    HIPCHK(c, s.col[i].ensure(px), "alloc temporal history");
+    HIPCHK(c, s.guide[i].ensure(px), "alloc temporal history");
+    HIPCHK(c, s.mom[i].ensure(px), "alloc temporal history");
+  }
+  HIPCHK(c, s.motionOut.ensure(2 * px), "alloc motion vectors");
+  HIPCHK(c, s.historyOut.ensure(px), "alloc history lengths");
+  HIPCHK(c, s.counters.ensure(4), "alloc temporal counters");
+  HIPCHK(c, s.motion.ensure((size_t)nSpheres), "alloc sphere motion");
+  const size_t nGroups = (size_t)((c->params.width + 15) / 16) * ((c->params.height + 15) / 16);
+  HIPCHK(c, s.partials.ensure(4 * nGroups), "alloc temporal partials");
+
+  TemporalArgs a;
+  memset(&a, 0, sizeof(a));
+  a.k.width = (int)c->params.width; a.k.height = (int)c->params.height; a.k.normalPower = p->normalPower;
+  a.k.sigmaLuminance = p->sigmaLuminance; a.k.sigmaDepth = p->sigmaDepth;
+  a.t.width = a.k.width; a.t.height = a.k.height;
+  a.t.maxHistory = t->maxHistory; a.t.varianceFrames = t->varianceFrames;
+  a.t.alpha = t->alpha; a.t.alphaMoments = t->alphaMoments; a.t.depthTolerance = t->depthTolerance; a.t.normalThreshold = t->normalThreshold;
+  a.t.cam = to_camera(c->params.cam);
+  a.t.haveHistory = s.have ? 1 : 0;
+  if (s.have) {
+    const TpCamera prev = to_camera(s.cam);
+    tp_solve_consts(prev, a.t);
+    a.t.sameCamera = tp_same_camera(prev, a.t.cam) ? 1 : 0;
+    a.t.nSpheres = nSpheres;
+    s.motionHost.resize((size_t)nSpheres);                    // a member: the call's final synchronise comes before its next change
+    for (int i = 0; i < nSpheres; i++) {
+      const v3 d = c->spheres[i].center - s.centres[i];
+      s.motionHost[i] = mk4(d.x, d.y, d.z, 0.0f);
+    }
+    if (nSpheres > 0)
+      HIPCHK(c, hipMemcpyAsync(s.motion.p, s.motionHost.data(), sizeof(v4) * nSpheres, hipMemcpyHostToDevice, c->stream), "upload sphere motion");
+  }
+  const moptix_aov_buffers b = aov_ptrs(c);
+  a.accum = accum_ptr(c); a.albedo = b.albedo; a.normal = b.normal; a.depth = b.depth; a.hits = b.hits;
+  a.primId = b.primId; a.matId = b.matId;
+  a.nAccumulation = nAccumulation; a.nSamples = (float)c->aov.samples;
+  a.iterations = p->iterations; a.demodulate = demodulate;
+  const int prev = s.cur, cur = s.cur ^ 1;
+  a.prevCol = s.col[prev].p; a.prevGuide = s.guide[prev].p; a.prevMom = s.mom[prev].p; a.motion = s.motion.p;
+  a.histCol = s.col[cur].p; a.histGuide = s.guide[cur].p; a.histMom = s.mom[cur].p;
+  a.colA = c->dn.colA.p; a.colB = c->dn.colB.p; a.side = c->dn.side.p;
+  a.motionOut = s.motionOut.p; a.historyOut = s.historyOut.p;
+  a.partials = reinterpret_cast<uint4*>(s.partials.p);
+  a.counters = reinterpret_cast<TemporalCounters*>(s.counters.p);
+  a.out = c->dn.bound ? c->dn.bound : c->dn.out.p;
+  const uint64_t frames = s.frames;
+  s.drop();                                                  // a failure below leaves no half-written history behind
+  HIPCHK(c, launch_temporal(c->stream, a), "launch temporal denoiser");
+  HIPCHK(c, hipMemcpyAsync(s.last, s.counters.p, sizeof(s.last), hipMemcpyDeviceToHost, c->stream), "read temporal counters");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "temporal denoiser");
+  s.cur = cur; s.have = true; s.frames = frames + 1;
+  s.width = c->params.width; s.height = c->params.height; s.nSpheres = nSpheres; s.demodulate = demodulate;
+  s.cam = c->params.cam;
+  s.centres.resize((size_t)nSpheres);
+  for (int i = 0; i < nSpheres; i++) s.centres[i] = c->spheres[i].center;
+  s.pixels = px;
+  c->dn.pixels = px;
+  return MOPTIX_OK;
+}
+
+int moptix_temporal_reset(moptix_context c) {
+  if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
+  c->tp.drop();
+  return MOPTIX_OK;
+}
+
+int moptix_temporal_info(moptix_context c, moptix_temporal_stats* out) {
+  if (!c || !out) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  const moptix_context_t::Temporal& s = c->tp;
+  memset(out, 0, sizeof(*out));
+  out->frames = s.frames;
+  if (s.pixels == 0) return MOPTIX_OK;
+  out->geometryPixels = s.last[0]; out->historyPixels = s.last[1]; out->disoccludedPixels = s.last[2];
+  out->meanHistory = s.last[0] ? (float)((double)s.last[3] / (double)s.last[0]) : 0.0f;
+  return MOPTIX_OK;
+}
+
+int moptix_temporal_read(moptix_context c, const moptix_temporal_buffers* dstHost) {
+  if (!c || !dstHost) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
+  const size_t px = (size_t)c->params.width * c->params.height;
+  if (c->tp.pixels != px) return fail(c, MOPTIX_ERR_STATE, "no moptix_denoise_temporal call at this frame size");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc;
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
+  if (dstHost->motion) HIPCHK(c, hipMemcpyAsync(dstHost->motion, c->tp.motionOut.p, sizeof(float) * 2 * px, hipMemcpyDeviceToHost, c->stream), "read motion vectors");
+  if (dstHost->history) HIPCHK(c, hipMemcpyAsync(dstHost->history, c->tp.historyOut.p, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read history lengths");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  return MOPTIX_OK;
+}
+
+}  // extern "C"

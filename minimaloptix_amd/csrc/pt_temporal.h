@@ -1,0 +1,187 @@
+// pt_temporal.h -- per-pixel code of the denoiser's temporal stage (include/moptix.h "denoiser: temporal accumulation", DESIGN.md
+// "Denoiser").
+//
+// SVGF's temporal half (Schied et al. 2017) in front of the a-trous iterations of pt_denoise.h: the previous call's pre-filter
+// accumulation is reprojected through the first-hit geometry (depth, normal, material id, the two cameras, the spheres' motion),
+// blended with this frame's demodulated beauty, and the temporal luminance moments replace the 3x3 spatial variance guess where a pixel
+// has enough history.  As in pt_denoise.h every pass is a function of one pixel over buffers of the previous pass or call, so the
+// kernels (temporalkernel.hip) and their CPU mirror (tests/temporalsim) run exactly these operations in this order and agree bit for
+// bit; the arithmetic follows the contract of pt_math.h (AC1-AC5, -ffp-contract=off, no libm transcendental).
+//
+// History, per pixel, three 16-byte records (one vector load per tap each):
+//   col   {I_acc.rgb, h}        the pre-filter accumulation and the history length (an integer kept as binary32)
+//   guide {N.xyz, Z}            the frame's normal and depth as dn_decode wrote them (Z = kDnBackground: never a tap); the same buffer
+//                               guides the a-trous passes of the call that wrote it
+//   mom   {m1, m2, matId, 0}    luminance moments; the material id rides in the spare third component as its bits (i2f), so the
+//                               material test costs no load of its own
+#pragma once
+#include "pt_denoise.h"
+
+namespace pt {
+
+constexpr float kTpMinWeight = 1e-2f;         // total weight of the valid taps below which a pixel counts as disoccluded
+constexpr float kTpSpatialVariance = -1.0f;   // col.w after tp_reproject where the prepass takes the 3x3 spatial estimate
+
+struct TpCamera { v3 origin, horizontal, vertical, lowerLeft; };
+
+// What tp_reproject reads besides the buffers; all wave-uniform (kernel arguments).
+struct TemporalConsts {
+  int width, height;
+  int haveHistory;              // 0: first frame after a drop, every pixel h = 1
+  int sameCamera;               // the previous camera is this one bit for bit
+  int nSpheres;                 // entries of the motion buffer (0 without history)
+  int maxHistory, varianceFrames;
+  float alpha, alphaMoments, depthTolerance, normalThreshold;
+  TpCamera cam;                 // this frame's
+  v3 prevOrigin;                // o'
+  v3 bc, ca, ab;                // cross(b, c), cross(c, a), cross(a, b) of a = LL' - o', b = H', c = V'
+  float det;                    // dot(a, bc)
+};
+
+// The 3x3 solve's constants from the previous camera.
+PT_HD void tp_solve_consts(const TpCamera& prev, TemporalConsts& k) {
+  const v3 a = prev.lowerLeft - prev.origin, b = prev.horizontal, c = prev.vertical;
+  k.prevOrigin = prev.origin;
+  k.bc = cross(b, c); k.ca = cross(c, a); k.ab = cross(a, b);
+  k.det = dot(a, k.bc);
+}
+
+PT_HD bool tp_same_camera(const TpCamera& p, const TpCamera& q) {
+  const float* a = &p.origin.x; const float* b = &q.origin.x;
+  for (int i = 0; i < 12; i++) if (f2i(a[i]) != f2i(b[i])) return false;
+  return true;
+}
+
+// Is the history of the previous call usable for this one?  (step 8 of the contract: frame size, sphere count, demodulation)
+PT_HD bool tp_history_kept(bool have, int prevW, int prevH, int prevSpheres, int prevDemodulate, int w, int h, int nSpheres, int demodulate) {
+  return have && prevW == w && prevH == h && prevSpheres == nSpheres && prevDemodulate == demodulate;
+}
+
+struct TpResult {
+  v4 col;             // {I_acc, v or kTpSpatialVariance}: the a-trous input
+  v4 hist;            // {I_acc, h}
+  v4 mom;             // {m1, m2, matId bits, 0}
+  float mvx, mvy;     // motion vector (x - fx, y - fy); 0 without history
+  bool geometry, history;
+};
+
+// Steps 1-6 for pixel (x, y) whose decoded signal, guide and ids are (col.xyz = I, guide = {N, Z}).  motion[i] = centre_now -
+// centre_prev of sphere i (k.nSpheres entries).  Operation order:
+//   u = (x + 0.5) / W, v = (y + 0.5) / H                                 (int -> float conversions exact)
+//   t = ((LL + u * Hz) + v * V) - o per component; d = normalize(t) (AC3); P = fma(Z, d, o) (AC7)
+//   P' = P - motion[primId] per component when 0 <= primId < nSpheres
+//   r = P' - o'; sn = dot(r, bc); s = sn / det; no history unless det != 0 and s > 0
+//   fx = (dot(r, ca) / sn) * W - 0.5, fy = (dot(r, ab) / sn) * H - 0.5; Z' = length(r)
+//   (the same camera bit for bit and a zero motion: fx = x, fy = y, Z' = Z exactly -- a static pixel maps onto itself)
+//   no history unless -1 < fx < W and -1 < fy < H; x0 = floor(fx), tx = fx - x0 (y alike)
+//   taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in this order, weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty;
+//     a tap counts iff its weight > 0, it is inside the frame, geometry in the previous frame, of the same material,
+//     dot(N_p, N_q) >= normalThreshold and |Z_q - Z'| <= depthTolerance * Z'
+//     sw += w; sI += w * I_q (per channel); s1 += w * m1_q; s2 += w * m2_q; hmin = min(hmin, h_q)
+//   history iff a tap counted and sw >= 1e-2: I_prev = sI / sw, m1_prev = s1 / sw, m2_prev = s2 / sw (one division each)
+//   h = min(hmin + 1, maxHistory); a = max(1 / h, alpha); I_acc = I_prev + a * (I - I_prev); moments alike with alphaMoments on
+//   l = l(I), l * l; without history h = 1, I_acc = I, m1 = l, m2 = l * l
+//   v = h >= varianceFrames ? max(0, m2 - m1 * m1) : kTpSpatialVariance
+PT_HD TpResult tp_reproject(const TemporalConsts& k, const v4* histCol, const v4* histGuide, const v4* histMom, const v4* motion,
+                            int x, int y, const v4& col, const v4& guide, int primId, int matId) {
+  TpResult o;
+  o.mvx = 0.0f; o.mvy = 0.0f; o.history = false;
+  o.geometry = dn_geometry(guide);
+  const v3 I = xyz(col);
+  if (!o.geometry) {
+    o.col = mk4(I.x, I.y, I.z, 0.0f); o.hist = mk4(I.x, I.y, I.z, 1.0f); o.mom = mk4(0.0f, 0.0f, i2f(matId), 0.0f);
+    return o;
+  }
+  const float l = dn_luminance(I);
+  v3 sI = mk3(0.0f, 0.0f, 0.0f);
+  float sw = 0.0f, s1 = 0.0f, s2 = 0.0f, hmin = 0.0f;
+  bool any = false;
+  float fx = 0.0f, fy = 0.0f;
+  if (k.haveHistory) {
+    const float Z = guide.w;
+    v3 mo = mk3(0.0f, 0.0f, 0.0f);
+    if (primId >= 0 && primId < k.nSpheres) mo = xyz(motion[primId]);
+    const bool still = k.sameCamera && mo.x == 0.0f && mo.y == 0.0f && mo.z == 0.0f;
+    bool ok = true;
+    float zp = Z;
+    if (still) {
+      fx = (float)x; fy = (float)y;
+    } else {
+      const float u = ((float)x + 0.5f) / (float)k.width, v = ((float)y + 0.5f) / (float)k.height;
+      const v3 t = mk3(((k.cam.lowerLeft.x + u * k.cam.horizontal.x) + v * k.cam.vertical.x) - k.cam.origin.x,
+                       ((k.cam.lowerLeft.y + u * k.cam.horizontal.y) + v * k.cam.vertical.y) - k.cam.origin.y,
+                       ((k.cam.lowerLeft.z + u * k.cam.horizontal.z) + v * k.cam.vertical.z) - k.cam.origin.z);
+      const v3 P = ray_at(k.cam.origin, normalize(t), Z);
+      const v3 r = (P - mo) - k.prevOrigin;
+      const float sn = dot(r, k.bc);
+      const float s = sn / k.det;
+      ok = k.det != 0.0f && s > 0.0f;
+      if (ok) {
+        fx = (dot(r, k.ca) / sn) * (float)k.width - 0.5f;
+        fy = (dot(r, k.ab) / sn) * (float)k.height - 0.5f;
+        zp = length(r);
+      }
+    }
+    ok = ok && fx > -1.0f && fx < (float)k.width && fy > -1.0f && fy < (float)k.height;
+    if (ok) {
+      const float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy);
+      const int x0 = (int)flx, y0 = (int)fly;
+      const float tx = fx - flx, ty = fy - fly;
+      const float ux = 1.0f - tx, uy = 1.0f - ty;
+      const v3 np = xyz(guide);
+      const float tol = k.depthTolerance * zp;
+      for (int j = 0; j < 2; j++) {
+        const int qy = y0 + j;
+        if (qy < 0 || qy >= k.height) continue;
+        for (int i = 0; i < 2; i++) {
+          const int qx = x0 + i;
+          if (qx < 0 || qx >= k.width) continue;
+          const float w = (i ? tx : ux) * (j ? ty : uy);
+          if (!(w > 0.0f)) continue;
+          const int q = qy * k.width + qx;
+          const v4 gq = histGuide[q];
+          if (!dn_geometry(gq)) continue;
+          const v4 mq = histMom[q];
+          if (f2i(mq.z) != matId) continue;
+          if (!(dot(np, xyz(gq)) >= k.normalThreshold)) continue;
+          if (!(__builtin_fabsf(gq.w - zp) <= tol)) continue;
+          const v4 cq = histCol[q];
+          sw = sw + w;
+          sI = mk3(sI.x + w * cq.x, sI.y + w * cq.y, sI.z + w * cq.z);
+          s1 = s1 + w * mq.x; s2 = s2 + w * mq.y;
+          hmin = any ? fminf_(hmin, cq.w) : cq.w;
+          any = true;
+        }
+      }
+    }
+  }
+  float h = 1.0f, m1 = l, m2 = l * l;
+  v3 acc = I;
+  if (any && sw >= kTpMinWeight) {
+    o.history = true;
+    o.mvx = (float)x - fx; o.mvy = (float)y - fy;
+    h = fminf_(hmin + 1.0f, (float)k.maxHistory);
+    const float ih = 1.0f / h;
+    const float a = fmaxf_(ih, k.alpha), am = fmaxf_(ih, k.alphaMoments);
+    const v3 ip = mk3(sI.x / sw, sI.y / sw, sI.z / sw);
+    const float p1 = s1 / sw, p2 = s2 / sw;
+    acc = mk3(ip.x + a * (I.x - ip.x), ip.y + a * (I.y - ip.y), ip.z + a * (I.z - ip.z));
+    m1 = p1 + am * (l - p1);
+    m2 = p2 + am * (l * l - p2);
+  }
+  const float var = h >= (float)k.varianceFrames ? fmaxf_(m2 - m1 * m1, 0.0f) : kTpSpatialVariance;
+  o.col = mk4(acc.x, acc.y, acc.z, var);
+  o.hist = mk4(acc.x, acc.y, acc.z, h);
+  o.mom = mk4(m1, m2, i2f(matId), 0.0f);
+  return o;
+}
+
+// The prepass after tp_reproject, geometry pixel (x, y): the depth gradient as dn_prepass, and its 3x3 spatial variance (taken on
+// I_acc) only where the temporal one is not there.
+PT_HD float tp_prepass(const DenoiseConsts& k, const v4* col, const v4* guide, int x, int y, float& g) {
+  const float spatial = dn_prepass(k, col, guide, x, y, g);
+  const float v = col[y * k.width + x].w;
+  return v == kTpSpatialVariance ? spatial : v;
+}
+
+}  // namespace pt

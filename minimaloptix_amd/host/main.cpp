@@ -22,6 +22,10 @@ static void usage() {
           "                     [--aov]  also PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm: first-hit AOVs of the same seeds (rank 0)\n"
           "                     [--denoise [--denoise-iterations L]]  also PREFIX_denoised.pfm / .png: the frame through the AOV-guided\n"
           "                              a-trous denoiser (default parameters, L = 0..8 iterations, default 5), on rank 0 after the gather\n"
+          "                     [--video-frames N [--denoise-temporal]]  scene random_spheres_256, one rank: after the frame, N animation steps\n"
+          "                              (spheres move, camera orbits, --spp new seeds each) saved as PREFIX_videoI.png; with --denoise-temporal\n"
+          "                              also PREFIX_videoI_denoised.pfm / .png: the step through the denoiser with temporal accumulation\n"
+          "                              (default parameters, --denoise-iterations L)\n"
           "       multi-GPU (one process per GPU, tile split + RCCL gather to rank 0, which writes the image):\n"
           "                     [--spawn N]  start N ranks of this program, rank r on device r, and wait for them\n"
           "                     [--spawn-same-device]  ... every rank on --device (a one-GPU box; needs a transport that accepts it,\n"
@@ -32,8 +36,8 @@ static void usage() {
 int main(int argc, char** argv) {
   std::string scene = "spheres", prefix = "frame", scenes = "scenes/", outdir = ".";
   unsigned spp = 32, width = 1920, height = 1080, seed = 0;
-  int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false, denoise = false;
-  int denoiseIterations = 5;
+  int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false, denoise = false, denoiseTemporal = false;
+  int denoiseIterations = 5, videoFrames = 0;
   int rank = 0, ranks = 1, spawn = 0, spawnTimeout = 600; bool spawnSame = false; std::string commFile;
   for (int i = 1; i < argc; i++) {
     auto need = [&](const char* n) { if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", n); exit(2); } return argv[++i]; };
@@ -57,8 +61,17 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--strict-missing")) strict = true;
     else if (!strcmp(argv[i], "--aov")) aov = true;
     else if (!strcmp(argv[i], "--denoise")) denoise = true;
+    else if (!strcmp(argv[i], "--video-frames")) videoFrames = atoi(need("--video-frames"));
+    else if (!strcmp(argv[i], "--denoise-temporal")) denoiseTemporal = true;
     else if (!strcmp(argv[i], "--denoise-iterations")) denoiseIterations = atoi(need("--denoise-iterations"));
     else { usage(); return 2; }
+  }
+  if (videoFrames < 0) { fprintf(stderr, "moptix_render: --video-frames must be >= 0\n"); return 2; }
+  if (denoiseTemporal && videoFrames == 0) { fprintf(stderr, "moptix_render: --denoise-temporal needs --video-frames N\n"); return 2; }
+  if (videoFrames > 0 && scene != "random_spheres_256") { fprintf(stderr, "moptix_render: --video-frames needs --scene random_spheres_256 (the animated scene)\n"); return 2; }
+  if (videoFrames > 0 && (spawn > 1 || ranks > 1)) {
+    fprintf(stderr, "moptix_render: --video-frames is for one rank (the animation steps have no tile gather)\n");
+    return 2;
   }
   if (spawn > 0) {
     // N ranks as child processes, forked before this process has touched the GPU (the parent never does); each child goes on
@@ -129,6 +142,11 @@ int main(int argc, char** argv) {
     app.renderScene(autosave, prefix);
     if (!autosave && rank == 0) app.saveCurrentFrame(false, prefix);
     if (aov && rank == 0) app.saveAovs(prefix);               // whole frame, on rank 0's context alone: no collective
+    app.denoiseTemporal = denoiseTemporal; app.videoPrefix = prefix;
+    for (int i = 0; i < videoFrames; i++) {
+      app.updateVideo();
+      app.saveCurrentFrame(false, prefix + "_video" + std::to_string(i));
+    }
     fprintf(stderr, "render %.3f ms (device), BVH build %.3f ms, %u nodes, depth %u\n", app.lastRenderMs,
             app.lastAccel.buildMs, app.lastAccel.nNodes, app.lastAccel.treeDepth);
   } catch (const std::exception& e) {

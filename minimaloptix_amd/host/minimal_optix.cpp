@@ -171,13 +171,19 @@ void MinimalOptiX::saveAovs(std::string fileNamePrefix) {
   }
 }
 
-void MinimalOptiX::saveDenoised(std::string fileNamePrefix) {
+void MinimalOptiX::saveDenoised(std::string fileNamePrefix, bool temporal) {
   check(moptix_aov_clear(context), "AOV clear");
   check(moptix_render_aovs(context, lastSeeds.data(), (int32_t)lastSeeds.size()), "render AOVs");
   moptix_denoise_params p;
   check(moptix_denoise_defaults(&p), "denoise defaults");
   p.iterations = denoiseIterations;
-  check(moptix_denoise(context, &p, (float)nSuperSampling), "denoise");
+  if (temporal) {
+    moptix_temporal_params t;
+    check(moptix_temporal_defaults(&t), "temporal defaults");
+    check(moptix_denoise_temporal(context, &p, &t, (float)nSuperSampling), "temporal denoise");
+  } else {
+    check(moptix_denoise(context, &p, (float)nSuperSampling), "denoise");
+  }
   const size_t px = (size_t)fixedWidth * fixedHeight;
   std::vector<float> out(3 * px);
   check(moptix_denoise_read(context, out.data()), "read denoised");
@@ -208,6 +214,11 @@ void MinimalOptiX::updateVideo() {
   std::vector<int32_t> seeds(nSuperSampling);
   for (uint i = 0; i < nSuperSampling; ++i) seeds[i] = randSeed();
   check(moptix_render(context, seeds.data(), (int32_t)nSuperSampling), "render");
+  if (denoiseTemporal && rank == 0) {                          // before the resolve below clears accuBuffer
+    lastSeeds = seeds;
+    saveDenoised(videoPrefix + "_video" + std::to_string(videoStep), true);
+  }
+  videoStep++;
   updateContent((float)nSuperSampling, true);
 }
 

@@ -93,7 +93,13 @@ public:
   // u8(clamp(v, 0, 1) * 255) as updateContent) in outputDir
   bool denoise = false;
   int denoiseIterations = 5;
-  void saveDenoised(std::string fileNamePrefix);
+  void saveDenoised(std::string fileNamePrefix, bool temporal = false);
+  // temporal accumulation over a video (new; include/moptix.h): with denoiseTemporal set, every updateVideo() step renders the AOVs of
+  // its seeds on rank 0, calls moptix_denoise_temporal (defaults, denoiseIterations) before its resolve clears accuBuffer, and writes
+  // <videoPrefix>_video<step>_denoised.pfm / .png through saveDenoised.  The first step is the history's first frame.
+  bool denoiseTemporal = false;
+  std::string videoPrefix = "frame";
+  int videoStep = 0;                  // updateVideo() steps taken
 
 private:
   uint launchCounter = 0;

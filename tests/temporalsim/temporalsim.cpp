@@ -1,0 +1,125 @@
+// temporalsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of moptix_denoise_temporal (minimaloptix_amd/csrc/temporalkernel.hip and the
+// history bookkeeping of api_temporal.hip): the same per-pixel code (pt_temporal.h, pt_denoise.h), compiled for the host and run
+// pass by pass over caller-given float arrays, in the order the kernels run it, with the history kept in an object between calls.
+// The GPU tests compare the device's output with this bit for bit.  It is not part of the product: nothing under minimaloptix_amd/
+// builds or loads it.
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/moptix.h"
+#include "../../minimaloptix_amd/csrc/pt_temporal.h"
+
+using namespace pt;
+
+namespace {
+
+struct Sim {
+  std::vector<v4> col[2], guide[2], mom[2];
+  int cur = 0;
+  bool have = false;
+  int width = 0, height = 0, nSpheres = 0, demodulate = 0;
+  TpCamera cam{};
+  std::vector<v3> centres;
+  uint64_t frames = 0;
+};
+
+TpCamera to_camera(const moptix_cam_params& c) {
+  TpCamera t;
+  t.origin = mk3(c.origin.x, c.origin.y, c.origin.z); t.horizontal = mk3(c.horizontal.x, c.horizontal.y, c.horizontal.z);
+  t.vertical = mk3(c.vertical.x, c.vertical.y, c.vertical.z);
+  t.lowerLeft = mk3(c.scrLowerLeftCorner.x, c.scrLowerLeftCorner.y, c.scrLowerLeftCorner.z);
+  return t;
+}
+
+}  // namespace
+
+extern "C" {
+
+void* temporalsim_create() { return new Sim; }
+void temporalsim_destroy(void* s) { delete (Sim*)s; }
+void temporalsim_reset(void* s) { ((Sim*)s)->have = false; ((Sim*)s)->frames = 0; }      // moptix_temporal_reset, moptix_clear_scene
+uint64_t temporalsim_frames(void* s) { return ((Sim*)s)->frames; }
+
+// moptix_denoise_temporal on the CPU over host arrays in the accumulation buffer's layout.  centres: nSpheres * 3 floats (the context's
+// spheres now).  Outputs, each optional: out W*H*3; motion W*H*2; history W*H; pre W*H*4 = {I_acc, v} as the first a-trous iteration
+// reads them (after the prepass; before it with iterations = 0); counters[4] = geometry, history, disoccluded pixels, sum of h over
+// the geometry pixels.  Parameters are taken as given (the C ABI checks their ranges).
+int temporalsim_run(void* state, int width, int height, const float* accum, const float* albedo, const float* normal, const float* depth,
+                    const float* hits, const int32_t* primId, const int32_t* matId, float nAccumulation, float nSamples,
+                    const moptix_cam_params* cam, const float* centres, int nSpheres, const moptix_denoise_params* prm,
+                    const moptix_temporal_params* tprm, float* out, float* motionOut, float* historyOut, float* pre, uint64_t* counters) {
+  Sim* s = (Sim*)state;
+  if (!s || width <= 0 || height <= 0 || !accum || !albedo || !normal || !depth || !hits || !primId || !matId || !cam || !prm || !tprm ||
+      (nSpheres > 0 && !centres))
+    return -1;
+  const int n = width * height;
+  const int demodulate = prm->iterations > 0 ? prm->demodulate : 0;
+  if (!tp_history_kept(s->have, s->width, s->height, s->nSpheres, s->demodulate, width, height, nSpheres, demodulate)) { s->have = false; s->frames = 0; }
+  DenoiseConsts k;
+  k.width = width; k.height = height; k.normalPower = prm->normalPower;
+  k.sigmaLuminance = prm->sigmaLuminance; k.sigmaDepth = prm->sigmaDepth;
+  TemporalConsts t{};
+  t.width = width; t.height = height; t.maxHistory = tprm->maxHistory; t.varianceFrames = tprm->varianceFrames;
+  t.alpha = tprm->alpha; t.alphaMoments = tprm->alphaMoments; t.depthTolerance = tprm->depthTolerance; t.normalThreshold = tprm->normalThreshold;
+  t.cam = to_camera(*cam);
+  t.haveHistory = s->have ? 1 : 0;
+  std::vector<v3> now((size_t)nSpheres);
+  for (int i = 0; i < nSpheres; i++) now[i] = mk3(centres[3 * i], centres[3 * i + 1], centres[3 * i + 2]);
+  std::vector<v4> motion((size_t)nSpheres);
+  if (s->have) {
+    tp_solve_consts(s->cam, t);
+    t.sameCamera = tp_same_camera(s->cam, t.cam) ? 1 : 0;
+    t.nSpheres = nSpheres;
+    for (int i = 0; i < nSpheres; i++) { const v3 d = now[i] - s->centres[i]; motion[i] = mk4(d.x, d.y, d.z, 0.0f); }
+  }
+  const int prev = s->cur, cur = s->cur ^ 1;
+  for (int i = 0; i < 2; i++) { s->col[i].resize(n); s->guide[i].resize(n); s->mom[i].resize(n); }
+  std::vector<v4> colA(n), colB(n), side(n);
+  std::vector<v4>& guide = s->guide[cur];
+  uint64_t cnt[4] = { 0, 0, 0, 0 };
+  for (int p = 0; p < n; p++) {
+    v4 c, g, sd;
+    dn_decode(accum, albedo, normal, depth, hits, nAccumulation, nSamples, demodulate, p, c, g, sd);
+    const TpResult r = tp_reproject(t, s->col[prev].data(), s->guide[prev].data(), s->mom[prev].data(), motion.data(), p % width, p / width,
+                                    c, g, primId[p], matId[p]);
+    colA[p] = r.col; side[p] = sd;
+    s->col[cur][p] = r.hist; guide[p] = g; s->mom[cur][p] = r.mom;
+    if (motionOut) { motionOut[2 * (size_t)p] = r.mvx; motionOut[2 * (size_t)p + 1] = r.mvy; }
+    if (historyOut) historyOut[p] = r.hist.w;
+    if (r.geometry) { cnt[0]++; cnt[1] += r.history ? 1 : 0; cnt[2] += r.history ? 0 : 1; cnt[3] += (uint64_t)r.hist.w; }
+  }
+  v4* curCol = colA.data();
+  if (prm->iterations > 0) {
+#pragma omp parallel for
+    for (int p = 0; p < n; p++) {
+      v4 c = colA[p];
+      if (dn_geometry(guide[p])) {
+        float g;
+        c.w = tp_prepass(k, colA.data(), guide.data(), p % width, p / width, g);
+        side[p].w = g;
+      }
+      colB[p] = c;
+    }
+    curCol = colB.data();
+    if (pre) for (int p = 0; p < n; p++) { pre[4 * (size_t)p] = colB[p].x; pre[4 * (size_t)p + 1] = colB[p].y; pre[4 * (size_t)p + 2] = colB[p].z; pre[4 * (size_t)p + 3] = colB[p].w; }
+    for (int i = 0; i < prm->iterations; i++) {
+      v4* next = curCol == colA.data() ? colB.data() : colA.data();
+#pragma omp parallel for
+      for (int p = 0; p < n; p++)
+        next[p] = dn_geometry(guide[p]) ? dn_iterate(k, curCol, guide.data(), p % width, p / width, 1 << i, side[p].w) : curCol[p];
+      curCol = next;
+    }
+  } else if (pre) {
+    for (int p = 0; p < n; p++) { pre[4 * (size_t)p] = colA[p].x; pre[4 * (size_t)p + 1] = colA[p].y; pre[4 * (size_t)p + 2] = colA[p].z; pre[4 * (size_t)p + 3] = colA[p].w; }
+  }
+  if (out) for (int p = 0; p < n; p++) dn_final(curCol[p], guide[p], side[p], out, p);
+  if (counters) for (int i = 0; i < 4; i++) counters[i] = cnt[i];
+  s->cur = cur; s->have = true; s->frames++;
+  s->width = width; s->height = height; s->nSpheres = nSpheres; s->demodulate = demodulate;
+  s->cam = t.cam; s->centres = now;
+  return 0;
+}
+
+}  // extern "C"
