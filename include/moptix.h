@@ -443,6 +443,69 @@ int moptix_temporal_reset(moptix_context ctx);
 int moptix_temporal_info(moptix_context ctx, moptix_temporal_stats* out);
 int moptix_temporal_read(moptix_context ctx, const moptix_temporal_buffers* dstHost);
 
+/* ---- adaptive sampling (new): per-pixel sample counts and luminance moments, and a render that stops sampling converged pixels ----
+ * moptix_render_adaptive renders a list of seeds like moptix_render, but after a first pass over the whole frame it keeps sampling
+ * only the pixels whose estimated error is above a threshold.  Whole frame only: with a tile split (moptix_set_partition other than
+ * (0, 1)) a pixel's 3x3 window crosses into other ranks' tiles and the call returns MOPTIX_ERR_STATE.
+ * Per-pixel state, in the accumulation buffer's pixel order (row 0 = bottom), allocated at the first adaptive call:
+ *   count      uint32      samples added to the pixel since the clear
+ *   moments    2 float32   s1 = sum l, s2 = sum l * l over those samples, plain binary32 adds in seed order; l = 0.2126 r + 0.7152 g +
+ *                          0.0722 b as the denoiser's l(I) (same operation order), of the clamped colour the trace kernel stored
+ *   converged  uint8       sticky: set once, cleared by moptix_adaptive_clear only
+ * Error of a pixel with n = count > 0: m = s1 / n, v = max(0, s2 / n - m * m) (biased), e = sqrt(v / n) / (m + 0.01) -- the relative
+ * standard error of the mean luminance with a floor of about 2.5 / 255; e = 0 where n = 0.  Every operation is one correctly rounded
+ * binary32 operation in the order written (n converted to float once; csrc/pt_adaptive.h).
+ * After each pass, for every pixel that is not converged: needs = n < minSamples || max of e over the in-frame pixels of its 3x3
+ * window > threshold; a pixel that does not need more becomes converged.  threshold == 0 means "no pixel converges".
+ * Passes: pass 0 takes the first min(minSamples, nSeeds) seeds, every later pass up to `batch` seeds, until the seeds are used up or
+ * no pixel is active.  A pixel active in a pass gets ALL seeds of that pass, so every pixel's samples are a prefix of the seed list:
+ *   accum[p] has the bits that moptix_render(seeds[0 : count[p]]) on a cleared accumulator leaves in accum[p],
+ * and with threshold = 0 the accumulation buffer has the bits of moptix_render(seeds), count == nSeeds everywhere.  The budget of the
+ * per-sample buffer ("sample_buffer_mb") cuts a pass into sub-passes as it cuts moptix_render's; per pixel nothing changes.
+ * A second call without a clear continues: the new seeds go to the pixels still active, counts and moments keep adding, and it has no
+ * minSamples pass of its own when the state already holds a pass (every pass is then up to `batch` seeds).  Seed lists A then B with
+ * the same parameters give the bits of one call with A + B WHEN A's length is a pass boundary of the joint call (minSamples + j *
+ * batch), not otherwise.
+ * The passes run through a trace kernel that keeps its paths in slots, handing the work out by pixel ("tile_major" 3), whatever the
+ * options "tile_major", "kernel_variant" and "analytic_queue" say: where moptix_render would take the per-lane kernel the queue kernel
+ * runs (get_option "kernel_variant_used" tells).  The kernels give the same bits (see the options), so this changes time only; the
+ * options read back as the caller set them.  The depth history that orders work items keeps being updated and is restarted per pixel
+ * when it was kept per tile.
+ * The counts describe what is in the accumulation buffer, so the two cannot be mixed silently:
+ *   - moptix_accum_clear, moptix_accum_bind, a clearing moptix_resolve_rgb8 and a change of frame size drop the adaptive state (it is
+ *     zeroed at the next adaptive call; bound memory is taken as it is: moptix_adaptive_clear before the first adaptive render into it);
+ *   - moptix_launch / moptix_render / moptix_render_async / moptix_render_counted after an adaptive call without a clear in between
+ *     return MOPTIX_ERR_STATE, and so does moptix_render_adaptive on an accumulator that those, moptix_unpack_tiles, moptix_gather_tiles
+ *     (on the destination rank) or moptix_reduce_frame have written to since its last clear.
+ * Ranges: threshold >= 0 and finite (default 0.03), minSamples >= 1 (16), batch >= 1 (64: every pass ends in the
+ * tail of its deepest paths, and sixteen passes of 16 seeds cost a 1920x1080 frame 45 % more than one of 256); bad values -> MOPTIX_ERR_INVALID.
+ *   moptix_adaptive_defaults      the defaults above; pure host (works without a device)
+ *   moptix_render_adaptive        blocking, on the context's stream; `out` may be NULL.  Stats: passes and samplesTraced of this call,
+ *                                 samplesUniform = in-frame pixels x nSeeds, and after the last pass the pixels still active, the
+ *                                 converged pixels, the smallest and largest count
+ *   moptix_adaptive_clear         zeroes count, moments, converged AND the accumulation buffer
+ *   moptix_adaptive_read          copies count (W*H uint32), moments (W*H*2 floats), error (W*H floats: e as defined, as of the last
+ *                                 pass) and converged (W*H bytes) to host memory; NULL members are skipped.  MOPTIX_ERR_STATE when
+ *                                 there is no adaptive state at this frame size (the reading entry points below alike)
+ *   moptix_adaptive_mean          W*H*3 floats: accum / count per pixel and channel (one division each), 0 where count is 0
+ *   moptix_adaptive_mean_device   the same into caller-owned device memory (e.g. the accumulator of a denoise call with nAccumulation 1)
+ *   moptix_adaptive_resolve_rgb8  moptix_resolve_rgb8's clamp, rounding and row flip on that mean; W*H*3 bytes, row 0 = top
+ * An adaptive call changes nothing else: not the AOVs, the denoiser's output, the temporal history or the node-format verdict. */
+typedef struct moptix_adaptive_params { float threshold; int32_t minSamples, batch; } moptix_adaptive_params;
+typedef struct moptix_adaptive_stats {
+  uint64_t passes, samplesTraced, samplesUniform;
+  uint64_t activePixelsLast, convergedPixels;
+  uint32_t minCount, maxCount;
+} moptix_adaptive_stats;
+typedef struct moptix_adaptive_buffers { uint32_t* count; float *moments, *error; uint8_t* converged; } moptix_adaptive_buffers;
+int moptix_adaptive_defaults(moptix_adaptive_params* out);
+int moptix_render_adaptive(moptix_context ctx, const int32_t* seeds, int32_t nSeeds, const moptix_adaptive_params* p, moptix_adaptive_stats* out);
+int moptix_adaptive_clear(moptix_context ctx);
+int moptix_adaptive_read(moptix_context ctx, const moptix_adaptive_buffers* dstHost);
+int moptix_adaptive_mean(moptix_context ctx, float* dstHost);
+int moptix_adaptive_mean_device(moptix_context ctx, float* dstDevice);
+int moptix_adaptive_resolve_rgb8(moptix_context ctx, uint8_t* dstHost);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --
  * and the number of its launches since the last reset */

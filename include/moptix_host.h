@@ -77,6 +77,13 @@ int mohost_render_scene(int device, int sceneId, const char* baseFolder, uint32_
                         uint32_t nSuperSampling, uint32_t baseSeed, int autoSave, const char* fileNamePrefix,
                         const char* outputDir, uint8_t* canvasRGB8, mohost_render_result* result);
 
+/* The same through moptix_render_adaptive (include/moptix.h "adaptive sampling"): the nSeeds launch seeds of the schedule rendered with
+ * `params` (NULL: moptix_adaptive_defaults), the canvas resolved with each pixel's own count.  Any of canvasRGB8 (W*H*3, row 0 = top),
+ * count (W*H), error (W*H floats; both row 0 = bottom) and stats may be NULL. */
+int mohost_render_scene_adaptive(int device, int sceneId, const char* baseFolder, uint32_t width, uint32_t height,
+                                 uint32_t nSeeds, uint32_t baseSeed, const moptix_adaptive_params* params,
+                                 uint8_t* canvasRGB8, uint32_t* count, float* error, moptix_adaptive_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

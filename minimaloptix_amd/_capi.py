@@ -129,6 +129,27 @@ class TemporalBuffers(C.Structure):
     _fields_ = [("motion", C.c_void_p), ("history", C.c_void_p)]
 
 
+class AdaptiveParams(C.Structure):
+    """moptix_adaptive_params (include/moptix.h "adaptive sampling")."""
+    _fields_ = [("threshold", C.c_float), ("minSamples", C.c_int32), ("batch", C.c_int32)]
+
+
+class AdaptiveStats(C.Structure):
+    """moptix_adaptive_stats: what moptix_render_adaptive reports."""
+    _fields_ = [("passes", C.c_uint64), ("samplesTraced", C.c_uint64), ("samplesUniform", C.c_uint64),
+                ("activePixelsLast", C.c_uint64), ("convergedPixels", C.c_uint64), ("minCount", C.c_uint32), ("maxCount", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(passes=int(self.passes), samples_traced=int(self.samplesTraced), samples_uniform=int(self.samplesUniform),
+                    active_pixels_last=int(self.activePixelsLast), converged_pixels=int(self.convergedPixels),
+                    min_count=int(self.minCount), max_count=int(self.maxCount))
+
+
+class AdaptiveBuffers(C.Structure):
+    """moptix_adaptive_buffers: host pointers for moptix_adaptive_read; NULL members are skipped."""
+    _fields_ = [("count", C.c_void_p), ("moments", C.c_void_p), ("error", C.c_void_p), ("converged", C.c_void_p)]
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -143,13 +164,15 @@ DEVICE_SYMBOLS = [
     "moptix_render_aovs", "moptix_aov_clear", "moptix_aov_samples", "moptix_aov_read", "moptix_aov_bind",
     "moptix_denoise_defaults", "moptix_denoise", "moptix_denoise_read", "moptix_denoise_bind",
     "moptix_temporal_defaults", "moptix_denoise_temporal", "moptix_temporal_reset", "moptix_temporal_info", "moptix_temporal_read",
+    "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
+    "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
     "mohost_scene_get_params", "mohost_scene_warning", "mohost_scene_copy", "mohost_scene_upload",
     "mohost_set_quad_params", "mohost_set_cam_params", "mohost_obj_stats", "mohost_render_scene",
     "mohost_animate_spheres", "mohost_video_camera", "mohost_scene_copy_texcoords", "mohost_scene_texture",
-    "mohost_read_image",
+    "mohost_read_image", "mohost_render_scene_adaptive",
 ]
 
 _dev = None
@@ -227,6 +250,13 @@ def device_lib():
         L.moptix_temporal_reset.argtypes = [vp]
         L.moptix_temporal_info.argtypes = [vp, C.POINTER(TemporalStats)]
         L.moptix_temporal_read.argtypes = [vp, C.POINTER(TemporalBuffers)]
+        L.moptix_adaptive_defaults.argtypes = [C.POINTER(AdaptiveParams)]
+        L.moptix_render_adaptive.argtypes = [vp, i32p, i32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+        L.moptix_adaptive_clear.argtypes = [vp]
+        L.moptix_adaptive_read.argtypes = [vp, C.POINTER(AdaptiveBuffers)]
+        L.moptix_adaptive_mean.argtypes = [vp, f32p]
+        L.moptix_adaptive_mean_device.argtypes = [vp, vp]
+        L.moptix_adaptive_resolve_rgb8.argtypes = [vp, u8p]
         _dev = L
     return _dev
 
@@ -261,5 +291,8 @@ def host_lib():
         L.mohost_obj_stats.argtypes = [C.c_char_p, i32p, i32p, i32p, i32p]
         L.mohost_render_scene.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(RenderResult)]
+        L.mohost_render_scene_adaptive.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.POINTER(AdaptiveParams), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_float), C.POINTER(AdaptiveStats)]
         _host = L
     return _host

@@ -447,6 +447,64 @@ class Context:
         self._chk(self._L.moptix_temporal_read(self._h, C.byref(b)))
         return dict(motion=motion, history=history)
 
+    # ---- adaptive sampling (include/moptix.h "adaptive sampling") ----
+    @staticmethod
+    def adaptive_defaults():
+        """moptix_adaptive_defaults as a dict: threshold, min_samples, batch.  Pure host: works without a device."""
+        p = K.AdaptiveParams()
+        rc = K.device_lib().moptix_adaptive_defaults(C.byref(p))
+        if rc != K.MOPTIX_OK:
+            raise MoptixError(rc, K.device_lib().moptix_last_error(None).decode())
+        return dict(threshold=float(p.threshold), min_samples=int(p.minSamples), batch=int(p.batch))
+
+    def render_adaptive(self, seeds, threshold=None, min_samples=None, batch=None):
+        """Renders `seeds` like render(), but after a first pass of min_samples seeds over the whole frame only the pixels whose
+        relative standard error (3x3 maximum) is above `threshold` get the following passes of `batch` seeds each; blocking.  None
+        keeps a parameter's default.  Returns the stats dict: passes, samples_traced, samples_uniform, active_pixels_last,
+        converged_pixels, min_count, max_count."""
+        d = self.adaptive_defaults()
+        p = K.AdaptiveParams(float(d["threshold"] if threshold is None else threshold),
+                             int(d["min_samples"] if min_samples is None else min_samples), int(d["batch"] if batch is None else batch))
+        s, sp = self._seeds(seeds)
+        st = K.AdaptiveStats()
+        self._chk(self._L.moptix_render_adaptive(self._h, sp, len(s), C.byref(p), C.byref(st)))
+        return st.as_dict()
+
+    def adaptive_clear(self):
+        """Zeroes the per-pixel counts, moments and converged flags AND the accumulation buffer."""
+        self._chk(self._L.moptix_adaptive_clear(self._h))
+
+    def adaptive_read(self):
+        """dict(count=(H, W) uint32, moments=(H, W, 2) float32, error=(H, W) float32, converged=(H, W) uint8) in accum_read's row
+        order (row 0 = bottom)."""
+        out = dict(count=np.empty((self.height, self.width), np.uint32), moments=np.empty((self.height, self.width, 2), np.float32),
+                   error=np.empty((self.height, self.width), np.float32), converged=np.empty((self.height, self.width), np.uint8))
+        b = K.AdaptiveBuffers(*[out[n].ctypes.data for n in ("count", "moments", "error", "converged")])
+        self._chk(self._L.moptix_adaptive_read(self._h, C.byref(b)))
+        return out
+
+    def adaptive_mean(self):
+        """accum / count per pixel (0 where count is 0): an (H, W, 3) float32 array in accum_read's row order."""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        self._chk(self._L.moptix_adaptive_mean(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def adaptive_mean_into(self, tensor):
+        """The same into a torch float32 tensor on this context's device, contiguous, H*W*3 elements."""
+        if not tensor.is_contiguous() or tensor.numel() != self.height * self.width * 3:
+            raise ValueError("adaptive_mean_into: must be a contiguous tensor of %d x %d x 3 elements" % (self.height, self.width))
+        if str(tensor.dtype) != "torch.float32":
+            raise ValueError("adaptive_mean_into: dtype %s" % tensor.dtype)
+        if not tensor.is_cuda:
+            raise ValueError("adaptive_mean_into: the tensor must live on the GPU (its data_ptr is handed to a kernel)")
+        self._chk(self._L.moptix_adaptive_mean_device(self._h, C.c_void_p(tensor.data_ptr())))
+
+    def adaptive_resolve_rgb8(self):
+        """resolve_rgb8 with each pixel's own count as the divisor: (H, W, 3) uint8, row 0 = top."""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        self._chk(self._L.moptix_adaptive_resolve_rgb8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
     def debug_read_accel(self):
         a = self.accel_info()
         nodes = np.zeros((max(1, a.nNodes), 32), np.uint32)     # Node128 = 32 words

@@ -271,6 +271,7 @@ int moptix_unpack_tiles(moptix_context c, int32_t rank, int32_t nRanks, const fl
   if (rc != MOPTIX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  c->accumPlain = true;                                      // samples without per-pixel counts (api_adaptive.hip)
   k_unpack_tiles<<<dim3((d.nItems + 255) / 256), dim3(256), 0, c->stream>>>(srcDevice, accum_ptr(c), d);
   HIPCHK(c, hipGetLastError(), "unpack tiles");
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
@@ -307,6 +308,7 @@ int moptix_gather_tiles(moptix_context c, int32_t dstRank) {
     if (recvErr != ncclSuccess && recvErr != ncclInProgress) return ncclFail(c, recvErr, "ncclRecv");
     // the receives are on the stream only once the group has settled (non-blocking communicator): the unpack kernels go behind them
     if ((rc = comm_settle(c, endErr, "ncclGroupEnd")) != MOPTIX_OK) return rc;
+    c->accumPlain = true;                                    // samples without per-pixel counts (api_adaptive.hip)
     for (int r = 0; r < n; r++) {                            // the other ranks' tiles into this rank's accuBuffer
       if (r == dstRank) continue;
       TileDeal dr = d; dr.rank = r;
@@ -325,6 +327,7 @@ int moptix_reduce_frame(moptix_context c, int32_t dstRank) {
   if (rc != MOPTIX_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  if (c->comm.ranks > 1) c->accumPlain = true;               // samples without per-pixel counts (api_adaptive.hip)
   if (c->comm.ranks > 1 && (rc = comm_settle(c, rccl().Reduce(accum_ptr(c), accum_ptr(c), 3 * c->accumPixels, ncclFloat, ncclSum, dstRank, c->comm.handle, c->stream), "ncclReduce")) != MOPTIX_OK)
     return rc;
   return c->comm.ranks > 1 ? comm_wait(c, "moptix_reduce_frame") : moptix_sync(c);

@@ -90,6 +90,7 @@ struct moptix_context_t {
 
   // ---- accumulation buffer and 8-bit resolve (api_core.hip) ----
   DevBuf<float> dAccum; float* accumBound = nullptr; size_t accumPixels = 0;
+  bool accumPlain = false;           // moptix_launch / render* have added to the accumulation buffer since its last clear (api_adaptive.hip)
   DevBuf<uint8_t> dRgb8;
 
   // ---- beauty launches (api_render.hip) ----
@@ -168,6 +169,25 @@ struct moptix_context_t {
       drop(); pixels = 0;
     }
   } tp;
+
+  // ---- adaptive sampling (api_adaptive.hip): per-pixel counts, luminance moments, the sticky converged flags and the order list of
+  // the adaptive passes; allocated and zeroed at the first adaptive call, dropped by whatever changes the accumulation buffer behind
+  // its back (frame-size change, moptix_accum_clear, moptix_accum_bind, a clearing moptix_resolve_rgb8) ----
+  struct Adaptive {
+    DevBuf<uint32_t> count; DevBuf<float> moments, error; DevBuf<uint8_t> converged;
+    DevBuf<unsigned int> key, keySorted; DevBuf<int> order, iota; DevBuf<uint8_t> sortTmp;
+    DevBuf<unsigned int> partials, totals;     // four words per 16x16 workgroup of the mask kernel; AdaptiveTotals
+    DevBuf<float> mean;                        // staging of moptix_adaptive_mean (allocated at its first call)
+    size_t pixels = 0;               // frame size the state holds (0 = to be (re)allocated and zeroed at the next adaptive call)
+    int items = 0;                   // pixel slots the order list holds
+    bool have = false;               // samples added since the clear: count describes the accumulation buffer
+    void drop() { pixels = 0; have = false; }
+    void release() {
+      count.release(); moments.release(); error.release(); converged.release();
+      key.release(); keySorted.release(); order.release(); iota.release(); sortTmp.release(); partials.release(); totals.release(); mean.release();
+      items = 0; drop();
+    }
+  } ad;
 };
 
 namespace pt { namespace api {
@@ -183,5 +203,39 @@ int ensure_accum(moptix_context c);
 void fill_view(moptix_context c, SceneView& v);
 moptix_aov_buffers aov_ptrs(moptix_context c);       // api_aov.hip: bound or own, member by member
 void comm_release(moptix_context c);                 // api_comm.hip: destroys the communicator, frees the staging
+
+// ---- the launch plan (api_render.hip): what one batch of launches will run, decided from the context and the batch size alone ----
+struct LaunchPlan {
+  const TraceKernel* kernel;      // kPacketKernel, kQueueKernel, kLeanQueueKernel, or null = the per-lane megakernel (launch_megakernel)
+  int variant;                    // the same as get_option "kernel_variant_used" reports it: 4, 3, 0
+  int nItems, tilesX;             // pixel slots of this rank (local tiles * 64); 8x8 tiles per row of the frame
+  int nBlocks;
+  long long perPass;              // launches per pass, before the out-of-memory halving of the per-sample buffer
+  int slotsInUse, auxDepth, drainBelow, ovfDepth;
+  int tileMajor, unitShift; long long historyUnits;
+  size_t poolBytes, overflowInts, workInts;      // path-slot records; stack overflow area; work counter + watchdog flag + drain list
+};
+// A prepared batch: the plan, the kernel arguments with every buffer the plan asks for in place, and the seeds one pass may take.
+struct RenderLaunch {
+  LaunchPlan p; LaunchArgs a;
+  long long perPass;              // the plan's, after the out-of-memory halving
+  bool counted, fast;
+};
+// What an adaptive pass hands to launch_pass instead of the defaults: its own order list (the first nWork / nSeeds entries are the
+// pixel slots to render) and its own reduction of the per-sample buffer.
+struct PassOverride {
+  const int* order; int nWork;
+  hipError_t (*reduce)(hipStream_t stream, const LaunchArgs& a, void* user); void* user;
+};
+// byPixelSlots: the plan of an adaptive pass -- hand-out by pixel ("tile_major" 3) through a kernel that keeps its paths in slots, whatever
+// the options "tile_major", "kernel_variant" and "analytic_queue" say.
+// prepare_launch: node format, plan, buffers, work header, depth history; r.p.nItems == 0 -> nothing to render.  The seeds are the
+// caller's to upload (c->dSeeds).
+int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelSlots, RenderLaunch& r);
+// One pass of n seeds from dSeeds: [order list sorted] trace kernel (+ drain kernel) and the reduction, between the context's events;
+// asynchronous (moptix_sync times it and reads the watchdog flag).
+int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, const PassOverride* over);
+// (key, id) pairs in descending key order, stable; tmp == nullptr: only tmpBytes, the scratch the sort needs, is set
+hipError_t sort_pairs_desc(void* tmp, size_t& tmpBytes, unsigned int* keys, unsigned int* keysSorted, int* ids, int* idsSorted, size_t n, hipStream_t stream);
 
 }}  // namespace pt::api

@@ -109,7 +109,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release(); c->tp.release();
+  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -140,7 +140,8 @@ int moptix_set_params(moptix_context c, const moptix_params* p) {
   // every frame, inside moptix_render_async as well.  set_option("node_format", 0) asks again explicitly.
   if (!c->haveParams || resized) c->formatDecided = false;
   c->params = *p; c->haveParams = true;
-  if (resized && !c->accumBound) { c->accumPixels = 0; }
+  if (resized && !c->accumBound) { c->accumPixels = 0; c->accumPlain = false; }      // reallocated and zeroed at the next use
+  if (resized) c->ad.release();                                // the adaptive state describes the old frame's accumulation buffer
   if (resized) c->aov.frame_resized();
   if (resized) c->dn.release();                                // the denoiser's scratch and output are reallocated at its next call
   if (resized) c->tp.release();                                // and the temporal history with them
@@ -371,6 +372,7 @@ int moptix_accum_clear(moptix_context c) {
   if (rc != MOPTIX_OK) return rc;
   HIPCHK(c, hipMemsetAsync(accum_ptr(c), 0, sizeof(float) * 3 * c->accumPixels, c->stream), "clear accuBuffer");
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  c->accumPlain = false; c->ad.drop();                         // per-pixel counts of a buffer that is gone: zeroed at the next adaptive call
   return MOPTIX_OK;
 }
 
@@ -389,6 +391,7 @@ int moptix_accum_bind(moptix_context c, void* devPtr) {
   if (!c) return MOPTIX_ERR_INVALID;
   c->accumBound = (float*)devPtr;
   c->accumPixels = 0;
+  c->accumPlain = false; c->ad.drop();                         // another buffer: the adaptive state does not describe it
   return MOPTIX_OK;
 }
 
@@ -403,6 +406,7 @@ int moptix_resolve_rgb8(moptix_context c, float nAccumulation, int clearBuffer, 
   HIPCHK(c, launch_resolve_rgb8(c->stream, accum_ptr(c), (int)c->params.width, (int)c->params.height, nAccumulation, clearBuffer, c->dRgb8.p), "resolve kernel");
   HIPCHK(c, hipMemcpyAsync(dstHost, c->dRgb8.p, bytes, hipMemcpyDeviceToHost, c->stream), "read rgb8");
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  if (clearBuffer) { c->accumPlain = false; c->ad.drop(); }
   return MOPTIX_OK;
 }
 

@@ -126,19 +126,9 @@ int read_stats(moptix_context c, moptix_stats* stats) {
 }
 
 // ---- the launch plan: what one batch of launches will run, decided from the context and the batch size alone --------------------------
-// plan_launch touches neither the device nor the context's buffers; do_render allocates what the plan asks for and launches it.
-struct LaunchPlan {
-  const TraceKernel* kernel;      // kPacketKernel, kQueueKernel, kLeanQueueKernel, or null = the per-lane megakernel (launch_megakernel)
-  int variant;                    // the same as get_option "kernel_variant_used" reports it: 4, 3, 0
-  int nItems, tilesX;             // pixel slots of this rank (local tiles * 64); 8x8 tiles per row of the frame
-  int nBlocks;
-  long long perPass;              // launches per pass, before the out-of-memory halving of the per-sample buffer
-  int slotsInUse, auxDepth, drainBelow, ovfDepth;
-  int tileMajor, unitShift; long long historyUnits;
-  size_t poolBytes, overflowInts, workInts;      // path-slot records; stack overflow area; work counter + watchdog flag + drain list
-};
-
-int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, LaunchPlan& p) {
+// plan_launch touches neither the device nor the context's buffers; prepare_launch allocates what the plan (api_context.h LaunchPlan) asks
+// for and launch_pass launches it.  byPixelSlots: the plan of an adaptive pass (api_adaptive.hip).
+int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool byPixelSlots, LaunchPlan& p) {
   memset(&p, 0, sizeof(p));
   const int tilesX = ((int)c->params.width + 7) / 8, tilesY = ((int)c->params.height + 7) / 8;
   const long long nTiles = (long long)tilesX * tilesY;
@@ -175,7 +165,8 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, Launch
   const bool variantExplicit = c->opt.kernelVariant >= 0;      // "kernel_variant" was set by the caller: no automatic choice
   const int variant = variantExplicit ? c->opt.kernelVariant : 3;
   const bool usePacket = packetOk && (variant == 4 || (!variantExplicit && c->opt.autoPacket != 0 && autoPacket));
-  const bool useQueue = !usePacket && (variant >= 3) && (hasTris || analyticQueue);
+  // (an adaptive pass hands its pixels out through handout_to_item, which the per-lane kernel does not go through: a queue kernel stands in)
+  const bool useQueue = !usePacket && (byPixelSlots || ((variant >= 3) && (hasTris || analyticQueue)));
   p.kernel = usePacket ? &kPacketKernel : !useQueue ? nullptr : hasTris ? &kQueueKernel : &kLeanQueueKernel;      // scenes without triangles: queuekernel_lean.hip
   p.variant = usePacket ? 4 : useQueue ? 3 : 0;
   // no tree to walk (queuekernel_lean.hip): a fourth workgroup per CU instead of path slots and stack entries
@@ -204,7 +195,7 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, Launch
   }
   // [0] work counter, [1] watchdog flag, then (variant 4) the drain list (megakernel.h kDrain*): counters, capacity, threshold, entries
   p.workInts = 2 + drain_list_ints(p.nBlocks, p.drainBelow);
-  p.tileMajor = p.kernel ? c->opt.tileMajor : 0;
+  p.tileMajor = byPixelSlots ? 3 : p.kernel ? c->opt.tileMajor : 0;
   p.unitShift = p.tileMajor == 3 ? 0 : 6;
   p.historyUnits = (localTiles * 64) >> p.unitShift;
   return MOPTIX_OK;
@@ -260,26 +251,20 @@ int evlog_write(moptix_context c, const DevBuf<unsigned long long>& evLog) {    
 }
 #endif
 
-// One batch of launches = [trace kernel: every (pixel, sample) work item -> per-sample buffer]
-// + [ordered reduction: accuBuffer[pixel] += samples in launch order].  Batches larger than the
-// sample-buffer budget (or 2^31 work items) are cut into passes of whole launches.
-int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool counted, bool blocking, moptix_stats* stats) {
-  int rc = check_ready(c);
-  if (rc != MOPTIX_OK) return rc;
-  if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;     // one batch in flight at a time
-  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
-  if (nSeeds == 0) return MOPTIX_OK;
-  if (!c->formatDecided && (rc = choose_node_format(c)) != MOPTIX_OK) return rc;
+}  // namespace
 
-  LaunchArgs a;
+namespace pt { namespace api {
+
+int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelSlots, RenderLaunch& r) {
+  int rc;
+  if (!c->formatDecided && (rc = choose_node_format(c)) != MOPTIX_OK) return rc;
+  LaunchArgs& a = r.a;
+  LaunchPlan& p = r.p;
   memset(&a, 0, sizeof(a));
   fill_view(c, a.scene);
-  LaunchPlan p;
-  if ((rc = plan_launch(c, a.scene, nSeeds, p)) != MOPTIX_OK || p.nItems == 0) return rc;
+  if ((rc = plan_launch(c, a.scene, nSeeds, byPixelSlots, p)) != MOPTIX_OK || p.nItems == 0) return rc;
   c->lastVariant = p.variant;
-  const bool fast = c->opt.fastShading != 0;
+  r.counted = counted; r.fast = c->opt.fastShading != 0;
 
   // ---- what the plan asks for ----
   a.accum = accum_ptr(c);
@@ -306,6 +291,7 @@ int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool count
     (void)hipGetLastError();
     perPass = (perPass + 1) / 2;
   }
+  r.perPass = perPass;
   a.sampleBuf = c->dSampleBuf.p;
   HIPCHK(c, c->dWork.ensure(p.workInts), "alloc work counter");
   {
@@ -325,43 +311,80 @@ int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool count
     HIPCHK(c, hipMemsetAsync(c->dCounters.p + kCntFirstWaveIn, 0xff, sizeof(unsigned long long) * 2, c->stream), "init min counters");      // and kCntItemsRanOut
     a.counters = c->dCounters.p;
   }
+  return MOPTIX_OK;
+}
+
+// rocprim's radix sort of (key, id) pairs, descending and stable, instantiated in this file alone: the depth history's order list
+// (start_tile_history, launch_pass) and the adaptive passes' (api_adaptive.hip) are the same template.
+hipError_t sort_pairs_desc(void* tmp, size_t& tmpBytes, unsigned int* keys, unsigned int* keysSorted, int* ids, int* idsSorted, size_t n, hipStream_t stream) {
+  return rocprim::radix_sort_pairs_desc(tmp, tmpBytes, keys, keysSorted, ids, idsSorted, n, 0, 32, stream);
+}
+
+int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, const PassOverride* over) {
+  LaunchArgs& a = r.a;
+  const LaunchPlan& p = r.p;
+  a.seeds = dSeeds; a.nSeeds = n; a.nWork = over ? over->nWork : n * a.nItems;
+  HIPCHK(c, hipMemsetAsync(c->dWork.p, 0, (2 + kDrainCap) * sizeof(int), c->stream), "zero work counter");      // counters only: capacity and threshold stay
+  if (over) a.tileOrder = over->order;
+  else if (a.tileMajor && a.tileCost) {
+    // tiles in descending order of the deepest path seen so far (stable: ties stay in raster order)
+    auto& t = c->tiles;
+    size_t tmpBytes = t.sortTmp.n;
+    HIPCHK(c, rocprim::radix_sort_pairs_desc(t.sortTmp.p, tmpBytes, t.cost.p, t.costSorted.p, t.iota.p, t.order.p, (size_t)p.historyUnits, 0, 32, c->stream), "sort tiles");
+  }
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
+  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast), p.kernel->launchWhat);
+  else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
+  if (p.drainBelow > 0) HIPCHK(c, launch_drainkernel(c->stream, a, c->numCUs, r.counted, r.fast), "launch drain kernel");
+  // Since the drain kernel came, a packet launch WITHOUT it ("drain_below" 0) has been followed by the per-lane megakernel: it finds the work counter
+  // used up and leaves at once.  Nothing needs that launch; it stays until a change of its own takes it out, so that the launches are what they were.
+  else if (p.kernel == &kPacketKernel) HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream), "event");
+  if (over) HIPCHK(c, over->reduce(c->stream, a, over->user), "launch adaptive reduction");
+  else HIPCHK(c, launch_reduce_samples(c->stream, a), "launch sample reduction");
+  HIPCHK(c, hipEventRecord(c->ev2, c->stream), "event");
+  c->asyncPending = true;
+  return MOPTIX_OK;
+}
+
+}}  // namespace pt::api
+
+namespace {
+
+// One batch of launches = [trace kernel: every (pixel, sample) work item -> per-sample buffer]
+// + [ordered reduction: accuBuffer[pixel] += samples in launch order].  Batches larger than the
+// sample-buffer budget (or 2^31 work items) are cut into passes of whole launches.
+int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool counted, bool blocking, moptix_stats* stats) {
+  int rc = check_ready(c);
+  if (rc != MOPTIX_OK) return rc;
+  if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
+  if (c->ad.have) return fail(c, MOPTIX_ERR_STATE, "the accumulation buffer holds an adaptive render (per-pixel sample counts): moptix_adaptive_clear or moptix_accum_clear first");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;     // one batch in flight at a time
+  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  if (nSeeds == 0) return MOPTIX_OK;
+  RenderLaunch r;
+  if ((rc = prepare_launch(c, nSeeds, counted, false, r)) != MOPTIX_OK || r.p.nItems == 0) return rc;
 #ifdef PT_EVLOG
   DevBuf<unsigned long long> evLog;
-  if ((rc = evlog_begin(c, evLog, a)) != MOPTIX_OK) return rc;
+  if ((rc = evlog_begin(c, evLog, r.a)) != MOPTIX_OK) return rc;
 #endif
   c->seedStaging.assign(seeds, seeds + nSeeds);   // lives in the context: the copy below may still be in flight when an async render returns
   HIPCHK(c, c->dSeeds.upload(c->seedStaging, c->stream), "upload seeds");
+  c->accumPlain = true;
 
   // ---- the launches ----
-  for (long long first = 0; first < nSeeds; first += perPass) {
-    const int n = (int)std::min(perPass, (long long)nSeeds - first);
-    a.seeds = c->dSeeds.p + first; a.nSeeds = n; a.nWork = n * a.nItems;
-    HIPCHK(c, hipMemsetAsync(c->dWork.p, 0, (2 + kDrainCap) * sizeof(int), c->stream), "zero work counter");      // counters only: capacity and threshold stay
-    if (a.tileMajor && a.tileCost) {
-      // tiles in descending order of the deepest path seen so far (stable: ties stay in raster order)
-      auto& t = c->tiles;
-      size_t tmpBytes = t.sortTmp.n;
-      HIPCHK(c, rocprim::radix_sort_pairs_desc(t.sortTmp.p, tmpBytes, t.cost.p, t.costSorted.p, t.iota.p, t.order.p, (size_t)p.historyUnits, 0, 32, c->stream), "sort tiles");
-    }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
-    if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, counted, fast), p.kernel->launchWhat);
-    else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, counted), "launch megakernel");
-    if (p.drainBelow > 0) HIPCHK(c, launch_drainkernel(c->stream, a, c->numCUs, counted, fast), "launch drain kernel");
-    // Since the drain kernel came, a packet launch WITHOUT it ("drain_below" 0) has been followed by the per-lane megakernel: it finds the work counter
-    // used up and leaves at once.  Nothing needs that launch; it stays until a change of its own takes it out, so that the launches are what they were.
-    else if (p.kernel == &kPacketKernel) HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, counted), "launch megakernel");
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream), "event");
-    HIPCHK(c, launch_reduce_samples(c->stream, a), "launch sample reduction");
-    HIPCHK(c, hipEventRecord(c->ev2, c->stream), "event");
-    c->asyncPending = true;
-    const bool last = first + perPass >= nSeeds;
+  for (long long first = 0; first < nSeeds; first += r.perPass) {
+    const int n = (int)std::min(r.perPass, (long long)nSeeds - first);
+    if ((rc = launch_pass(c, r, c->dSeeds.p + first, n, nullptr)) != MOPTIX_OK) return rc;
+    const bool last = first + r.perPass >= nSeeds;
     if (!last || blocking) { if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc; }
   }
 #ifdef PT_EVLOG
   if (blocking && !counted && getenv("MOPTIX_EVLOG") && (rc = evlog_write(c, evLog)) != MOPTIX_OK) return rc;
   evLog.release();
 #endif
-  if (blocking && a.tileCost && getenv("MOPTIX_DEBUG") && (rc = report_tile_history(c)) != MOPTIX_OK) return rc;
+  if (blocking && r.a.tileCost && getenv("MOPTIX_DEBUG") && (rc = report_tile_history(c)) != MOPTIX_OK) return rc;
   if (blocking && counted && stats) return read_stats(c, stats);
   return MOPTIX_OK;
 }

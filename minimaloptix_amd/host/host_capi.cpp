@@ -192,3 +192,25 @@ int mohost_render_scene(int device, int sceneId, const char* baseFolder, uint32_
     return MOPTIX_OK;
   } catch (const std::exception& e) { g_err = e.what(); return MOPTIX_ERR_INVALID; }
 }
+
+int mohost_render_scene_adaptive(int device, int sceneId, const char* baseFolder, uint32_t width, uint32_t height,
+                                 uint32_t nSeeds, uint32_t baseSeed, const moptix_adaptive_params* params,
+                                 uint8_t* canvasRGB8, uint32_t* count, float* error, moptix_adaptive_stats* stats) {
+  try {
+    MinimalOptiX app(device);
+    app.verbose = false;
+    app.fixedWidth = width; app.fixedHeight = height; app.nSuperSampling = nSeeds;
+    app.baseSeed = baseSeed; app.sceneId = (MinimalOptiX::SceneId)sceneId;
+    if (baseFolder) app.baseSceneFolder = baseFolder;
+    app.adaptive = true;
+    if (params) app.adaptiveParams = *params;
+    else (void)moptix_adaptive_defaults(&app.adaptiveParams);
+    app.setupContext();
+    app.renderScene(false, "");
+    if (canvasRGB8) memcpy(canvasRGB8, app.canvas.data(), app.canvas.size());
+    if (count) memcpy(count, app.adaptiveCount.data(), sizeof(uint32_t) * app.adaptiveCount.size());
+    if (error) memcpy(error, app.adaptiveError.data(), sizeof(float) * app.adaptiveError.size());
+    if (stats) *stats = app.lastAdaptive;
+    return MOPTIX_OK;
+  } catch (const std::exception& e) { g_err = e.what(); return MOPTIX_ERR_INVALID; }
+}

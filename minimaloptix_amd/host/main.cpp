@@ -26,6 +26,11 @@ static void usage() {
           "                              (spheres move, camera orbits, --spp new seeds each) saved as PREFIX_videoI.png; with --denoise-temporal\n"
           "                              also PREFIX_videoI_denoised.pfm / .png: the step through the denoiser with temporal accumulation\n"
           "                              (default parameters, --denoise-iterations L)\n"
+          "                     [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N]]  the --spp seeds rendered adaptively: after N\n"
+          "                              (default 16) seeds for every pixel, passes of up to N (default 64) seeds for the pixels whose relative\n"
+          "                              standard error (3x3 maximum) is above THRESHOLD; the image is each pixel's own mean; prints the stats; with\n"
+          "                              --aov also PREFIX_count.pfm and PREFIX_error.pfm; with --denoise the mean is what is denoised.  One rank, no\n"
+          "                              --autosave, no --video-frames\n"
           "       multi-GPU (one process per GPU, tile split + RCCL gather to rank 0, which writes the image):\n"
           "                     [--spawn N]  start N ranks of this program, rank r on device r, and wait for them\n"
           "                     [--spawn-same-device]  ... every rank on --device (a one-GPU box; needs a transport that accepts it,\n"
@@ -38,6 +43,8 @@ int main(int argc, char** argv) {
   unsigned spp = 32, width = 1920, height = 1080, seed = 0;
   int device = 0; bool autosave = false, randomSeeds = false, strict = false, aov = false, denoise = false, denoiseTemporal = false;
   int denoiseIterations = 5, videoFrames = 0;
+  bool adaptive = false; moptix_adaptive_params adaptiveParams;
+  moptix_adaptive_defaults(&adaptiveParams);                    // pure host: no device is touched
   int rank = 0, ranks = 1, spawn = 0, spawnTimeout = 600; bool spawnSame = false; std::string commFile;
   for (int i = 1; i < argc; i++) {
     auto need = [&](const char* n) { if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", n); exit(2); } return argv[++i]; };
@@ -63,8 +70,15 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--denoise")) denoise = true;
     else if (!strcmp(argv[i], "--video-frames")) videoFrames = atoi(need("--video-frames"));
     else if (!strcmp(argv[i], "--denoise-temporal")) denoiseTemporal = true;
+    else if (!strcmp(argv[i], "--adaptive")) { adaptive = true; adaptiveParams.threshold = strtof(need("--adaptive"), nullptr); }
+    else if (!strcmp(argv[i], "--adaptive-min")) adaptiveParams.minSamples = atoi(need("--adaptive-min"));
+    else if (!strcmp(argv[i], "--adaptive-batch")) adaptiveParams.batch = atoi(need("--adaptive-batch"));
     else if (!strcmp(argv[i], "--denoise-iterations")) denoiseIterations = atoi(need("--denoise-iterations"));
     else { usage(); return 2; }
+  }
+  if (adaptive && (spawn > 0 || ranks > 1 || !commFile.empty() || videoFrames > 0 || autosave)) {
+    fprintf(stderr, "moptix_render: --adaptive is for one rank and one image (not with --spawn, --ranks, --comm-file, --video-frames, --autosave)\n");
+    return 2;
   }
   if (videoFrames < 0) { fprintf(stderr, "moptix_render: --video-frames must be >= 0\n"); return 2; }
   if (denoiseTemporal && videoFrames == 0) { fprintf(stderr, "moptix_render: --denoise-temporal needs --video-frames N\n"); return 2; }
@@ -122,6 +136,7 @@ int main(int argc, char** argv) {
     app.baseSeed = seed; app.reproducibleSeeds = !randomSeeds; app.skipMissingMeshes = !strict;
     app.baseSceneFolder = scenes; app.outputDir = outdir;
     app.denoise = denoise; app.denoiseIterations = denoiseIterations;
+    app.adaptive = adaptive; app.adaptiveParams = adaptiveParams;
     app.setupContext();
     if (scene == "spheres") app.sceneId = MinimalOptiX::SCENE_SPHERES;
     else if (scene == "coffee") app.sceneId = MinimalOptiX::SCENE_COFFEE;
@@ -142,6 +157,7 @@ int main(int argc, char** argv) {
     app.renderScene(autosave, prefix);
     if (!autosave && rank == 0) app.saveCurrentFrame(false, prefix);
     if (aov && rank == 0) app.saveAovs(prefix);               // whole frame, on rank 0's context alone: no collective
+    if (aov && adaptive) app.saveAdaptive(prefix);
     app.denoiseTemporal = denoiseTemporal; app.videoPrefix = prefix;
     for (int i = 0; i < videoFrames; i++) {
       app.updateVideo();

@@ -9,6 +9,8 @@
 #include <random>
 #include <stdexcept>
 
+#include <hip/hip_runtime_api.h>      // hipMalloc / hipFree of the adaptive path's mean buffer: nothing else of HIP is used on the host
+
 #include "../csrc/pt_rng.h"
 #include "image_io.h"
 
@@ -109,6 +111,7 @@ void MinimalOptiX::renderScene(bool autoSave, std::string fileNamePrefix) {
   setupScene();
   check(moptix_validate(context), "validate");                 // :542
   const bool multi = nRanks > 1 || !commIdFile.empty();
+  if (adaptive && (multi || autoSave)) throw std::runtime_error("adaptive sampling is for one rank and one image (no tile split, no progressive snapshots)");
   if (multi) { setupCommunicator(); autoSave = false; }         // progressive snapshots would need a gather each: one-GPU only
   moptix_get_accel_info(context, &lastAccel);
   if (canvas.size() != (size_t)fixedWidth * fixedHeight * 3) canvas.assign((size_t)fixedWidth * fixedHeight * 3, 0);
@@ -116,6 +119,7 @@ void MinimalOptiX::renderScene(bool autoSave, std::string fileNamePrefix) {
   std::vector<int32_t> seeds(nSuperSampling);
   for (uint i = 0; i < nSuperSampling; ++i) seeds[i] = randSeed();   // :545 one seed per launch
   lastSeeds = seeds;
+  if (adaptive) { renderAdaptive(fileNamePrefix); return; }
   uint checkpoint = 1;
   uint done = 0;
   while (done < nSuperSampling) {
@@ -137,6 +141,53 @@ void MinimalOptiX::renderScene(bool autoSave, std::string fileNamePrefix) {
   uint64_t n = 0;
   moptix_kernel_time(context, &lastRenderMs, &n, 0);
   if (verbose) fprintf(stderr, "vertices: %zu faces: %zu\n", nVertices, nFaces);   // :559
+}
+
+// renderScene()'s launches and resolve when `adaptive` is set
+void MinimalOptiX::renderAdaptive(std::string fileNamePrefix) {
+  check(moptix_adaptive_clear(context), "adaptive clear");
+  check(moptix_render_adaptive(context, lastSeeds.data(), (int32_t)lastSeeds.size(), &adaptiveParams, &lastAdaptive), "adaptive render");
+  const size_t px = (size_t)fixedWidth * fixedHeight;
+  adaptiveCount.assign(px, 0u); adaptiveError.assign(px, 0.f);
+  moptix_adaptive_buffers b = { adaptiveCount.data(), nullptr, adaptiveError.data(), nullptr };
+  check(moptix_adaptive_read(context, &b), "read adaptive state");
+  check(moptix_adaptive_resolve_rgb8(context, canvas.data()), "adaptive resolve");
+  if (denoise) {
+    // the per-pixel mean as the accumulator of a denoise call that divides by 1; binding drops the adaptive state, which is read by now
+    float* mean = nullptr;
+    if (hipMalloc((void**)&mean, sizeof(float) * 3 * px) != hipSuccess) throw std::runtime_error("cannot allocate the mean buffer");
+    try {
+      check(moptix_adaptive_mean_device(context, mean), "adaptive mean");
+      check(moptix_accum_bind(context, mean), "bind mean");
+      saveDenoised(fileNamePrefix, false, 1.0f);
+      check(moptix_accum_bind(context, nullptr), "unbind mean");
+    } catch (...) { moptix_accum_bind(context, nullptr); (void)hipFree(mean); throw; }
+    (void)hipFree(mean);
+  }
+  check(moptix_accum_clear(context), "clear");                  // as updateContent(n, true) leaves it
+  uint64_t n = 0;
+  moptix_kernel_time(context, &lastRenderMs, &n, 0);
+  if (verbose) {
+    const moptix_adaptive_stats& s = lastAdaptive;
+    fprintf(stderr, "adaptive: threshold %g, %d + n x %d seeds: %llu passes, %llu of %llu samples traced (%.1f %%), %llu pixels active and %llu converged after the last pass, %u to %u samples per pixel\n",
+            (double)adaptiveParams.threshold, adaptiveParams.minSamples, adaptiveParams.batch, (unsigned long long)s.passes, (unsigned long long)s.samplesTraced,
+            (unsigned long long)s.samplesUniform, s.samplesUniform ? 100.0 * (double)s.samplesTraced / (double)s.samplesUniform : 0.0,
+            (unsigned long long)s.activePixelsLast, (unsigned long long)s.convergedPixels, s.minCount, s.maxCount);
+    fprintf(stderr, "vertices: %zu faces: %zu\n", nVertices, nFaces);
+  }
+}
+
+void MinimalOptiX::saveAdaptive(std::string fileNamePrefix) {
+  const size_t px = (size_t)fixedWidth * fixedHeight;
+  if (adaptiveCount.size() != px || adaptiveError.size() != px) throw std::runtime_error("no adaptive render to save");
+  std::vector<float> img(3 * px);
+  const std::string base = outputDir + "/" + (fileNamePrefix.empty() ? std::string("frame") : fileNamePrefix);
+  for (int which = 0; which < 2; which++) {
+    for (size_t i = 0; i < px; i++) img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = which == 0 ? (float)adaptiveCount[i] : adaptiveError[i];
+    const std::string name = base + (which == 0 ? "_count.pfm" : "_error.pfm");
+    if (!writePFM(name, img.data(), fixedWidth, fixedHeight)) throw std::runtime_error("cannot write " + name);
+    if (verbose) fprintf(stderr, "Adaptive-sampling image saved to %s\n", name.c_str());
+  }
 }
 
 // MinimalOptiX.cpp:43-66 (normalise, clamp, flip rows, optionally clear) -- done on the device
@@ -171,7 +222,8 @@ void MinimalOptiX::saveAovs(std::string fileNamePrefix) {
   }
 }
 
-void MinimalOptiX::saveDenoised(std::string fileNamePrefix, bool temporal) {
+void MinimalOptiX::saveDenoised(std::string fileNamePrefix, bool temporal, float nAccumulation) {
+  if (!(nAccumulation > 0.f)) nAccumulation = (float)nSuperSampling;
   check(moptix_aov_clear(context), "AOV clear");
   check(moptix_render_aovs(context, lastSeeds.data(), (int32_t)lastSeeds.size()), "render AOVs");
   moptix_denoise_params p;
@@ -180,9 +232,9 @@ void MinimalOptiX::saveDenoised(std::string fileNamePrefix, bool temporal) {
   if (temporal) {
     moptix_temporal_params t;
     check(moptix_temporal_defaults(&t), "temporal defaults");
-    check(moptix_denoise_temporal(context, &p, &t, (float)nSuperSampling), "temporal denoise");
+    check(moptix_denoise_temporal(context, &p, &t, nAccumulation), "temporal denoise");
   } else {
-    check(moptix_denoise(context, &p, (float)nSuperSampling), "denoise");
+    check(moptix_denoise(context, &p, nAccumulation), "denoise");
   }
   const size_t px = (size_t)fixedWidth * fixedHeight;
   std::vector<float> out(3 * px);

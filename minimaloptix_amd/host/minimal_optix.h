@@ -93,7 +93,7 @@ public:
   // u8(clamp(v, 0, 1) * 255) as updateContent) in outputDir
   bool denoise = false;
   int denoiseIterations = 5;
-  void saveDenoised(std::string fileNamePrefix, bool temporal = false);
+  void saveDenoised(std::string fileNamePrefix, bool temporal = false, float nAccumulation = 0.f);      // 0: nSuperSampling
   // temporal accumulation over a video (new; include/moptix.h): with denoiseTemporal set, every updateVideo() step renders the AOVs of
   // its seeds on rank 0, calls moptix_denoise_temporal (defaults, denoiseIterations) before its resolve clears accuBuffer, and writes
   // <videoPrefix>_video<step>_denoised.pfm / .png through saveDenoised.  The first step is the history's first frame.
@@ -101,7 +101,20 @@ public:
   std::string videoPrefix = "frame";
   int videoStep = 0;                  // updateVideo() steps taken
 
+  // adaptive sampling (new; include/moptix.h): with adaptive set, renderScene() renders its nSuperSampling seeds through
+  // moptix_render_adaptive with adaptiveParams (one rank, no progressive snapshots: an error otherwise), fills the canvas through the
+  // count-aware resolve, keeps the stats and the count / error images, and leaves the accumulator cleared as the plain path does.
+  // With denoise set the per-pixel mean goes into a device buffer of this object that is bound as the accumulator for the denoise
+  // call with nAccumulation = 1 (the denoiser divides by one number for the whole frame).  saveAdaptive writes PREFIX_count.pfm and
+  // PREFIX_error.pfm (rows bottom-up, the value in three equal channels) in outputDir.
+  bool adaptive = false;
+  moptix_adaptive_params adaptiveParams{ 0.03f, 16, 64 };
+  moptix_adaptive_stats lastAdaptive{};
+  std::vector<uint32_t> adaptiveCount; std::vector<float> adaptiveError;      // of the last adaptive renderScene()
+  void saveAdaptive(std::string fileNamePrefix);
+
 private:
+  void renderAdaptive(std::string fileNamePrefix);
   uint launchCounter = 0;
   void check(int rc, const char* what);
 };
