@@ -8,8 +8,8 @@
 // seed's row of the per-sample buffer, so the loads stay coalesced whatever the active set looks like; a slot whose pixel is
 // converged (it was not handed out in this pass) or outside the frame is skipped.  One read of the buffer serves the colour sum and
 // the luminance moments.
-// k_ad_mask: the denoiser's mapping, a lane per pixel, a 256-thread workgroup covers 16x16 pixels as four 8x8 tiles, one per wave -- the
-// wave's tile is a tile of the trace kernels' slot numbering, so lane l of the wave owns slot tile * 64 + l and the keys are written
+// k_ad_mask: the denoiser's mapping (image_tile.h), a lane per pixel, a 256-thread workgroup covers 16x16 pixels as four 8x8 tiles, one per wave --
+// the wave's tile is a tile of the trace kernels' slot numbering, so lane l of the wave owns slot tile * 64 + l and the keys are written
 // as one 256-byte row per wave.  The 3x3 window's errors are recomputed from count / moments (nine 12-byte loads per pixel, served
 // by the L1/L2: a wave's window is a 10x10-pixel neighbourhood) instead of from an error buffer written by a kernel of its own: that
 // would add a launch and a 4-byte round trip per pixel and pass to save a square root and two divisions per tap, on 2 M pixels.
@@ -18,12 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include "adaptivekernel.h"
+#include "image_tile.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = 256;
+constexpr int kBlockThreads = kImageBlockThreads;
 
 __global__ void __launch_bounds__(kBlockThreads) k_ad_reduce(const AdaptiveArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,9 +51,8 @@ __global__ void __launch_bounds__(kBlockThreads) k_ad_reduce(const AdaptiveArgs 
 
 __global__ void __launch_bounds__(kBlockThreads) k_ad_mask(const AdaptiveArgs a, int decide) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tx = blockIdx.x * 2 + (wave & 1), ty = blockIdx.y * 2 + (wave >> 1);
-  const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-  const bool inside = x < a.k.width && y < a.k.height;      // no early return: the whole wave takes part in the reduction
+  int x, y, tx, ty;
+  const bool inside = image_pixel(a.k.width, a.k.height, x, y, tx, ty);      // no early return: the whole wave takes part in the reduction
   bool active = false, conv = false;
   unsigned int cmin = 0xffffffffu, cmax = 0u;
   if (inside) {
@@ -123,7 +123,7 @@ hipError_t launch_adaptive_reduce(hipStream_t stream, const AdaptiveArgs& a) {
 }
 
 hipError_t launch_adaptive_mask(hipStream_t stream, const AdaptiveArgs& a, int decide) {
-  const dim3 grid((a.k.width + 15) / 16, (a.k.height + 15) / 16);
+  const dim3 grid = image_grid(a.k.width, a.k.height);
   k_ad_mask<<<grid, kBlockThreads, 0, stream>>>(a, decide);
   k_ad_fold<<<1, kBlockThreads, 0, stream>>>(a.partials, (int)(grid.x * grid.y), a.totals);
   return hipGetLastError();

@@ -21,7 +21,7 @@ void fill_args(moptix_context c, AdaptiveArgs& a) {
   a.tilesX = (a.k.width + 7) / 8; a.nItems = a.tilesX * ((a.k.height + 7) / 8) * 64;
   a.accum = accum_ptr(c);
   a.count = s.count.p; a.moments = s.moments.p; a.error = s.error.p; a.converged = s.converged.p;
-  a.key = s.key.p; a.partials = reinterpret_cast<uint4*>(s.partials.p); a.totals = reinterpret_cast<AdaptiveTotals*>(s.totals.p);
+  a.key = s.order.keys.p; a.partials = reinterpret_cast<uint4*>(s.partials.p); a.totals = reinterpret_cast<AdaptiveTotals*>(s.totals.p);
 }
 
 // The state at this frame size: allocated and zeroed when there is none (first call, or dropped since).
@@ -45,32 +45,12 @@ int ensure_state(moptix_context c) {
   return MOPTIX_OK;
 }
 
-// The order list's buffers for nItems pixel slots; the keys of the padding slots stay at the 0 they are cleared to here.
-int ensure_order(moptix_context c, int nItems) {
-  moptix_context_t::Adaptive& s = c->ad;
-  if (s.items == nItems) return MOPTIX_OK;
-  HIPCHK(c, s.key.ensure((size_t)nItems), "alloc adaptive order");
-  HIPCHK(c, s.keySorted.ensure((size_t)nItems), "alloc adaptive order");
-  HIPCHK(c, s.order.ensure((size_t)nItems), "alloc adaptive order");
-  std::vector<int> iota((size_t)nItems);
-  for (size_t i = 0; i < iota.size(); i++) iota[i] = (int)i;
-  HIPCHK(c, s.iota.upload(iota, c->stream), "upload slot ids");
-  HIPCHK(c, hipMemsetAsync(s.key.p, 0, sizeof(unsigned int) * (size_t)nItems, c->stream), "zero adaptive keys");
-  size_t tmpBytes = 0;
-  HIPCHK(c, sort_pairs_desc(nullptr, tmpBytes, s.key.p, s.keySorted.p, s.iota.p, s.order.p, (size_t)nItems, c->stream), "size adaptive sort");
-  HIPCHK(c, s.sortTmp.ensure(tmpBytes), "alloc sort scratch");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync adaptive order");    // iota staging dies here
-  s.items = nItems;
-  return MOPTIX_OK;
-}
-
 // Mask kernel (decide: pixels that need no more samples converge), then the order list: active slots first, deepest paths of earlier
 // launches first, ties in slot order (the sort is stable).  Blocking: the host needs nActive for the next pass's work count.
 int mask_and_order(moptix_context c, AdaptiveArgs& a, int decide, AdaptiveTotals& t) {
   moptix_context_t::Adaptive& s = c->ad;
   HIPCHK(c, launch_adaptive_mask(c->stream, a, decide), "launch adaptive mask");
-  size_t tmpBytes = s.sortTmp.n;
-  HIPCHK(c, sort_pairs_desc(s.sortTmp.p, tmpBytes, s.key.p, s.keySorted.p, s.iota.p, s.order.p, (size_t)a.nItems, c->stream), "sort adaptive order");
+  HIPCHK(c, s.order.sort(c->stream), "sort adaptive order");
   HIPCHK(c, hipMemcpyAsync(&t, s.totals.p, sizeof(t), hipMemcpyDeviceToHost, c->stream), "read adaptive totals");
   HIPCHK(c, hipStreamSynchronize(c->stream), "adaptive mask");
   return MOPTIX_OK;
@@ -88,10 +68,7 @@ int check_state(moptix_context c) {
   if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
   if (c->ad.pixels == 0 || c->ad.pixels != (size_t)c->params.width * c->params.height)
     return fail(c, MOPTIX_ERR_STATE, "no adaptive state: moptix_render_adaptive or moptix_adaptive_clear first");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc;
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
-  return ensure_accum(c);
+  return begin_call(c, true);
 }
 
 }  // namespace
@@ -114,9 +91,7 @@ int moptix_render_adaptive(moptix_context c, const int32_t* seeds, int32_t nSeed
   if (c->rank != 0 || c->nRanks != 1)
     return fail(c, MOPTIX_ERR_STATE, "adaptive sampling renders the whole frame: a pixel's 3x3 window crosses into other ranks' tiles (moptix_set_partition(0, 1))");
   if (c->accumPlain) return fail(c, MOPTIX_ERR_STATE, "the accumulation buffer holds plain renders without per-pixel sample counts: moptix_adaptive_clear first");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
-  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  if ((rc = begin_call(c, true)) != MOPTIX_OK) return rc;
   if ((rc = ensure_state(c)) != MOPTIX_OK) return rc;
   moptix_context_t::Adaptive& s = c->ad;
 
@@ -130,8 +105,8 @@ int moptix_render_adaptive(moptix_context c, const int32_t* seeds, int32_t nSeed
     RenderLaunch r;
     if ((rc = prepare_launch(c, nSeeds, false, true, r)) != MOPTIX_OK) return rc;
     if (r.p.nItems != a.nItems) return fail(c, MOPTIX_ERR_STATE, "launch plan and adaptive state disagree on the frame's pixel slots");
-    if ((rc = ensure_order(c, a.nItems)) != MOPTIX_OK) return rc;
-    a.key = s.key.p;
+    HIPCHK(c, s.order.ensure(a.nItems, c->stream), "alloc adaptive order");      // the padding slots' keys stay at the 0 they are cleared to here
+    a.key = s.order.keys.p;
     a.tileCost = r.a.tileCost;
     c->seedStaging.assign(seeds, seeds + nSeeds);
     HIPCHK(c, c->dSeeds.upload(c->seedStaging, c->stream), "upload seeds");
@@ -141,7 +116,7 @@ int moptix_render_adaptive(moptix_context c, const int32_t* seeds, int32_t nSeed
       const int n = ad_pass_seeds(s.have, p->minSamples, p->batch, nSeeds - first);
       for (long long sub = 0; sub < n; sub += r.perPass) {      // the per-sample buffer's budget cuts a pass, as it cuts moptix_render's
         const int m = (int)std::min<long long>(r.perPass, n - sub);
-        PassOverride over = { s.order.p, (int)t.active * m, reduce_pass, &a };
+        PassOverride over = { s.order.order.p, (int)t.active * m, reduce_pass, &a };
         s.have = true;                                     // from here on the counts may describe samples in the accumulation buffer
         if ((rc = launch_pass(c, r, c->dSeeds.p + first + sub, m, &over)) != MOPTIX_OK) return rc;
         if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
@@ -152,8 +127,8 @@ int moptix_render_adaptive(moptix_context c, const int32_t* seeds, int32_t nSeed
     }
   }
   if (nSeeds == 0) {      // nothing to render: the totals of the state as it is (no launch plan: the depth history is not read)
-    if ((rc = ensure_order(c, a.nItems)) != MOPTIX_OK) return rc;
-    a.key = s.key.p;
+    HIPCHK(c, s.order.ensure(a.nItems, c->stream), "alloc adaptive order");      // the padding slots' keys stay at the 0 they are cleared to here
+    a.key = s.order.keys.p;
     if ((rc = mask_and_order(c, a, 0, t)) != MOPTIX_OK) return rc;
   }
   if (out) {
@@ -177,13 +152,9 @@ int moptix_adaptive_read(moptix_context c, const moptix_adaptive_buffers* d) {
   if (!c || !d) return fail(c, MOPTIX_ERR_INVALID, "null argument");
   int rc = check_state(c);
   if (rc != MOPTIX_OK) return rc;
-  const size_t px = c->ad.pixels;
-  if (d->count) HIPCHK(c, hipMemcpyAsync(d->count, c->ad.count.p, sizeof(uint32_t) * px, hipMemcpyDeviceToHost, c->stream), "read adaptive counts");
-  if (d->moments) HIPCHK(c, hipMemcpyAsync(d->moments, c->ad.moments.p, sizeof(float) * 2 * px, hipMemcpyDeviceToHost, c->stream), "read adaptive moments");
-  if (d->error) HIPCHK(c, hipMemcpyAsync(d->error, c->ad.error.p, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read adaptive errors");
-  if (d->converged) HIPCHK(c, hipMemcpyAsync(d->converged, c->ad.converged.p, px, hipMemcpyDeviceToHost, c->stream), "read adaptive flags");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
-  return MOPTIX_OK;
+  const moptix_context_t::Adaptive& s = c->ad;
+  return read_back(c, { { d->count, s.count.p, sizeof(uint32_t) * s.pixels }, { d->moments, s.moments.p, sizeof(float) * 2 * s.pixels },
+                        { d->error, s.error.p, sizeof(float) * s.pixels }, { d->converged, s.converged.p, s.pixels } }, "read adaptive state");
 }
 
 int moptix_adaptive_mean_device(moptix_context c, float* dstDevice) {
@@ -206,9 +177,7 @@ int moptix_adaptive_mean(moptix_context c, float* dstHost) {
   AdaptiveArgs a;
   fill_args(c, a);
   HIPCHK(c, launch_adaptive_mean(c->stream, a, c->ad.mean.p), "launch adaptive mean");
-  HIPCHK(c, hipMemcpyAsync(dstHost, c->ad.mean.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read adaptive mean");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "adaptive mean");
-  return MOPTIX_OK;
+  return read_back(c, { { dstHost, c->ad.mean.p, sizeof(float) * 3 * px } }, "read adaptive mean");
 }
 
 int moptix_adaptive_resolve_rgb8(moptix_context c, uint8_t* dstHost) {
@@ -220,9 +189,7 @@ int moptix_adaptive_resolve_rgb8(moptix_context c, uint8_t* dstHost) {
   AdaptiveArgs a;
   fill_args(c, a);
   HIPCHK(c, launch_adaptive_resolve_rgb8(c->stream, a, c->dRgb8.p), "adaptive resolve kernel");
-  HIPCHK(c, hipMemcpyAsync(dstHost, c->dRgb8.p, bytes, hipMemcpyDeviceToHost, c->stream), "read rgb8");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
-  return MOPTIX_OK;
+  return read_back(c, { { dstHost, c->dRgb8.p, bytes } }, "read rgb8");
 }
 
 }  // extern "C"

@@ -50,9 +50,7 @@ int moptix_render_aovs(moptix_context c, const int32_t* seeds, int32_t nSeeds) {
   int rc = check_ready(c);
   if (rc != MOPTIX_OK) return rc;
   if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;     // a beauty batch still in flight finishes (and is timed) first
-  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  if ((rc = begin_call(c, false)) != MOPTIX_OK || (rc = ensure_aov(c)) != MOPTIX_OK) return rc;
   if (nSeeds == 0) { HIPCHK(c, hipStreamSynchronize(c->stream), "sync"); return MOPTIX_OK; }
   if ((long long)((c->params.width + 7) / 8) * ((c->params.height + 7) / 8) > 0x7fffffffLL) return fail(c, MOPTIX_ERR_LIMIT, "frame too large");
   AovArgs a;
@@ -81,10 +79,8 @@ int moptix_render_aovs(moptix_context c, const int32_t* seeds, int32_t nSeeds) {
 int moptix_aov_clear(moptix_context c) {
   if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
   if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   int rc;
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
-  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  if ((rc = begin_call(c, false)) != MOPTIX_OK || (rc = ensure_aov(c)) != MOPTIX_OK) return rc;
   if ((rc = aov_zero(c)) != MOPTIX_OK) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
   return MOPTIX_OK;
@@ -99,20 +95,13 @@ int moptix_aov_samples(moptix_context c, uint64_t* out) {
 int moptix_aov_read(moptix_context c, const moptix_aov_buffers* dst) {
   if (!c || !dst) return fail(c, MOPTIX_ERR_INVALID, "null argument");
   if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   int rc;
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
-  if ((rc = ensure_aov(c)) != MOPTIX_OK) return rc;
+  if ((rc = begin_call(c, false)) != MOPTIX_OK || (rc = ensure_aov(c)) != MOPTIX_OK) return rc;
   const size_t px = c->aov.pixels;
   const moptix_aov_buffers p = aov_ptrs(c);
-  if (dst->albedo) HIPCHK(c, hipMemcpyAsync(dst->albedo, p.albedo, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  if (dst->normal) HIPCHK(c, hipMemcpyAsync(dst->normal, p.normal, sizeof(float) * 3 * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  if (dst->depth) HIPCHK(c, hipMemcpyAsync(dst->depth, p.depth, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  if (dst->hits) HIPCHK(c, hipMemcpyAsync(dst->hits, p.hits, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  if (dst->primId) HIPCHK(c, hipMemcpyAsync(dst->primId, p.primId, sizeof(int) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  if (dst->matId) HIPCHK(c, hipMemcpyAsync(dst->matId, p.matId, sizeof(int) * px, hipMemcpyDeviceToHost, c->stream), "read AOVs");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
-  return MOPTIX_OK;
+  const size_t plane = sizeof(float) * px;      // the ids are 4 bytes a pixel as well
+  return read_back(c, { { dst->albedo, p.albedo, 3 * plane }, { dst->normal, p.normal, 3 * plane }, { dst->depth, p.depth, plane },
+                        { dst->hits, p.hits, plane }, { dst->primId, p.primId, plane }, { dst->matId, p.matId, plane } }, "read AOVs");
 }
 
 int moptix_aov_bind(moptix_context c, const moptix_aov_buffers* dstDevice) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,19 @@ template <class T> struct DevBuf {
     return hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+// Unit ids in descending order of their keys, ties in id order: the depth history of the beauty launches (keys: the cost buffer the trace
+// kernels write, LaunchArgs::tileCost; units: pixels or 8x8 tiles) and the adaptive passes' list (keys: k_ad_mask's, one per pixel slot).
+// Defined in api_render.hip, beside the one instantiation of rocprim's sort.
+struct OrderList {
+  long long units = -1;              // units the list holds (-1 = none: the next ensure() starts it afresh)
+  DevBuf<unsigned int> keys, keysSorted; DevBuf<int> order, iota; DevBuf<uint8_t> sortTmp;
+  // n units: no-op when the list holds n, else buffers, iota, zero keys and the sort's scratch; synchronises the stream
+  hipError_t ensure(long long n, hipStream_t stream);
+  hipError_t sort(hipStream_t stream);      // keys -> order (stable radix sort, descending), asynchronously
+  void forget() { units = -1; }
+  void release() { keys.release(); keysSorted.release(); order.release(); iota.release(); sortTmp.release(); units = -1; }
 };
 
 // moptix_set_option / moptix_get_option (api_core.hip kOptions: names, accepted values, what a change invalidates)
@@ -108,13 +122,9 @@ struct moptix_context_t {
     dSeeds.release(); dWork.release(); dCounters.release(); dOverflow.release(); dPoolCold.release(); dSampleBuf.release();
     tiles.release();
   }
-  // which units (pixels or 8x8 tiles) had the deepest paths in earlier launches: they are handed out first (LaunchArgs::tileOrder)
-  struct TileHistory {
-    long long units = -1;            // units the history holds (-1 = none: the next launch starts it afresh)
-    DevBuf<unsigned int> cost, costSorted; DevBuf<int> order, iota; DevBuf<uint8_t> sortTmp;
-    void forget() { units = -1; }
-    void release() { cost.release(); costSorted.release(); order.release(); iota.release(); sortTmp.release(); units = -1; }
-  } tiles;
+  // which units (pixels or 8x8 tiles) had the deepest paths in earlier launches: they are handed out first (LaunchArgs::tileOrder);
+  // forgotten by a new scene, partition or granularity
+  pt::api::OrderList tiles;
 
   // ---- multi-GPU, one process per GPU (api_comm.hip): RCCL communicator of this rank + staging for the tile gather ----
   struct Comm {
@@ -175,22 +185,23 @@ struct moptix_context_t {
   // its back (frame-size change, moptix_accum_clear, moptix_accum_bind, a clearing moptix_resolve_rgb8) ----
   struct Adaptive {
     DevBuf<uint32_t> count; DevBuf<float> moments, error; DevBuf<uint8_t> converged;
-    DevBuf<unsigned int> key, keySorted; DevBuf<int> order, iota; DevBuf<uint8_t> sortTmp;
+    pt::api::OrderList order;                  // the pixel slots, active ones first
     DevBuf<unsigned int> partials, totals;     // four words per 16x16 workgroup of the mask kernel; AdaptiveTotals
     DevBuf<float> mean;                        // staging of moptix_adaptive_mean (allocated at its first call)
     size_t pixels = 0;               // frame size the state holds (0 = to be (re)allocated and zeroed at the next adaptive call)
-    int items = 0;                   // pixel slots the order list holds
     bool have = false;               // samples added since the clear: count describes the accumulation buffer
     void drop() { pixels = 0; have = false; }
     void release() {
       count.release(); moments.release(); error.release(); converged.release();
-      key.release(); keySorted.release(); order.release(); iota.release(); sortTmp.release(); partials.release(); totals.release(); mean.release();
-      items = 0; drop();
+      order.release(); partials.release(); totals.release(); mean.release();
+      drop();
     }
   } ad;
 };
 
-namespace pt { namespace api {
+namespace pt {
+struct DenoiseConsts;      // pt_denoise.h
+namespace api {
 
 // the error text goes to the context, or (no context: moptix_create, moptix_comm_unique_id) to the library's own
 int fail(moptix_context c, int code, const std::string& msg);
@@ -200,9 +211,20 @@ int hipFail(moptix_context c, hipError_t e, const char* what);
 int check_ready(moptix_context c);                   // params set, tree built, stream alive
 float* accum_ptr(moptix_context c);
 int ensure_accum(moptix_context c);
+// What a call that uses the device starts with: hipSetDevice, the batch in flight finishes (moptix_sync: timed, watchdog flag read) and,
+// withAccum, the accumulation buffer exists at this frame size.
+int begin_call(moptix_context c, bool withAccum);
+// Copies every entry with a host destination from its device buffer, then synchronises the stream.
+struct ReadBack { void* dst; const void* src; size_t bytes; };
+int read_back(moptix_context c, std::initializer_list<ReadBack> copies, const char* what);
 void fill_view(moptix_context c, SceneView& v);
 moptix_aov_buffers aov_ptrs(moptix_context c);       // api_aov.hip: bound or own, member by member
 void comm_release(moptix_context c);                 // api_comm.hip: destroys the communicator, frees the staging
+// api_denoise.hip, for moptix_denoise and moptix_denoise_temporal alike: the context is usable and has AOV samples, begin_call, the
+// scratch (guide: only the spatial entry's own; the temporal one filters under its history's) and the own output unless one is bound
+int denoise_begin(moptix_context c, bool ownGuide, size_t& px);
+void denoise_consts(moptix_context c, const moptix_denoise_params* p, DenoiseConsts& k);
+inline float* denoise_out(moptix_context c) { return c->dn.bound ? c->dn.bound : c->dn.out.p; }
 
 // ---- the launch plan (api_render.hip): what one batch of launches will run, decided from the context and the batch size alone ----
 struct LaunchPlan {
@@ -235,7 +257,5 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
 // One pass of n seeds from dSeeds: [order list sorted] trace kernel (+ drain kernel) and the reduction, between the context's events;
 // asynchronous (moptix_sync times it and reads the watchdog flag).
 int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, const PassOverride* over);
-// (key, id) pairs in descending key order, stable; tmp == nullptr: only tmpBytes, the scratch the sort needs, is set
-hipError_t sort_pairs_desc(void* tmp, size_t& tmpBytes, unsigned int* keys, unsigned int* keysSorted, int* ids, int* idsSorted, size_t n, hipStream_t stream);
 
 }}  // namespace pt::api

@@ -38,6 +38,19 @@ int ensure_accum(moptix_context c) {
   return MOPTIX_OK;
 }
 
+int begin_call(moptix_context c, bool withAccum) {
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  const int rc = moptix_sync(c);      // one batch in flight at a time: it finishes (and is timed) first
+  return rc != MOPTIX_OK || !withAccum ? rc : ensure_accum(c);
+}
+
+int read_back(moptix_context c, std::initializer_list<ReadBack> copies, const char* what) {
+  for (const ReadBack& r : copies)
+    if (r.dst) HIPCHK(c, hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream), what);
+  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
+  return MOPTIX_OK;
+}
+
 void fill_view(moptix_context c, SceneView& v) {
   memset(&v, 0, sizeof(v));
   const moptix_params& p = c->params;

@@ -201,28 +201,10 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   return MOPTIX_OK;
 }
 
-// New frame size / partition / granularity: forget which units had deep paths and start the history afresh.
-int start_tile_history(moptix_context c, long long historyUnits) {
-  auto& t = c->tiles;
-  HIPCHK(c, t.cost.ensure((size_t)historyUnits), "alloc tile cost");
-  HIPCHK(c, t.costSorted.ensure((size_t)historyUnits), "alloc tile cost");
-  HIPCHK(c, t.order.ensure((size_t)historyUnits), "alloc tile order");
-  std::vector<int> iota((size_t)historyUnits);
-  for (size_t i = 0; i < iota.size(); i++) iota[i] = (int)i;
-  HIPCHK(c, t.iota.upload(iota, c->stream), "upload tile ids");
-  HIPCHK(c, hipMemsetAsync(t.cost.p, 0, sizeof(unsigned int) * (size_t)historyUnits, c->stream), "zero tile cost");
-  size_t tmpBytes = 0;
-  HIPCHK(c, rocprim::radix_sort_pairs_desc(nullptr, tmpBytes, t.cost.p, t.costSorted.p, t.iota.p, t.order.p, (size_t)historyUnits, 0, 32, c->stream), "size tile sort");
-  HIPCHK(c, t.sortTmp.ensure(tmpBytes), "alloc sort scratch");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync tile history");    // iota staging dies here
-  t.units = historyUnits;
-  return MOPTIX_OK;
-}
-
 // MOPTIX_DEBUG: how the deepest-path history is distributed over the tiles
 int report_tile_history(moptix_context c) {
   std::vector<unsigned int> cost((size_t)c->tiles.units);
-  HIPCHK(c, hipMemcpy(cost.data(), c->tiles.cost.p, sizeof(unsigned int) * cost.size(), hipMemcpyDeviceToHost), "read tile cost");
+  HIPCHK(c, hipMemcpy(cost.data(), c->tiles.keys.p, sizeof(unsigned int) * cost.size(), hipMemcpyDeviceToHost), "read tile cost");
   size_t hist[6] = { 0, 0, 0, 0, 0, 0 };                        // 0, 8..15, 16..63, 64..255, 256+, first half of the tiles holding 256+
   for (size_t i = 0; i < cost.size(); i++) {
     const unsigned int v = cost[i];
@@ -302,8 +284,8 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   a.workCounter = c->dWork.p;
   a.tileMajor = p.tileMajor; a.unitShift = p.unitShift;
   if (p.tileMajor) {
-    if (c->tiles.units != p.historyUnits && (rc = start_tile_history(c, p.historyUnits)) != MOPTIX_OK) return rc;
-    a.tileOrder = c->tiles.order.p; a.tileCost = c->tiles.cost.p;
+    HIPCHK(c, c->tiles.ensure(p.historyUnits, c->stream), "start depth history");      // new frame size / partition / granularity: afresh
+    a.tileOrder = c->tiles.order.p; a.tileCost = c->tiles.keys.p;
   }
   if (counted) {
     HIPCHK(c, c->dCounters.ensure(kCntTotal), "alloc counters");
@@ -314,10 +296,33 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   return MOPTIX_OK;
 }
 
-// rocprim's radix sort of (key, id) pairs, descending and stable, instantiated in this file alone: the depth history's order list
-// (start_tile_history, launch_pass) and the adaptive passes' (api_adaptive.hip) are the same template.
-hipError_t sort_pairs_desc(void* tmp, size_t& tmpBytes, unsigned int* keys, unsigned int* keysSorted, int* ids, int* idsSorted, size_t n, hipStream_t stream) {
-  return rocprim::radix_sort_pairs_desc(tmp, tmpBytes, keys, keysSorted, ids, idsSorted, n, 0, 32, stream);
+// ---- OrderList (api_context.h).  rocprim's radix sort of (key, id) pairs, descending and stable (ties stay in id order), is instantiated
+// here alone: tmp == nullptr sets only tmpBytes, the scratch the sort needs.
+static hipError_t sort_pairs_desc(void* tmp, size_t& tmpBytes, OrderList& l, size_t n, hipStream_t stream) {
+  return rocprim::radix_sort_pairs_desc(tmp, tmpBytes, l.keys.p, l.keysSorted.p, l.iota.p, l.order.p, n, 0, 32, stream);
+}
+
+hipError_t OrderList::ensure(long long n, hipStream_t stream) {
+  if (units == n) return hipSuccess;
+  units = -1;
+  std::vector<int> ids((size_t)n);
+  for (size_t i = 0; i < ids.size(); i++) ids[i] = (int)i;
+  hipError_t e = keys.ensure((size_t)n);
+  if (e == hipSuccess) e = keysSorted.ensure((size_t)n);
+  if (e == hipSuccess) e = order.ensure((size_t)n);
+  if (e == hipSuccess) e = iota.upload(ids, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(keys.p, 0, sizeof(unsigned int) * (size_t)n, stream);
+  size_t tmpBytes = 0;
+  if (e == hipSuccess) e = sort_pairs_desc(nullptr, tmpBytes, *this, (size_t)n, stream);
+  if (e == hipSuccess) e = sortTmp.ensure(tmpBytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);      // ids dies here
+  if (e == hipSuccess) units = n;
+  return e;
+}
+
+hipError_t OrderList::sort(hipStream_t stream) {
+  size_t tmpBytes = sortTmp.n;
+  return sort_pairs_desc(sortTmp.p, tmpBytes, *this, (size_t)units, stream);
 }
 
 int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, const PassOverride* over) {
@@ -326,12 +331,7 @@ int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, con
   a.seeds = dSeeds; a.nSeeds = n; a.nWork = over ? over->nWork : n * a.nItems;
   HIPCHK(c, hipMemsetAsync(c->dWork.p, 0, (2 + kDrainCap) * sizeof(int), c->stream), "zero work counter");      // counters only: capacity and threshold stay
   if (over) a.tileOrder = over->order;
-  else if (a.tileMajor && a.tileCost) {
-    // tiles in descending order of the deepest path seen so far (stable: ties stay in raster order)
-    auto& t = c->tiles;
-    size_t tmpBytes = t.sortTmp.n;
-    HIPCHK(c, rocprim::radix_sort_pairs_desc(t.sortTmp.p, tmpBytes, t.cost.p, t.costSorted.p, t.iota.p, t.order.p, (size_t)p.historyUnits, 0, 32, c->stream), "sort tiles");
-  }
+  else if (a.tileMajor && a.tileCost) HIPCHK(c, c->tiles.sort(c->stream), "sort tiles");      // deepest path seen so far first, ties in raster order
   HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
   if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast), p.kernel->launchWhat);
   else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
@@ -359,9 +359,7 @@ int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool count
   if (rc != MOPTIX_OK) return rc;
   if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
   if (c->ad.have) return fail(c, MOPTIX_ERR_STATE, "the accumulation buffer holds an adaptive render (per-pixel sample counts): moptix_adaptive_clear or moptix_accum_clear first");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;     // one batch in flight at a time
-  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
+  if ((rc = begin_call(c, true)) != MOPTIX_OK) return rc;
   if (nSeeds == 0) return MOPTIX_OK;
   RenderLaunch r;
   if ((rc = prepare_launch(c, nSeeds, counted, false, r)) != MOPTIX_OK || r.p.nItems == 0) return rc;

@@ -17,17 +17,6 @@ TpCamera to_camera(const moptix_cam_params& c) {
   return t;
 }
 
-bool finite_in(float v, float lo, float hi) { return __builtin_isfinite(v) && v >= lo && v <= hi; }
-
-const char* bad_temporal_params(const moptix_temporal_params* t) {
-  if (!finite_in(t->alpha, 0.0f, 1.0f) || !finite_in(t->alphaMoments, 0.0f, 1.0f)) return "alpha and alphaMoments in [0,1]";
-  if (!__builtin_isfinite(t->depthTolerance) || !(t->depthTolerance >= 0.0f)) return "depthTolerance must be finite and >= 0";
-  if (!finite_in(t->normalThreshold, -1.0f, 1.0f)) return "normalThreshold in [-1,1]";
-  if (t->maxHistory < 1 || t->maxHistory > 65536) return "maxHistory in [1,65536]";
-  if (t->varianceFrames < 1 || t->varianceFrames > 65536) return "varianceFrames in [1,65536]";
-  return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -42,32 +31,18 @@ int moptix_temporal_defaults(moptix_temporal_params* out) {
 int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, const moptix_temporal_params* t, float nAccumulation) {
   // the checks of the arguments themselves come first: they need no context (a NULL one then fails as a null argument)
   if (!p || !t) return fail(c, MOPTIX_ERR_INVALID, "null argument");
-  if (!(nAccumulation > 0.0f) || !__builtin_isfinite(nAccumulation)) return fail(c, MOPTIX_ERR_INVALID, "nAccumulation must be > 0");
-  if (p->iterations < 0 || p->iterations > 8) return fail(c, MOPTIX_ERR_INVALID, "iterations in [0,8]");
-  if (p->normalPower < 1 || p->normalPower > 256) return fail(c, MOPTIX_ERR_INVALID, "normalPower in [1,256]");
-  if (p->demodulate != 0 && p->demodulate != 1) return fail(c, MOPTIX_ERR_INVALID, "demodulate is 0 or 1");
-  if (!(p->sigmaLuminance >= 0.0f) || !__builtin_isfinite(p->sigmaLuminance) || !(p->sigmaDepth >= 0.0f) || !__builtin_isfinite(p->sigmaDepth))
-    return fail(c, MOPTIX_ERR_INVALID, "sigmas must be finite and >= 0");
-  if (const char* why = bad_temporal_params(t)) return fail(c, MOPTIX_ERR_INVALID, why);
+  const char* why = dn_bad_params(nAccumulation, p->iterations, p->normalPower, p->demodulate, p->sigmaLuminance, p->sigmaDepth);
+  if (!why) why = tp_bad_params(t->alpha, t->alphaMoments, t->depthTolerance, t->normalThreshold, t->maxHistory, t->varianceFrames);
+  if (why) return fail(c, MOPTIX_ERR_INVALID, why);
   if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
-  if (c->poisoned) return fail(c, MOPTIX_ERR_COMM, "this context is unusable: kernels of an aborted collective never left its stream");
-  if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "moptix_set_params has not been called");
-  if (c->aov.samples == 0) return fail(c, MOPTIX_ERR_STATE, "no AOV samples: moptix_render_aovs first");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc;
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;       // a beauty batch still in flight finishes (and is timed) first
-  if ((rc = ensure_accum(c)) != MOPTIX_OK) return rc;
-  const size_t px = (size_t)c->params.width * c->params.height;
-  if (px > 0x7fffffffULL) return fail(c, MOPTIX_ERR_LIMIT, "frame too large");
+  size_t px;
+  const int rc = denoise_begin(c, false, px);      // the filter runs in the denoiser's scratch, under this call's history guide
+  if (rc != MOPTIX_OK) return rc;
   moptix_context_t::Temporal& s = c->tp;
   const int demodulate = p->iterations > 0 ? p->demodulate : 0;
   const int nSpheres = (int)c->spheres.size();
   if (!tp_history_kept(s.have, (int)s.width, (int)s.height, s.nSpheres, s.demodulate, (int)c->params.width, (int)c->params.height, nSpheres, demodulate))
     s.drop();
-  HIPCHK(c, c->dn.colA.ensure(px), "alloc denoiser");
-  HIPCHK(c, c->dn.colB.ensure(px), "alloc denoiser");
-  HIPCHK(c, c->dn.side.ensure(px), "alloc denoiser");
-  if (!c->dn.bound) HIPCHK(c, c->dn.out.ensure(3 * px), "alloc denoiser output");
   for (int i = 0; i < 2; i++) {
     HIPCHK(c, s.col[i].ensure(px), "alloc temporal history");
     HIPCHK(c, s.guide[i].ensure(px), "alloc temporal history");
@@ -82,8 +57,7 @@ int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, co
 
   TemporalArgs a;
   memset(&a, 0, sizeof(a));
-  a.k.width = (int)c->params.width; a.k.height = (int)c->params.height; a.k.normalPower = p->normalPower;
-  a.k.sigmaLuminance = p->sigmaLuminance; a.k.sigmaDepth = p->sigmaDepth;
+  denoise_consts(c, p, a.k);
   a.t.width = a.k.width; a.t.height = a.k.height;
   a.t.maxHistory = t->maxHistory; a.t.varianceFrames = t->varianceFrames;
   a.t.alpha = t->alpha; a.t.alphaMoments = t->alphaMoments; a.t.depthTolerance = t->depthTolerance; a.t.normalThreshold = t->normalThreshold;
@@ -114,7 +88,7 @@ int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, co
   a.motionOut = s.motionOut.p; a.historyOut = s.historyOut.p;
   a.partials = reinterpret_cast<uint4*>(s.partials.p);
   a.counters = reinterpret_cast<TemporalCounters*>(s.counters.p);
-  a.out = c->dn.bound ? c->dn.bound : c->dn.out.p;
+  a.out = denoise_out(c);
   const uint64_t frames = s.frames;
   s.drop();                                                  // a failure below leaves no half-written history behind
   HIPCHK(c, launch_temporal(c->stream, a), "launch temporal denoiser");
@@ -152,13 +126,10 @@ int moptix_temporal_read(moptix_context c, const moptix_temporal_buffers* dstHos
   if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "no params");
   const size_t px = (size_t)c->params.width * c->params.height;
   if (c->tp.pixels != px) return fail(c, MOPTIX_ERR_STATE, "no moptix_denoise_temporal call at this frame size");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc;
-  if ((rc = moptix_sync(c)) != MOPTIX_OK) return rc;
-  if (dstHost->motion) HIPCHK(c, hipMemcpyAsync(dstHost->motion, c->tp.motionOut.p, sizeof(float) * 2 * px, hipMemcpyDeviceToHost, c->stream), "read motion vectors");
-  if (dstHost->history) HIPCHK(c, hipMemcpyAsync(dstHost->history, c->tp.historyOut.p, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream), "read history lengths");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
-  return MOPTIX_OK;
+  const int rc = begin_call(c, false);
+  if (rc != MOPTIX_OK) return rc;
+  return read_back(c, { { dstHost->motion, c->tp.motionOut.p, sizeof(float) * 2 * px }, { dstHost->history, c->tp.historyOut.p, sizeof(float) * px } },
+                   "read motion vectors / history lengths");
 }
 
 }  // extern "C"

@@ -15,7 +15,13 @@ struct DenoiseArgs {
   float* out;                                                   // float3 W*H
 };
 
-// All passes on `stream`, asynchronously: decode, prepass and iterations when iterations > 0, final.
+// All passes on `stream`, asynchronously: decode, then the a-trous chain.
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& a);
+
+// The a-trous chain over colA (the decoded or reprojected signal): prepass colA -> colB and `iterations` ping-pong passes at step 2^i when
+// iterations > 0, final -> out.  temporalVariance: the prepass keeps col.w where tp_reproject left a temporal variance (pt_temporal.h
+// tp_prepass) instead of taking the 3x3 spatial estimate everywhere.  This is the one place that says which buffer is current.
+hipError_t launch_atrous(hipStream_t stream, const DenoiseConsts& k, v4* colA, v4* colB, const v4* guide, v4* side, int iterations,
+                         bool temporalVariance, float* out);
 
 }  // namespace pt

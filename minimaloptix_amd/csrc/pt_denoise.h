@@ -66,6 +66,18 @@ struct DenoiseConsts {
   float sigmaLuminance, sigmaDepth;
 };
 
+// The argument check of moptix_denoise and moptix_denoise_temporal: null when nAccumulation and the moptix_denoise_params members are in
+// range, else what is wrong with them.
+PT_HD const char* dn_bad_params(float nAccumulation, int iterations, int normalPower, int demodulate, float sigmaLuminance, float sigmaDepth) {
+  if (!(nAccumulation > 0.0f) || !__builtin_isfinite(nAccumulation)) return "nAccumulation must be > 0";
+  if (iterations < 0 || iterations > 8) return "iterations in [0,8]";
+  if (normalPower < 1 || normalPower > 256) return "normalPower in [1,256]";
+  if (demodulate != 0 && demodulate != 1) return "demodulate is 0 or 1";
+  if (!(sigmaLuminance >= 0.0f) || !__builtin_isfinite(sigmaLuminance) || !(sigmaDepth >= 0.0f) || !__builtin_isfinite(sigmaDepth))
+    return "sigmas must be finite and >= 0";
+  return nullptr;
+}
+
 // Pass 1, pixel p: C = accum / nAcc, and for a geometry pixel (hits > 0) A = albedo / S, N = normalize(normal / S) (0 where that is
 // 0), Z = depth / hits -- each division one IEEE operation per component, normalize as AC3.  demodulate: I = C / max(A, 1e-3) per
 // channel, else I = C.  A background pixel stores I = C, guide (0, 0, 0, kDnBackground) and a = 1.

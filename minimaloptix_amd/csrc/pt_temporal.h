@@ -38,6 +38,16 @@ struct TemporalConsts {
   float det;                    // dot(a, bc)
 };
 
+// The check of moptix_temporal_params: null when its members are in range, else what is wrong with them.
+PT_HD const char* tp_bad_params(float alpha, float alphaMoments, float depthTolerance, float normalThreshold, int maxHistory, int varianceFrames) {
+  if (!(alpha >= 0.0f && alpha <= 1.0f) || !(alphaMoments >= 0.0f && alphaMoments <= 1.0f)) return "alpha and alphaMoments in [0,1]";      // NaN fails
+  if (!__builtin_isfinite(depthTolerance) || !(depthTolerance >= 0.0f)) return "depthTolerance must be finite and >= 0";
+  if (!(normalThreshold >= -1.0f && normalThreshold <= 1.0f)) return "normalThreshold in [-1,1]";
+  if (maxHistory < 1 || maxHistory > 65536) return "maxHistory in [1,65536]";
+  if (varianceFrames < 1 || varianceFrames > 65536) return "varianceFrames in [1,65536]";
+  return nullptr;
+}
+
 // The 3x3 solve's constants from the previous camera.
 PT_HD void tp_solve_consts(const TpCamera& prev, TemporalConsts& k) {
   const v3 a = prev.lowerLeft - prev.origin, b = prev.horizontal, c = prev.vertical;

@@ -3,10 +3,10 @@
 // this frame's beauty; the temporal luminance moments drive the filter's edge stop where a pixel has history.
 //
 // Its own translation unit, as aovkernel.hip and denoisekernel.hip: the trace kernels' register allocation moves with code they
-// never run (NOTEBOOK.md), so nothing of this pass is compiled into them, and denoisekernel.hip keeps its code object as well -- the
-// iterate and final kernels here are this file's own wrappers around the same pt_denoise.h functions.
+// never run (NOTEBOOK.md), so nothing of this pass is compiled into them.  This file holds the reprojection and its counters; the
+// a-trous passes behind them, the variance-keeping prepass k_tp_prepass included, are denoisekernel.hip's (launch_atrous).
 //
-// The denoiser's mapping: a lane per pixel, a 256-thread workgroup covers 16x16 pixels as four 8x8 tiles, one per wave.  Under
+// The denoiser's mapping (image_tile.h): a lane per pixel, a 256-thread workgroup covers 16x16 pixels as four 8x8 tiles, one per wave.  Under
 // camera motion a wave's 2x2 bilinear taps fall on a 9x9-pixel neighbourhood of the history: three 16-byte records per tap
 // ({I_acc, h}, {N, Z}, {m1, m2, matId, -}), each one vector load, the material id in the moments record's spare component.
 // The counters of moptix_temporal_info are reduced per wave (ballot / shuffle), then per workgroup through LDS into one 16-byte
@@ -14,20 +14,15 @@
 // not depend on the order.  (One atomic per wave and counter on a single record serialised in the L2 and cost 1.5 ms at 1920x1080.)
 #include <hip/hip_runtime.h>
 
+#include "denoisekernel.h"
+#include "image_tile.h"
 #include "temporalkernel.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = 256;
-
-__device__ __forceinline__ bool tp_pixel(int width, int height, int& x, int& y) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  x = (blockIdx.x * 2 + (wave & 1)) * 8 + (lane & 7);
-  y = (blockIdx.y * 2 + (wave >> 1)) * 8 + (lane >> 3);
-  return x < width && y < height;
-}
+constexpr int kBlockThreads = kImageBlockThreads;
 
 __device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
   for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
@@ -36,7 +31,7 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
 
 __global__ void __launch_bounds__(kBlockThreads) k_tp_reproject(const TemporalArgs a) {
   int x, y;
-  const bool inside = tp_pixel(a.k.width, a.k.height, x, y);   // no early return: the whole wave takes part in the reduction
+  const bool inside = image_pixel(a.k.width, a.k.height, x, y);   // no early return: the whole wave takes part in the reduction
   bool geometry = false, history = false;
   unsigned int hlen = 0;
   if (inside) {
@@ -80,54 +75,13 @@ __global__ void __launch_bounds__(kBlockThreads) k_tp_reduce(const uint4* __rest
   }
 }
 
-__global__ void __launch_bounds__(kBlockThreads) k_tp_prepass(const DenoiseConsts k, const v4* __restrict__ colIn, const v4* __restrict__ guide,
-                                                             v4* __restrict__ colOut, v4* __restrict__ side) {
-  int x, y;
-  if (!tp_pixel(k.width, k.height, x, y)) return;
-  const int p = y * k.width + x;
-  v4 c = colIn[p];
-  if (dn_geometry(guide[p])) {
-    float g;
-    c.w = tp_prepass(k, colIn, guide, x, y, g);
-    side[p].w = g;
-  }
-  colOut[p] = c;
-}
-
-__global__ void __launch_bounds__(kBlockThreads) k_tp_iterate(const DenoiseConsts k, const v4* __restrict__ colIn, const v4* __restrict__ guide,
-                                                             const v4* __restrict__ side, v4* __restrict__ colOut, int step) {
-  int x, y;
-  if (!tp_pixel(k.width, k.height, x, y)) return;
-  const int p = y * k.width + x;
-  colOut[p] = dn_geometry(guide[p]) ? dn_iterate(k, colIn, guide, x, y, step, side[p].w) : colIn[p];
-}
-
-__global__ void __launch_bounds__(kBlockThreads) k_tp_final(const DenoiseConsts k, const v4* __restrict__ col, const v4* __restrict__ guide,
-                                                           const v4* __restrict__ side, float* __restrict__ out) {
-  int x, y;
-  if (!tp_pixel(k.width, k.height, x, y)) return;
-  const int p = y * k.width + x;
-  dn_final(col[p], guide[p], side[p], out, p);
-}
-
 }  // namespace
 
 hipError_t launch_temporal(hipStream_t stream, const TemporalArgs& a) {
-  const dim3 grid((a.k.width + 15) / 16, (a.k.height + 15) / 16);
+  const dim3 grid = image_grid(a.k.width, a.k.height);
   k_tp_reproject<<<grid, kBlockThreads, 0, stream>>>(a);
   k_tp_reduce<<<1, kBlockThreads, 0, stream>>>(a.partials, (int)(grid.x * grid.y), a.counters);
-  v4* cur = a.colA;
-  if (a.iterations > 0) {
-    k_tp_prepass<<<grid, kBlockThreads, 0, stream>>>(a.k, a.colA, a.histGuide, a.colB, a.side);
-    cur = a.colB;
-    for (int i = 0; i < a.iterations; i++) {
-      v4* next = cur == a.colA ? a.colB : a.colA;
-      k_tp_iterate<<<grid, kBlockThreads, 0, stream>>>(a.k, cur, a.histGuide, a.side, next, 1 << i);
-      cur = next;
-    }
-  }
-  k_tp_final<<<grid, kBlockThreads, 0, stream>>>(a.k, cur, a.histGuide, a.side, a.out);
-  return hipGetLastError();
+  return launch_atrous(stream, a.k, a.colA, a.colB, a.histGuide, a.side, a.iterations, true, a.out);
 }
 
 }  // namespace pt

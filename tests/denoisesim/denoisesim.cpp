@@ -1,15 +1,14 @@
 // denoisesim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the denoiser kernels (minimaloptix_amd/csrc/denoisekernel.hip): the same
 // per-pixel code (pt_denoise.h), compiled for the host and run pass by pass over caller-given float arrays, in the order the kernels
-// run it.  The GPU tests compare the kernels' output with this bit for bit.  It is not part of the product: nothing under
-// minimaloptix_amd/ builds or loads it.
+// run it (atrous_host.h, which temporalsim shares).  The GPU tests compare the kernels' output with this bit for bit.  It is not part of
+// the product: nothing under minimaloptix_amd/ builds or loads it.
 #include <stddef.h>
 #include <stdint.h>
 
-#include <utility>
 #include <vector>
 
 #include "../../include/moptix.h"
-#include "../../minimaloptix_amd/csrc/pt_denoise.h"
+#include "atrous_host.h"
 
 using namespace pt;
 
@@ -29,28 +28,7 @@ int denoisesim_run(int width, int height, const float* accum, const float* albed
   std::vector<v4> colA(n), colB(n), guide(n), side(n);
 #pragma omp parallel for
   for (int p = 0; p < n; p++) dn_decode(accum, albedo, normal, depth, hits, nAccumulation, nSamples, demodulate, p, colA[p], guide[p], side[p]);
-  v4* cur = colA.data();
-  if (prm->iterations > 0) {
-#pragma omp parallel for
-    for (int p = 0; p < n; p++) {
-      v4 c = colA[p];
-      if (dn_geometry(guide[p])) {
-        float g;
-        c.w = dn_prepass(k, colA.data(), guide.data(), p % width, p / width, g);
-        side[p].w = g;
-      }
-      colB[p] = c;
-    }
-    cur = colB.data();
-    for (int i = 0; i < prm->iterations; i++) {
-      v4* next = cur == colA.data() ? colB.data() : colA.data();
-#pragma omp parallel for
-      for (int p = 0; p < n; p++)
-        next[p] = dn_geometry(guide[p]) ? dn_iterate(k, cur, guide.data(), p % width, p / width, 1 << i, side[p].w) : cur[p];
-      cur = next;
-    }
-  }
-  for (int p = 0; p < n; p++) dn_final(cur[p], guide[p], side[p], out, p);
+  atrous_host(k, colA, colB, guide.data(), side.data(), prm->iterations, false, nullptr, out);
   return 0;
 }
 

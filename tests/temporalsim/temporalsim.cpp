@@ -1,6 +1,7 @@
 // temporalsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of moptix_denoise_temporal (minimaloptix_amd/csrc/temporalkernel.hip and the
 // history bookkeeping of api_temporal.hip): the same per-pixel code (pt_temporal.h, pt_denoise.h), compiled for the host and run
-// pass by pass over caller-given float arrays, in the order the kernels run it, with the history kept in an object between calls.
+// pass by pass over caller-given float arrays, in the order the kernels run it (the a-trous passes: ../denoisesim/atrous_host.h), with the
+// history kept in an object between calls.
 // The GPU tests compare the device's output with this bit for bit.  It is not part of the product: nothing under minimaloptix_amd/
 // builds or loads it.
 #include <stddef.h>
@@ -9,7 +10,7 @@
 #include <vector>
 
 #include "../../include/moptix.h"
-#include "../../minimaloptix_amd/csrc/pt_temporal.h"
+#include "../denoisesim/atrous_host.h"
 
 using namespace pt;
 
@@ -90,31 +91,7 @@ int temporalsim_run(void* state, int width, int height, const float* accum, cons
     if (historyOut) historyOut[p] = r.hist.w;
     if (r.geometry) { cnt[0]++; cnt[1] += r.history ? 1 : 0; cnt[2] += r.history ? 0 : 1; cnt[3] += (uint64_t)r.hist.w; }
   }
-  v4* curCol = colA.data();
-  if (prm->iterations > 0) {
-#pragma omp parallel for
-    for (int p = 0; p < n; p++) {
-      v4 c = colA[p];
-      if (dn_geometry(guide[p])) {
-        float g;
-        c.w = tp_prepass(k, colA.data(), guide.data(), p % width, p / width, g);
-        side[p].w = g;
-      }
-      colB[p] = c;
-    }
-    curCol = colB.data();
-    if (pre) for (int p = 0; p < n; p++) { pre[4 * (size_t)p] = colB[p].x; pre[4 * (size_t)p + 1] = colB[p].y; pre[4 * (size_t)p + 2] = colB[p].z; pre[4 * (size_t)p + 3] = colB[p].w; }
-    for (int i = 0; i < prm->iterations; i++) {
-      v4* next = curCol == colA.data() ? colB.data() : colA.data();
-#pragma omp parallel for
-      for (int p = 0; p < n; p++)
-        next[p] = dn_geometry(guide[p]) ? dn_iterate(k, curCol, guide.data(), p % width, p / width, 1 << i, side[p].w) : curCol[p];
-      curCol = next;
-    }
-  } else if (pre) {
-    for (int p = 0; p < n; p++) { pre[4 * (size_t)p] = colA[p].x; pre[4 * (size_t)p + 1] = colA[p].y; pre[4 * (size_t)p + 2] = colA[p].z; pre[4 * (size_t)p + 3] = colA[p].w; }
-  }
-  if (out) for (int p = 0; p < n; p++) dn_final(curCol[p], guide[p], side[p], out, p);
+  atrous_host(k, colA, colB, guide.data(), side.data(), prm->iterations, true, pre, out);
   if (counters) for (int i = 0; i < 4; i++) counters[i] = cnt[i];
   s->cur = cur; s->have = true; s->frames++;
   s->width = width; s->height = height; s->nSpheres = nSpheres; s->demodulate = demodulate;
