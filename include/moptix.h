@@ -270,6 +270,8 @@ int moptix_unpack_tiles(moptix_context ctx, int32_t rank, int32_t nRanks, const 
  *   "forget_history"   (write-only, any value) drop the per-pixel depth history that orders the work items ("tile_major"): the next launch
  *                      is ordered like the first one of a context -- what a single-frame render sees
  *   "comm_blocking"    1 = moptix_comm_init makes a blocking communicator even where a non-blocking one is available (default 0)
+ *   "query_blocks_per_cu"  ray queries: the grid's cap in workgroups of 256 rays per CU (default 32, 1..64); a longer batch is walked by
+ *                      that grid in a loop, and the stack overflow area is sized by it.  Time and memory only: same results for any value
  *   "drain_below"      variant 4: a workgroup of the trace kernel that is down to this many paths (default 64, 0 = never) hands them
  *                      to the drain kernel (csrc/drainkernel.hip: a wave per up to 16 paths, all lanes on one frontier) at their next
  *                      packet boundary and leaves; same image bits, ray and hit counts either way -- the node / triangle-test counts
@@ -505,6 +507,41 @@ int moptix_adaptive_read(moptix_context ctx, const moptix_adaptive_buffers* dstH
 int moptix_adaptive_mean(moptix_context ctx, float* dstHost);
 int moptix_adaptive_mean_device(moptix_context ctx, float* dstDevice);
 int moptix_adaptive_resolve_rgb8(moptix_context ctx, uint8_t* dstHost);
+
+/* ---- ray queries (new): closest hit and occlusion for the caller's own rays ---------------------------------------------------
+ * A ray is eight floats  ox oy oz dx dy dz tmin tmax  (moptix_debug_trace's layout).  The direction is used as given, not normalised;
+ * t is in units of |d| (the sphere intersector solves the unit-direction quadratic, as for every ray of the renderer: give spheres
+ * unit directions).  Needs moptix_set_params and moptix_build_accel like a render; the camera and the frame size play no part.
+ * MOPTIX_QUERY_CLOSEST -> one moptix_hit (32 bytes) per ray:
+ *   t     distance along the ray of the nearest primitive: nearest by (t, prim) among the primitives the ray meets with
+ *         tmin < t < tmax; at exactly equal t the lower prim wins (rule D5), so the answer depends neither on the tree nor on the
+ *         node format nor on scheduling.  Every primitive counts, whatever its material (lights and glass included).
+ *   prim  primitive id: spheres, then quads, then triangles by original face id (what moptix_debug_trace reports); -1 = miss
+ *   mat   material id of the primitive; -1 on a miss
+ *   u, v  triangles: the barycentric weights of the face's second and third vertex (the hit point is p0 + u (p1 - p0) + v (p2 - p0));
+ *         0 for spheres and quads
+ *   ng    geometric normal as the closest-hit programs receive it, before any face-forward flip: triangles normalize(cross(p0 - p2,
+ *         p1 - p0)), spheres normalize(hit point - centre), quads the plane's normal
+ *   miss  t = tmax, prim = mat = -1, every other field 0
+ * MOPTIX_QUERY_ANY -> one int32 per ray: 1 if and only if the closest query on the same ray reports prim >= 0, else 0.  Purely
+ * geometric (the shadow rays' material classes, "shadow_rule" and Disney glass play no part); the traversal stops at the first
+ * primitive it accepts.
+ * Invalid rays are misses, decided before traversal: a non-finite component, tmax <= tmin, or a zero direction.  A negative tmin is
+ * walked as tmin = 0 (the traversal works on t >= 0, which is why moptix_set_params refuses a negative rayEpsilonT): nothing behind the
+ * origin is reported.
+ * Nodes: the 64-byte form where the tree has one, else the 128-byte one; option "node_format" 64 / 128 forces either (same bits).
+ *   moptix_query_rays_device  dRays, dOut: device memory, 16-byte aligned (dOut of MOPTIX_QUERY_ANY: 4).  Asynchronous on the
+ *                             context's stream (moptix_set_stream): moptix_sync, or the stream's own synchronisation, waits for
+ *                             it.  Allocates nothing after the first query on a tree: the stack overflow area
+ *                             lives in the context until moptix_clear_scene, moptix_build_accel or moptix_destroy.  The scene tables
+ *                             are read as they are when the kernel runs: a query after moptix_update_spheres sees the moved spheres.
+ *   moptix_query_rays         host pointers, blocking: upload, query, read back (staging kept in the context)
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 rays); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_render.  A query changes nothing else in the context. */
+typedef struct { float t; int32_t prim; int32_t mat; float u, v; float ng[3]; } moptix_hit;
+enum { MOPTIX_QUERY_CLOSEST = 0, MOPTIX_QUERY_ANY = 1 };
+int moptix_query_rays_device(moptix_context ctx, const float* dRays, int64_t n, int32_t mode, void* dOut);
+int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t mode, void* out);
 
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --

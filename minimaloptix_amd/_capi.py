@@ -150,6 +150,14 @@ class AdaptiveBuffers(C.Structure):
     _fields_ = [("count", C.c_void_p), ("moments", C.c_void_p), ("error", C.c_void_p), ("converged", C.c_void_p)]
 
 
+class Hit(C.Structure):
+    """moptix_hit: the record of a closest-hit ray query (32 bytes)."""
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("mat", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("ng", C.c_float * 3)]
+
+
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -166,6 +174,7 @@ DEVICE_SYMBOLS = [
     "moptix_temporal_defaults", "moptix_denoise_temporal", "moptix_temporal_reset", "moptix_temporal_info", "moptix_temporal_read",
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
+    "moptix_query_rays_device", "moptix_query_rays",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
@@ -257,6 +266,8 @@ def device_lib():
         L.moptix_adaptive_mean.argtypes = [vp, f32p]
         L.moptix_adaptive_mean_device.argtypes = [vp, vp]
         L.moptix_adaptive_resolve_rgb8.argtypes = [vp, u8p]
+        L.moptix_query_rays_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_rays.argtypes = [vp, f32p, C.c_int64, i32, vp]
         _dev = L
     return _dev
 

@@ -8,6 +8,11 @@ from . import _capi as K
 from ._capi import MoptixError
 
 
+# moptix_hit as a numpy record (include/moptix.h "ray queries")
+HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("ng", np.float32, (3,))])
+assert HIT_DTYPE.itemsize == C.sizeof(K.Hit) == 32
+
+
 def scenes_dir():
     """Folder holding `<name>/<name>.scene` (the reference's baseSceneFolder "scenes/")."""
     return os.path.join(K.REPO_ROOT, "scenes") + "/"
@@ -169,6 +174,7 @@ class Context:
         rc = self._L.moptix_create(C.byref(self._h), device)
         if rc != K.MOPTIX_OK:
             raise MoptixError(rc, self._L.moptix_last_error(None).decode())
+        self.device = int(device)
         self.width = self.height = 0
 
     def close(self):
@@ -504,6 +510,45 @@ class Context:
         out = np.empty((self.height, self.width, 3), np.uint8)
         self._chk(self._L.moptix_adaptive_resolve_rgb8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- ray queries (include/moptix.h "ray queries") ----
+    QUERY_MODES = dict(closest=K.QUERY_CLOSEST, any=K.QUERY_ANY)
+
+    def query_rays(self, rays, mode="closest"):
+        """Closest hit ("closest") or occlusion ("any") of the caller's rays, n x 8 floats o, d, tmin, tmax; blocking.
+        A numpy array takes the host path: "closest" returns a HIT_DTYPE record array (t, prim, mat, u, v, ng), "any" an int32 array.
+        A contiguous (n, 8) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
+        "any" an int32 tensor; "closest" a dict of views t, prim, mat, u, v, ng into "records", the (n, 8) float32 tensor of the
+        raw moptix_hit records."""
+        if mode not in self.QUERY_MODES:
+            raise ValueError("query_rays: mode %r (closest or any)" % (mode,))
+        m = self.QUERY_MODES[mode]
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):
+            rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
+            out = np.zeros(len(rays), HIT_DTYPE if m == K.QUERY_CLOSEST else np.int32)
+            self._chk(self._L.moptix_query_rays(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), m, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        if not rays.is_cuda:
+            raise ValueError("query_rays: the tensor must live on the GPU (its data_ptr is handed to a kernel); pass a numpy array for the host path")
+        if str(rays.dtype) != "torch.float32":
+            raise ValueError("query_rays: dtype %s" % rays.dtype)
+        if rays.device.index != self.device:
+            raise ValueError("query_rays: the tensor is on %s, the context on GPU %d" % (rays.device, self.device))
+        if not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("query_rays: must be a contiguous (n, 8) tensor")
+        n = rays.shape[0]
+        if m == K.QUERY_ANY:
+            out = torch.empty(n, dtype=torch.int32, device=rays.device)
+        else:
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()      # the rays are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_rays_device(self._h, C.c_void_p(rays.data_ptr()), n, m, C.c_void_p(out.data_ptr())))
+        self.sync()
+        if m == K.QUERY_ANY:
+            return out
+        ints = out.view(torch.int32)
+        return dict(records=out, t=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], ng=out[:, 5:8])
 
     def debug_read_accel(self):
         a = self.accel_info()

@@ -62,6 +62,7 @@ struct Options {
   int slotsInUse = -1;            // -1 = chosen per launch from its size
   int drainBelow = 64;            // a workgroup of the packet kernel with this many paths left hands them to the drain kernel (0 = off)
   int auxDepth = 16;              // variant 4: depth from which a path's shadow rays get slots of their own (0 = off)
+  int queryBlocksPerCU = 32;      // ray queries (querykernel.hip): the grid's cap in workgroups per CU; beyond it lanes loop over rays
 };
 
 }}  // namespace pt::api
@@ -197,6 +198,15 @@ struct moptix_context_t {
       drop();
     }
   } ad;
+
+  // ---- ray queries (api_query.hip): the stack overflow area of the query kernel, allocated at the first query after a build and
+  // dropped with the tree it was sized for (moptix_clear_scene, moptix_build_accel); the staging of the host-pointer entry point ----
+  struct Query {
+    DevBuf<int> overflow;
+    DevBuf<float> rays; DevBuf<uint8_t> out;
+    void drop() { overflow.release(); }
+    void release() { drop(); rays.release(); out.release(); }
+  } query;
 };
 
 namespace pt {

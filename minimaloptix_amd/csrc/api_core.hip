@@ -122,7 +122,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release();
+  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -168,6 +168,11 @@ int moptix_clear_scene(moptix_context c) {
   c->faceUV.clear(); c->anyUV = false; c->textures.clear();
   c->sceneDirty = true; c->accelBuilt = false;
   c->tp.drop();                                                // the temporal history belongs to the scene that made it
+  if (c->query.overflow.p && !c->poisoned) {                   // a query in flight still uses what is dropped here
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    c->query.drop();
+  }
   return MOPTIX_OK;
 }
 
@@ -294,6 +299,10 @@ int moptix_build_accel(moptix_context c, const char* kind) {
     return fail(c, MOPTIX_ERR_LIMIT, "acceleration structure too large: triangle / node tables must stay below 4 GB (2^28 triangles at most)");
   if ((unsigned long long)c->mats.size() * sizeof(DevMaterial) >= (1ull << 32)) return fail(c, MOPTIX_ERR_LIMIT, "material table must stay below 4 GB");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  if (c->query.overflow.p && !c->poisoned) {      // an asynchronous query in flight still walks the old tree; the area was sized for its depth
+    HIPCHK(c, hipStreamSynchronize(c->stream), "sync before the build");
+    c->query.drop();
+  }
   HIPCHK(c, c->dMats.upload(c->mats, c->stream), "upload materials");
   HIPCHK(c, c->dSpheres.upload(c->spheres, c->stream), "upload spheres");
   HIPCHK(c, c->dSphereMat.upload(c->sphereMat, c->stream), "upload sphere materials");

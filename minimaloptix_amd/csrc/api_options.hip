@@ -48,6 +48,7 @@ const Option kOptions[] = {
   { "watchdog_ms", &Options::watchdogMs, nullptr, 1, INT_MAX, ">= 1" },
   { "comm_timeout_ms", &Options::commTimeoutMs, nullptr, 1, INT_MAX, ">= 1" },
   { "comm_blocking", &Options::commBlocking, nullptr, 0, 1, "in {0,1}" },
+  { "query_blocks_per_cu", &Options::queryBlocksPerCU, nullptr, 1, 64, "in [1,64]" },
   { "forget_history", nullptr, nullptr, INT_MIN, INT_MAX, "", kTileHistory },      // the next launch orders its work like a context's first (measurement of a cold frame)
   { "comm_nonblocking_used", nullptr, [](moptix_context c) { return c->comm.nonBlocking ? 1 : 0; } },
   { "node_format_used", nullptr, [](moptix_context c) { return c->nodeFormatUsed; } },
