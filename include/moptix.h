@@ -543,6 +543,58 @@ enum { MOPTIX_QUERY_CLOSEST = 0, MOPTIX_QUERY_ANY = 1 };
 int moptix_query_rays_device(moptix_context ctx, const float* dRays, int64_t n, int32_t mode, void* dOut);
 int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t mode, void* out);
 
+/* ---- mesh updates and refit ------------------------------------------------- */
+/* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
+ * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
+ * minus the numbers of spheres and quads.  The face count and which vertices a face joins cannot change: that takes moptix_clear_scene.
+ *   moptix_update_faces         pos9: 9 floats per face, p0 p1 p2 (from indexed data: verts[faces]); nrm9: NULL = the normals stay, else 9
+ *                               floats per face, stored only for faces that had normals at upload (which faces have normals does not
+ *                               change).  Materials, texcoords and shadow classes stay.  Host memory; copied before the call returns.
+ *   moptix_update_faces_device  the same from device memory (4-byte aligned), as device-to-device copies enqueued on the context's stream:
+ *                               the caller's buffers must stay valid, and their contents ready, until the stream has run them
+ *                               (moptix_sync).  The values are not inspected.  A later moptix_build_accel first fetches them back into
+ *                               the host staging.  Before moptix_build_accel there is no device copy to write: the call then blocks
+ *                               and copies into the host staging.
+ * MOPTIX_ERR_INVALID: firstFace < 0, nFaces < 0, a range past the last face, null positions (with nFaces > 0), a misaligned device
+ * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
+ * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
+ * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
+ * moptix_query_rays*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * run.  The denoiser entries do not trace and are not affected.
+ *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
+ *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
+ *                               kept), every shading record, every child box of every 128-byte node and every 64-byte node:
+ *                                 scene box     min / max over the faces' boxes; padAbs = 1e-5 * its largest extent + 1e-30
+ *                                 triangle      its box from the three positions, padded as the builder pads (by padAbs + 1e-6 |v|)
+ *                                 leaf child    min / max over its triangles' padded boxes
+ *                                 node child    min / max over the child boxes of that node
+ *                                 64-byte node  the builder's compression of the 128-byte node
+ *                               Unused child slots, references and counts are untouched.  min / max are exact, so the result does not
+ *                               depend on scheduling, and a refit over unchanged positions reproduces the built tree word for word.
+ *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
+ *                               node format is decided again at the next render); a tree built without it does not gain one.
+ *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
+ *                               64-byte form survives), the ray queries' stack overflow area (the tree's depth cannot change), the
+ *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
+ *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
+ *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.
+ *                               moptix_denoise_temporal does not reproject moving triangles: a moved triangle is treated as static
+ *                               and falls to the depth / normal validity tests.
+ *   moptix_get_refit_info       of the last refit on this tree (zeros before the first):
+ *     refitMs       device time of the refit's kernels (HIP events)
+ *     sahCost       the sum over every child slot in use of every node of surface area(child box) x (1 for a node child, the triangle
+ *                   count for a leaf child), divided by the surface area of the union of the root's child boxes, in binary64; 0 for a
+ *                   tree without nodes
+ *     sahCostBuilt  the same for the tree as built (taken at the first refit, before anything is overwritten)
+ *     has64         1 while the tree has its 64-byte form
+ *   sahCost / sahCostBuilt is a SIGNAL of how far the refitted boxes have grown beyond what a rebuild would choose; the library attaches
+ *   no threshold to it. */
+typedef struct { float refitMs; double sahCost, sahCostBuilt; uint32_t has64; } moptix_refit_info;
+int moptix_update_faces(moptix_context ctx, int32_t firstFace, int32_t nFaces, const float* pos9, const float* nrm9);
+int moptix_update_faces_device(moptix_context ctx, int32_t firstFace, int32_t nFaces, const float* dPos9, const float* dNrm9);
+int moptix_refit_accel(moptix_context ctx);
+int moptix_get_refit_info(moptix_context ctx, moptix_refit_info* out);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* device time (HIP events on the launch stream) of the trace kernel -- the dominant kernel --
  * and the number of its launches since the last reset */
@@ -556,6 +608,11 @@ int moptix_debug_read_accel(moptix_context ctx, void* nodes, void* tris, int32_t
 /* the same nodes in the 64-byte form the trace kernels fetch (nNodes*64 B: corner, grid steps, 24 plane bytes, the four
  * child references -- csrc/pt_types.h Node64); node i of this array stands for node i of moptix_debug_read_accel's. */
 int moptix_debug_read_nodes64(moptix_context ctx, void* nodes64);
+/* A test aid, not an interface to build on: the addresses of buffers a call is documented to keep, so that a test can see that it
+ * neither freed nor reallocated them (0 = not allocated).  out[0]: the ray queries' stack overflow area (device); out[1..6]: the refit
+ * plan's device buffers (level order, per-triangle boxes, scene box, cost partials, cost, 64-byte verdict); out[7]: its pinned
+ * read-back record (host).  Touches no device and no stream. */
+int moptix_debug_buffer_addresses(moptix_context ctx, uint64_t out[8]);
 /* nearest-hit query for n rays (BVH-vs-brute-force tests): rays = n x {ox,oy,oz,dx,dy,dz,tmin,tmax};
  * outT[n], outPrim[n] (prim id: spheres, quads, triangles; -1 = miss). */
 int moptix_debug_trace(moptix_context ctx, const float* rays, int32_t n, float* outT, int32_t* outPrim);

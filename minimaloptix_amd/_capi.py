@@ -158,6 +158,14 @@ class Hit(C.Structure):
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 
 
+class RefitInfo(C.Structure):
+    """moptix_refit_info: what moptix_get_refit_info reports."""
+    _fields_ = [("refitMs", C.c_float), ("sahCost", C.c_double), ("sahCostBuilt", C.c_double), ("has64", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(refitMs=float(self.refitMs), sahCost=float(self.sahCost), sahCostBuilt=float(self.sahCostBuilt), has64=int(self.has64))
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -175,6 +183,7 @@ DEVICE_SYMBOLS = [
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
     "moptix_query_rays_device", "moptix_query_rays",
+    "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
     "mohost_last_error", "mohost_scene_build", "mohost_scene_free", "mohost_scene_get_sizes",
@@ -268,6 +277,11 @@ def device_lib():
         L.moptix_adaptive_resolve_rgb8.argtypes = [vp, u8p]
         L.moptix_query_rays_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_rays.argtypes = [vp, f32p, C.c_int64, i32, vp]
+        L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]
+        L.moptix_update_faces_device.argtypes = [vp, i32, i32, vp, vp]
+        L.moptix_refit_accel.argtypes = [vp]
+        L.moptix_get_refit_info.argtypes = [vp, C.POINTER(RefitInfo)]
+        L.moptix_debug_buffer_addresses.argtypes = [vp, C.POINTER(C.c_uint64)]
         _dev = L
     return _dev
 

@@ -550,6 +550,55 @@ class Context:
         ints = out.view(torch.int32)
         return dict(records=out, t=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], ng=out[:, 5:8])
 
+    # ---- mesh updates and refit (include/moptix.h "mesh updates and refit") ----
+    def update_faces(self, first, positions, normals=None):
+        """New positions (and normals) of the faces first .. first + n, numbered in upload order: (n, 3, 3) or (n, 9) float32, p0 p1 p2
+        per face (from indexed data: verts[faces]).  A numpy array goes through the host entry.  A contiguous float32 torch tensor on this
+        context's device is read where it is (moptix_update_faces_device).  On a built scene, refit_accel() or build_accel() must follow
+        before anything traces."""
+        if isinstance(positions, np.ndarray) or not hasattr(positions, "data_ptr"):
+            pos = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 9))
+            nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 9))
+            if nrm is not None and len(nrm) != len(pos):
+                raise ValueError("update_faces: %d faces of positions, %d of normals" % (len(pos), len(nrm)))
+            fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+            self._chk(self._L.moptix_update_faces(self._h, int(first), len(pos), fp(pos), None if nrm is None else fp(nrm)))
+            return
+        import torch
+        for name, t in (("positions", positions), ("normals", normals)):
+            if t is None:
+                continue
+            if not hasattr(t, "data_ptr") or not t.is_cuda:
+                raise ValueError("update_faces: %s must live on the GPU like the positions (pass numpy arrays for the host path)" % name)
+            if str(t.dtype) != "torch.float32":
+                raise ValueError("update_faces: %s has dtype %s" % (name, t.dtype))
+            if t.device.index != self.device:
+                raise ValueError("update_faces: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
+            if not t.is_contiguous() or t.numel() % 9 != 0 or t.numel() != positions.numel():
+                raise ValueError("update_faces: %s must be a contiguous tensor of 9 floats per face" % name)
+        n = positions.numel() // 9
+        torch.cuda.current_stream(positions.device).synchronize()      # the values are ready before the context's stream copies them
+        self._chk(self._L.moptix_update_faces_device(self._h, int(first), n, C.c_void_p(positions.data_ptr() if n else None),
+                                                     C.c_void_p(normals.data_ptr()) if normals is not None and n else None))
+        self.sync()                                                    # the caller may free or overwrite the tensors now
+
+    def refit_accel(self):
+        """Fits the built tree to the updated faces in place (topology kept); blocking.  Returns refit_info()."""
+        self._chk(self._L.moptix_refit_accel(self._h))
+        return self.refit_info()
+
+    def refit_info(self):
+        """dict of the last refit on this tree: refitMs, sahCost, sahCostBuilt (their ratio is the quality signal), has64."""
+        r = K.RefitInfo()
+        self._chk(self._L.moptix_get_refit_info(self._h, C.byref(r)))
+        return r.as_dict()
+
+    def debug_buffer_addresses(self):
+        """A test aid: dict(query_overflow=address, refit_plan=(7 addresses)) of buffers that a refit and a query on a refitted tree keep."""
+        a = (C.c_uint64 * 8)()
+        self._chk(self._L.moptix_debug_buffer_addresses(self._h, a))
+        return dict(query_overflow=int(a[0]), refit_plan=tuple(int(x) for x in a[1:]))
+
     def debug_read_accel(self):
         a = self.accel_info()
         nodes = np.zeros((max(1, a.nNodes), 32), np.uint32)     # Node128 = 32 words

@@ -9,6 +9,7 @@
 #include "../../include/moptix.h"
 #include "lbvh.h"
 #include "megakernel.h"
+#include "refitkernel.h"
 
 struct ncclComm;      // RCCL's communicator (api_comm.hip is the only file that sees RCCL's declarations)
 
@@ -207,6 +208,30 @@ struct moptix_context_t {
     void drop() { overflow.release(); }
     void release() { drop(); rays.release(); out.release(); }
   } query;
+
+  // ---- mesh updates and refit (api_refit.hip) ----
+  // facesDirty: positions changed since the tree was built or refitted (check_ready refuses to trace); hostStale: the device copy of the
+  // faces is ahead of the host staging (moptix_update_faces_device; moptix_build_accel fetches it back first); facesOnDevice: how many
+  // faces moptix_build_accel uploaded -- the first so many of the staging, which moptix_add_mesh may have grown since.
+  // The refit plan belongs to one built tree: the levels of the emitted four-wide tree, the raw boxes by sorted slot and the scratch of the
+  // passes.  Made at the first refit after a build, dropped by moptix_build_accel, moptix_clear_scene and destroy.
+  struct Refit {
+    bool facesDirty = false, hostStale = false;
+    size_t facesOnDevice = 0;
+    bool planned = false;
+    DevBuf<int> levelOrder; std::vector<int> levelFirst;      // pt_refit.h refit_plan_levels
+    DevBuf<pt::RefitBox> raw; DevBuf<uint32_t> sceneBox; DevBuf<double> partials; DevBuf<pt::RefitCost> cost; DevBuf<int> bad;
+    struct Pinned { pt::RefitCost cost; int bad; }* pinned = nullptr;      // where the folded cost and the Node64 verdict come back
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    moptix_refit_info info{};
+    void drop() {
+      levelOrder.release(); levelFirst.clear(); raw.release(); sceneBox.release(); partials.release(); cost.release(); bad.release();
+      if (pinned) (void)hipHostFree(pinned);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+      pinned = nullptr; e0 = nullptr; e1 = nullptr; planned = false; info = moptix_refit_info{};
+    }
+  } refit;
 };
 
 namespace pt {
@@ -218,7 +243,8 @@ int fail(moptix_context c, int code, const std::string& msg);
 int hipFail(moptix_context c, hipError_t e, const char* what);
 #define HIPCHK(c, x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pt::api::hipFail((c), e_, (what)); } while (0)
 
-int check_ready(moptix_context c);                   // params set, tree built, stream alive
+int check_ready(moptix_context c);                   // params set, tree built and fitted to the faces, stream alive
+int fetch_faces(moptix_context c);                   // api_refit.hip: the host staging catches up with device-side face updates
 float* accum_ptr(moptix_context c);
 int ensure_accum(moptix_context c);
 // What a call that uses the device starts with: hipSetDevice, the batch in flight finishes (moptix_sync: timed, watchdog flag read) and,

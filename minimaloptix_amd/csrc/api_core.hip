@@ -78,6 +78,8 @@ int check_ready(moptix_context c) {
   if (c->poisoned) return fail(c, MOPTIX_ERR_COMM, "this context is unusable: kernels of an aborted collective never left its stream");
   if (!c->haveParams) return fail(c, MOPTIX_ERR_STATE, "moptix_set_params has not been called");
   if (!c->accelBuilt) return fail(c, MOPTIX_ERR_STATE, "moptix_build_accel has not been called since the scene changed");
+  if (c->refit.facesDirty)
+    return fail(c, MOPTIX_ERR_STATE, "mesh faces were updated since the tree was fitted: call moptix_refit_accel (keeps the topology) or moptix_build_accel (rebuilds)");
   return MOPTIX_OK;
 }
 
@@ -122,7 +124,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release();
+  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->refit.drop();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -168,11 +170,12 @@ int moptix_clear_scene(moptix_context c) {
   c->faceUV.clear(); c->anyUV = false; c->textures.clear();
   c->sceneDirty = true; c->accelBuilt = false;
   c->tp.drop();                                                // the temporal history belongs to the scene that made it
-  if (c->query.overflow.p && !c->poisoned) {                   // a query in flight still uses what is dropped here
+  if ((c->query.overflow.p || c->refit.planned) && !c->poisoned) {      // a query in flight still uses what is dropped here
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     c->query.drop();
   }
+  c->refit.drop(); c->refit.facesDirty = false; c->refit.hostStale = false; c->refit.facesOnDevice = 0;      // the faces are gone, and the plan with their tree
   return MOPTIX_OK;
 }
 
@@ -299,6 +302,11 @@ int moptix_build_accel(moptix_context c, const char* kind) {
     return fail(c, MOPTIX_ERR_LIMIT, "acceleration structure too large: triangle / node tables must stay below 4 GB (2^28 triangles at most)");
   if ((unsigned long long)c->mats.size() * sizeof(DevMaterial) >= (1ull << 32)) return fail(c, MOPTIX_ERR_LIMIT, "material table must stay below 4 GB");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  if (c->refit.hostStale) {                       // moptix_update_faces_device left the newest positions on the device only
+    const int rc = fetch_faces(c);
+    if (rc != MOPTIX_OK) return rc;
+  }
+  c->refit.drop();                                // the plan describes the tree that is about to go
   if (c->query.overflow.p && !c->poisoned) {      // an asynchronous query in flight still walks the old tree; the area was sized for its depth
     HIPCHK(c, hipStreamSynchronize(c->stream), "sync before the build");
     c->query.drop();
@@ -324,6 +332,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
     HIPCHK(c, c->dFacePos.upload(c->facePos, c->stream), "upload face positions");
     HIPCHK(c, c->dFaceNrm.upload(c->faceNrm, c->stream), "upload face normals");
     HIPCHK(c, c->dFaceHasNrm.upload(c->faceHasNrm, c->stream), "upload face flags");
+    c->refit.facesOnDevice = (size_t)nFaces;
     {
       std::vector<int> words(c->faceMat.size());      // material id + what the face is to a shadow ray (pt_types.h SHADOW_*)
       for (size_t f = 0; f < words.size(); f++) { const DevMaterial& m = c->mats[c->faceMat[f]]; words[f] = face_mat_word(c->faceMat[f], shadow_class(m.kind, m.brdfType)); }
@@ -344,7 +353,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
   }
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync after upload");
   c->formatDecided = false;            // choose_node_format at the next render: it needs the camera
-  c->sceneDirty = false; c->accelBuilt = true;
+  c->sceneDirty = false; c->accelBuilt = true; c->refit.facesDirty = false;
   c->tiles.forget();            // new scene: forget which tiles had deep paths
   return MOPTIX_OK;
 }
