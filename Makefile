@@ -7,6 +7,7 @@
 #   make aovsim     -> tests/aovsim/libaovsim.so                (test infrastructure: CPU mirror of the AOV kernel)
 #   make denoisesim -> tests/denoisesim/libdenoisesim.so        (test infrastructure: CPU mirror of the denoiser kernels)
 #   make temporalsim -> tests/temporalsim/libtemporalsim.so     (test infrastructure: CPU mirror of the temporal-accumulation kernels)
+#   make facemotionsim -> tests/facemotionsim/libfacemotionsim.so (test infrastructure: CPU mirror of moptix_denoise_temporal with per-face motion)
 #   make adaptivesim -> tests/adaptivesim/libadaptivesim.so     (test infrastructure: CPU mirror of the adaptive-sampling kernels and passes)
 #   make querysim   -> tests/querysim/libquerysim.so            (test infrastructure: CPU mirror of the ray-query kernel)
 #   make refitsim   -> tests/refitsim/librefitsim.so            (test infrastructure: CPU mirror of the mesh refit)
@@ -28,7 +29,7 @@ BUILD    ?= build
 HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -fno-slp-vectorize -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -include cstring
 CXXFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -fno-math-errno -mavx2 -mfma -Wall -Wno-unused-function -Wno-unknown-pragmas
 
-DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/refitkernel.hip
+DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/facemotionkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/refitkernel.hip
 DEV_OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(DEV_SRCS))
 DEV_HDRS := $(wildcard $(CSRC)/*.h) include/moptix.h
 HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(HOST)/standin_scenes.cpp $(HOST)/image_read.cpp $(HOST)/jpeg_read.cpp \
@@ -36,7 +37,7 @@ HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(
 HOST_OBJS := $(patsubst $(HOST)/%.cpp,build/host_%.o,$(HOST_SRCS))
 HOST_HDRS := $(wildcard $(HOST)/*.h) $(wildcard $(CSRC)/pt_*.h) include/moptix.h include/moptix_host.h
 
-all: device host oracle hostsim aovsim denoisesim temporalsim adaptivesim querysim refitsim loopback
+all: device host oracle hostsim aovsim denoisesim temporalsim facemotionsim adaptivesim querysim refitsim loopback
 
 device: $(LIBDIR)/$(LIBNAME)
 host: $(LIBDIR)/libmoptix_host.so $(LIBDIR)/moptix_render
@@ -50,6 +51,8 @@ denoisesim:
 	$(MAKE) -C tests/denoisesim -s
 temporalsim:
 	$(MAKE) -C tests/temporalsim -s
+facemotionsim:
+	$(MAKE) -C tests/facemotionsim -s
 adaptivesim:
 	$(MAKE) -C tests/adaptivesim -s
 querysim:
@@ -87,6 +90,6 @@ $(LIBDIR)/moptix_render: $(HOST)/main.cpp $(LIBDIR)/libmoptix_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST)/main.cpp -L$(LIBDIR) -lmoptix_host -lmoptix -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/aovsim/libaovsim.so tests/denoisesim/libdenoisesim.so tests/temporalsim/libtemporalsim.so tests/adaptivesim/libadaptivesim.so tests/querysim/libquerysim.so tests/refitsim/librefitsim.so tests/rccl_loopback/librccl_loopback.so
+	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/aovsim/libaovsim.so tests/denoisesim/libdenoisesim.so tests/temporalsim/libtemporalsim.so tests/facemotionsim/libfacemotionsim.so tests/adaptivesim/libadaptivesim.so tests/querysim/libquerysim.so tests/refitsim/librefitsim.so tests/rccl_loopback/librccl_loopback.so
 
-.PHONY: all device host oracle hostsim aovsim denoisesim temporalsim adaptivesim querysim refitsim loopback clean
+.PHONY: all device host oracle hostsim aovsim denoisesim temporalsim facemotionsim adaptivesim querysim refitsim loopback clean

@@ -390,6 +390,24 @@ int moptix_denoise_bind(moptix_context ctx, float* dstDevice);
  * 2 Object motion.  primId_p < nSpheres (ids are spheres, quads, triangles in upload order): P' = P - (center_now - center_prev) of
  *     that sphere per component, else P' = P.  "prev" centres and camera are those the context held (its host copy of the spheres, the
  *     camera of moptix_set_params) at the end of the previous moptix_denoise_temporal call; moptix_update_spheres is not hooked.
+ *     Triangles, with the option "temporal_face_motion" = 1 (moptix_set_option; 0, the default, leaves a moved triangle to the validity
+ *     tests of step 4 and gives the bits this entry gave before the option existed).  f = primId_p - nSpheres - nQuads is the pixel's
+ *     face (moptix_update_faces' numbering); the case applies when 0 <= f < nTracked, the number of faces on the device for which a
+ *     snapshot exists.  "now" positions p0 p1 p2 of the face: the device copy of the faces as it stands when the call runs, whether or
+ *     not a refit has followed the last update -- so denoise a frame BEFORE updating the faces for the next one.  "prev": what the
+ *     device copy held at the end of the previous moptix_denoise_temporal call made with the option on.  d_i = p_i(now) - p_i(prev)
+ *     per component, one binary32 subtraction each.  All nine components zero: the face has not moved, its motion is (0, 0, 0) and the
+ *     pixel takes the path of a static one (the exact shortcut of step 3 included), so a static mesh gives the same bits with the
+ *     option on.  Otherwise, with e1 = p1 - p0, e2 = p2 - p0, n = cross(e1, e2), nn = dot(n, n), w = P - p0:
+ *       nn > 0:  bu = dot(cross(w, e2), n) / nn,  bv = dot(cross(e1, w), n) / nn, each clamped to [-1, 2] (max, then min);  else bu = bv = 0
+ *       mo = (d0 + bu * (d1 - d0)) + bv * (d2 - d0) per component, in this order;  P' = P - mo
+ *     -- the triangle's own affine motion at the projection of P onto its plane; the clamp bounds the extrapolation at silhouettes,
+ *     where the mean depth and the first sample's primId disagree.  Quads are not reprojected.
+ *     Snapshot life: taken by every call with the option on; dropped by moptix_clear_scene, by a different number of faces on the
+ *     device (faces added, then a rebuild), by setting the option to 0 and by everything that drops the history (step 8).  A call
+ *     without a usable snapshot treats every face as unmoved and takes the snapshot; a changed face count does not drop the history.
+ *     moptix_build_accel over the same number of faces keeps the snapshot: the faces keep their upload order.  The per-face pass runs
+ *     only in a call before which moptix_update_faces*, moptix_build_accel or moptix_clear_scene ran: a static scene pays nothing.
  * 3 Projection into the previous camera (o', LL', H', V').  a = LL' - o', b = H', c = V', r = P' - o'; Cramer's rule on
  *     r = s a + (s u') b + (s v') c with the triple products written as dots with cross(b, c), cross(c, a), cross(a, b) (AC1, AC2):
  *     det = dot(a, cross(b, c)), sn = dot(r, cross(b, c)), s = sn / det; det == 0 or not s > 0 -> no history;
@@ -429,7 +447,12 @@ int moptix_denoise_bind(moptix_context ctx, float* dstDevice);
  *                             the geometry pixels (integer sums reduced on the device)
  *   moptix_temporal_read      of the last call: motion vectors (W*H*2 floats, x then y) and history lengths h (W*H floats), in the
  *                             accumulation buffer's pixel order; NULL members are skipped (MOPTIX_ERR_STATE when there was no call
- *                             since the last frame-size change) */
+ *                             since the last frame-size change)
+ *   moptix_temporal_face_info of the last call: trackedFaces = faces with a usable snapshot in that call (0 with the option off and in
+ *                             a call that only took the snapshot), movedFaces = tracked faces with a non-zero displacement,
+ *                             movedPixels = geometry pixels whose face was a moved one (integer sums reduced on the device); zeros
+ *                             before the first call.  The snapshot, three float4 per face of displacement records and the counters
+ *                             are allocated at the first call that needs them and freed with the snapshot and by moptix_destroy. */
 typedef struct moptix_temporal_params {
   float alpha, alphaMoments, depthTolerance, normalThreshold;
   int32_t maxHistory, varianceFrames;
@@ -444,6 +467,8 @@ int moptix_denoise_temporal(moptix_context ctx, const moptix_denoise_params* p, 
 int moptix_temporal_reset(moptix_context ctx);
 int moptix_temporal_info(moptix_context ctx, moptix_temporal_stats* out);
 int moptix_temporal_read(moptix_context ctx, const moptix_temporal_buffers* dstHost);
+typedef struct { uint64_t trackedFaces, movedFaces, movedPixels; } moptix_temporal_face_stats;
+int moptix_temporal_face_info(moptix_context ctx, moptix_temporal_face_stats* out);
 
 /* ---- adaptive sampling (new): per-pixel sample counts and luminance moments, and a render that stops sampling converged pixels ----
  * moptix_render_adaptive renders a list of seeds like moptix_render, but after a first pass over the whole frame it keeps sampling
@@ -578,8 +603,8 @@ int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t 
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.
- *                               moptix_denoise_temporal does not reproject moving triangles: a moved triangle is treated as static
- *                               and falls to the depth / normal validity tests.
+ *                               moptix_denoise_temporal follows the moved triangles with the option "temporal_face_motion" = 1
+ *                               (step 2 of its contract); by default a moved triangle is treated as static there.
  *   moptix_get_refit_info       of the last refit on this tree (zeros before the first):
  *     refitMs       device time of the refit's kernels (HIP events)
  *     sahCost       the sum over every child slot in use of every node of surface area(child box) x (1 for a node child, the triangle

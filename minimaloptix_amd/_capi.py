@@ -124,6 +124,11 @@ class TemporalStats(C.Structure):
                 ("meanHistory", C.c_float)]
 
 
+class TemporalFaceStats(C.Structure):
+    """moptix_temporal_face_stats: what moptix_temporal_face_info reports."""
+    _fields_ = [("trackedFaces", C.c_uint64), ("movedFaces", C.c_uint64), ("movedPixels", C.c_uint64)]
+
+
 class TemporalBuffers(C.Structure):
     """moptix_temporal_buffers: host pointers for moptix_temporal_read; NULL members are skipped."""
     _fields_ = [("motion", C.c_void_p), ("history", C.c_void_p)]
@@ -180,6 +185,7 @@ DEVICE_SYMBOLS = [
     "moptix_render_aovs", "moptix_aov_clear", "moptix_aov_samples", "moptix_aov_read", "moptix_aov_bind",
     "moptix_denoise_defaults", "moptix_denoise", "moptix_denoise_read", "moptix_denoise_bind",
     "moptix_temporal_defaults", "moptix_denoise_temporal", "moptix_temporal_reset", "moptix_temporal_info", "moptix_temporal_read",
+    "moptix_temporal_face_info",
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
     "moptix_query_rays_device", "moptix_query_rays",
@@ -268,6 +274,7 @@ def device_lib():
         L.moptix_temporal_reset.argtypes = [vp]
         L.moptix_temporal_info.argtypes = [vp, C.POINTER(TemporalStats)]
         L.moptix_temporal_read.argtypes = [vp, C.POINTER(TemporalBuffers)]
+        L.moptix_temporal_face_info.argtypes = [vp, C.POINTER(TemporalFaceStats)]
         L.moptix_adaptive_defaults.argtypes = [C.POINTER(AdaptiveParams)]
         L.moptix_render_adaptive.argtypes = [vp, i32p, i32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
         L.moptix_adaptive_clear.argtypes = [vp]

@@ -419,7 +419,8 @@ class Context:
     def denoise_temporal(self, n_accumulation, temporal=None, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
                          demodulate=False):
         """denoise() with the temporal stage in front: last call's accumulation is reprojected through the AOVs (depth, normal, ids),
-        the camera of set_params and the spheres as update_spheres left them, and blended with this frame.  temporal: a dict with
+        the camera of set_params and the spheres as update_spheres left them (with set_option("temporal_face_motion", 1) also
+        through the motion of the faces that update_faces moved since the last call), and blended with this frame.  temporal: a dict with
         some of temporal_defaults()'s keys (the rest keep their defaults).  Returns an (H, W, 3) float32 array as denoise()."""
         t = self.temporal_defaults()
         for k, v in (temporal or {}).items():
@@ -444,6 +445,13 @@ class Context:
         self._chk(self._L.moptix_temporal_info(self._h, C.byref(s)))
         return dict(frames=int(s.frames), geometry_pixels=int(s.geometryPixels), history_pixels=int(s.historyPixels),
                     disoccluded_pixels=int(s.disoccludedPixels), mean_history=float(s.meanHistory))
+
+    def temporal_face_info(self):
+        """dict of the last denoise_temporal call under set_option("temporal_face_motion", 1): tracked_faces (faces that had a
+        snapshot to compare with), moved_faces, moved_pixels.  Zeros with the option off."""
+        s = K.TemporalFaceStats()
+        self._chk(self._L.moptix_temporal_face_info(self._h, C.byref(s)))
+        return dict(tracked_faces=int(s.trackedFaces), moved_faces=int(s.movedFaces), moved_pixels=int(s.movedPixels))
 
     def temporal_read(self):
         """Of the last denoise_temporal call: dict(motion=(H, W, 2) float32 pixel motion vectors, history=(H, W) float32 lengths)."""

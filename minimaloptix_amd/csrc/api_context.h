@@ -64,6 +64,7 @@ struct Options {
   int drainBelow = 64;            // a workgroup of the packet kernel with this many paths left hands them to the drain kernel (0 = off)
   int auxDepth = 16;              // variant 4: depth from which a path's shadow rays get slots of their own (0 = off)
   int queryBlocksPerCU = 32;      // ray queries (querykernel.hip): the grid's cap in workgroups per CU; beyond it lanes loop over rays
+  int temporalFaceMotion = 0;     // 1 = moptix_denoise_temporal reprojects moved triangles through their own motion (api_temporal.hip)
 };
 
 }}  // namespace pt::api
@@ -174,10 +175,23 @@ struct moptix_context_t {
     uint64_t frames = 0;                       // calls since the last drop
     size_t pixels = 0;                         // frame size of the last call's motion vectors / history lengths (0: none)
     unsigned long long last[4] = { 0, 0, 0, 0 };
-    void drop() { have = false; frames = 0; }
+    // Per-face motion (option "temporal_face_motion", facemotionkernel.hip).  The snapshot holds the device copy of the faces as the
+    // last call with the option on saw it; it goes with the history, with the scene, with a different face count and with the option.
+    struct Faces {
+      DevBuf<float> prev;                      // the snapshot: 9 floats per face
+      DevBuf<pt::v4> rec;                      // three displacement records per face (pt_temporal.h TpFaces)
+      DevBuf<unsigned int> partials;           // moved faces per workgroup of the face pass
+      DevBuf<unsigned long long> counters;     // FaceMotionCounters
+      bool have = false; size_t count = 0;     // a snapshot exists, of so many faces
+      bool changed = true;                     // the faces may differ from the snapshot (moptix_update_faces*, moptix_build_accel, moptix_clear_scene)
+      unsigned long long last[3] = { 0, 0, 0 };       // moptix_temporal_face_info: tracked faces, moved faces, moved pixels of the last call
+      void release() { prev.release(); rec.release(); partials.release(); counters.release(); have = false; count = 0; }
+    } faces;
+    void drop() { have = false; frames = 0; faces.have = false; }
     void release() {
       for (int i = 0; i < 2; i++) { col[i].release(); guide[i].release(); mom[i].release(); }
       motion.release(); motionOut.release(); historyOut.release(); counters.release(); partials.release();
+      faces.release();
       drop(); pixels = 0;
     }
   } tp;

@@ -170,10 +170,12 @@ int moptix_clear_scene(moptix_context c) {
   c->faceUV.clear(); c->anyUV = false; c->textures.clear();
   c->sceneDirty = true; c->accelBuilt = false;
   c->tp.drop();                                                // the temporal history belongs to the scene that made it
-  if ((c->query.overflow.p || c->refit.planned) && !c->poisoned) {      // a query in flight still uses what is dropped here
+  c->tp.faces.changed = true;
+  if ((c->query.overflow.p || c->refit.planned || c->tp.faces.prev.p) && !c->poisoned) {      // a query in flight still uses what is dropped here
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     c->query.drop();
+    c->tp.faces.release();                                     // the face snapshot too
   }
   c->refit.drop(); c->refit.facesDirty = false; c->refit.hostStale = false; c->refit.facesOnDevice = 0;      // the faces are gone, and the plan with their tree
   return MOPTIX_OK;
@@ -354,6 +356,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync after upload");
   c->formatDecided = false;            // choose_node_format at the next render: it needs the camera
   c->sceneDirty = false; c->accelBuilt = true; c->refit.facesDirty = false;
+  c->tp.faces.changed = true;   // the device copy of the faces was uploaded afresh (the snapshot stays: the faces keep their upload order)
   c->tiles.forget();            // new scene: forget which tiles had deep paths
   return MOPTIX_OK;
 }

@@ -9,7 +9,7 @@ using namespace pt::api;
 
 namespace {
 
-enum Invalidates { kNothing, kAccelIfChanged, kNodeFormat, kTileHistory };
+enum Invalidates { kNothing, kAccelIfChanged, kNodeFormat, kTileHistory, kFaceSnapshot };
 // A row with a member is stored: it can be set and read.  A row with `read` is computed from the context and can only be read; a row with
 // neither is an action, it can only be set.  Whatever a row cannot do answers "unknown option", as a name the table does not hold.
 struct Option {
@@ -49,6 +49,7 @@ const Option kOptions[] = {
   { "comm_timeout_ms", &Options::commTimeoutMs, nullptr, 1, INT_MAX, ">= 1" },
   { "comm_blocking", &Options::commBlocking, nullptr, 0, 1, "in {0,1}" },
   { "query_blocks_per_cu", &Options::queryBlocksPerCU, nullptr, 1, 64, "in [1,64]" },
+  { "temporal_face_motion", &Options::temporalFaceMotion, nullptr, 0, 1, "in {0,1}", kFaceSnapshot },      // 0 drops the face snapshot
   { "forget_history", nullptr, nullptr, INT_MIN, INT_MAX, "", kTileHistory },      // the next launch orders its work like a context's first (measurement of a cold frame)
   { "comm_nonblocking_used", nullptr, [](moptix_context c) { return c->comm.nonBlocking ? 1 : 0; } },
   { "node_format_used", nullptr, [](moptix_context c) { return c->nodeFormatUsed; } },
@@ -78,6 +79,12 @@ int moptix_set_option(moptix_context c, const char* name, int32_t value) {
   if (o->invalidates == kAccelIfChanged && value != c->opt.*o->member) c->accelBuilt = false;
   if (o->invalidates == kNodeFormat) c->formatDecided = false;
   if (o->invalidates == kTileHistory) c->tiles.forget();
+  if (o->invalidates == kFaceSnapshot && value == 0 && c->tp.faces.prev.p) {      // the snapshot and its records go with the option
+    (void)hipSetDevice(c->device);
+    if (!c->poisoned) (void)hipStreamSynchronize(c->stream);
+    c->tp.faces.release();
+  }
+  if (o->invalidates == kFaceSnapshot && value == 0) c->tp.faces.have = false;
   if (o->member) c->opt.*o->member = value;
   return MOPTIX_OK;
 }

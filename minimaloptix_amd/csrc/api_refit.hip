@@ -104,7 +104,7 @@ int moptix_update_faces(moptix_context c, int32_t first, int32_t n, const float*
   HIPCHK(c, hipMemcpyAsync(c->dFacePos.p + 9 * (size_t)first, c->facePos.data() + 9 * (size_t)first, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, c->stream), "update face positions");
   if (nrm9) HIPCHK(c, hipMemcpyAsync(c->dFaceNrm.p + 9 * (size_t)first, c->faceNrm.data() + 9 * (size_t)first, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, c->stream), "update face normals");
   HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
-  c->refit.facesDirty = true;
+  c->refit.facesDirty = true; c->tp.faces.changed = true;
   return MOPTIX_OK;
 }
 
@@ -129,7 +129,7 @@ int moptix_update_faces_device(moptix_context c, int32_t first, int32_t n, const
   }
   HIPCHK(c, hipMemcpyAsync(c->dFacePos.p + 9 * (size_t)first, dPos9, bytes, hipMemcpyDeviceToDevice, c->stream), "update face positions");
   if (dNrm9) HIPCHK(c, launch_refit_copy_normals(c->stream, n, dNrm9, c->dFaceHasNrm.p + first, c->dFaceNrm.p + 9 * (size_t)first), "update face normals");
-  c->refit.facesDirty = true; c->refit.hostStale = true;
+  c->refit.facesDirty = true; c->refit.hostStale = true; c->tp.faces.changed = true;
   return MOPTIX_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "api_context.h"
+#include "facemotionkernel.h"
 #include "temporalkernel.h"
 
 using namespace pt;
@@ -54,6 +55,21 @@ int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, co
   HIPCHK(c, s.motion.ensure((size_t)nSpheres), "alloc sphere motion");
   const size_t nGroups = (size_t)((c->params.width + 15) / 16) * ((c->params.height + 15) / 16);
   HIPCHK(c, s.partials.ensure(4 * nGroups), "alloc temporal partials");
+  // Per-face motion: the faces are the device copy as it stands now.  Without a usable snapshot (none yet, another face count) every
+  // face counts as unmoved and the pass only takes the snapshot; with one, the pass runs only where the faces may have changed since.
+  moptix_context_t::Temporal::Faces& fm = s.faces;
+  const bool facesOn = c->opt.temporalFaceMotion != 0;
+  const size_t nFaces = facesOn && c->dFacePos.p && c->dFacePos.n >= 9 * c->refit.facesOnDevice ? c->refit.facesOnDevice : 0;
+  if (!facesOn) fm.have = false;
+  const bool tracked = facesOn && fm.have && fm.count == nFaces;
+  const bool facePass = facesOn && nFaces > 0 && (!tracked || fm.changed);
+  if (facePass) {
+    if (fm.prev.p && fm.count != nFaces) fm.release();          // sized for another scene
+    HIPCHK(c, fm.prev.ensure(9 * nFaces), "alloc face snapshot");
+    HIPCHK(c, fm.rec.ensure(3 * nFaces), "alloc face motion records");
+    HIPCHK(c, fm.partials.ensure((size_t)face_motion_blocks(nFaces)), "alloc face motion partials");
+    HIPCHK(c, fm.counters.ensure(2), "alloc face motion counters");
+  }
 
   TemporalArgs a;
   memset(&a, 0, sizeof(a));
@@ -90,10 +106,27 @@ int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, co
   a.counters = reinterpret_cast<TemporalCounters*>(s.counters.p);
   a.out = denoise_out(c);
   const uint64_t frames = s.frames;
-  s.drop();                                                  // a failure below leaves no half-written history behind
+  s.drop();                                                  // a failure below leaves no half-written history (or face snapshot) behind
+  fm.last[0] = fm.last[1] = fm.last[2] = 0;                  // nor the previous call's face counters
+  const bool faceMotion = facePass && tracked;               // only then can a record say "moved"
+  FaceMotionCounters faceCounts = { 0, 0 };
+  if (facePass) {
+    FaceMotionArgs f;
+    f.now = c->dFacePos.p; f.prev = fm.prev.p; f.rec = fm.rec.p; f.nFaces = (int)nFaces; f.snapshotOnly = tracked ? 0 : 1;
+    f.partials = fm.partials.p;
+    HIPCHK(c, launch_face_motion(c->stream, f), "launch face motion pass");
+  }
+  if (faceMotion) { a.faces.pos = c->dFacePos.p; a.faces.rec = fm.rec.p; a.faces.first = nSpheres + (int)c->quads.size(); a.faces.nTracked = (int)nFaces; }
   HIPCHK(c, launch_temporal(c->stream, a), "launch temporal denoiser");
   HIPCHK(c, hipMemcpyAsync(s.last, s.counters.p, sizeof(s.last), hipMemcpyDeviceToHost, c->stream), "read temporal counters");
+  if (faceMotion) {
+    HIPCHK(c, launch_face_motion_reduce(c->stream, fm.partials.p, face_motion_blocks(nFaces), a.partials, (int)nGroups,
+                                        reinterpret_cast<FaceMotionCounters*>(fm.counters.p)), "launch face motion counters");
+    HIPCHK(c, hipMemcpyAsync(&faceCounts, fm.counters.p, sizeof(faceCounts), hipMemcpyDeviceToHost, c->stream), "read face motion counters");
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream), "temporal denoiser");
+  fm.last[0] = tracked ? nFaces : 0; fm.last[1] = faceCounts.movedFaces; fm.last[2] = faceCounts.movedPixels;
+  if (facesOn) { fm.have = true; fm.count = nFaces; fm.changed = false; }
   s.cur = cur; s.have = true; s.frames = frames + 1;
   s.width = c->params.width; s.height = c->params.height; s.nSpheres = nSpheres; s.demodulate = demodulate;
   s.cam = c->params.cam;
@@ -107,6 +140,20 @@ int moptix_denoise_temporal(moptix_context c, const moptix_denoise_params* p, co
 int moptix_temporal_reset(moptix_context c) {
   if (!c) return fail(c, MOPTIX_ERR_INVALID, "null context");
   c->tp.drop();
+  if (c->tp.faces.prev.p) {                                   // the face snapshot goes with the history
+    (void)hipSetDevice(c->device);
+    if (!c->poisoned) (void)hipStreamSynchronize(c->stream);
+    c->tp.faces.release();
+  }
+  return MOPTIX_OK;
+}
+
+int moptix_temporal_face_info(moptix_context c, moptix_temporal_face_stats* out) {
+  if (!c || !out) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  const moptix_context_t::Temporal& s = c->tp;
+  memset(out, 0, sizeof(*out));
+  if (s.pixels == 0) return MOPTIX_OK;
+  out->trackedFaces = s.faces.last[0]; out->movedFaces = s.faces.last[1]; out->movedPixels = s.faces.last[2];
   return MOPTIX_OK;
 }
 

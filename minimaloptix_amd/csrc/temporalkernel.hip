@@ -29,32 +29,43 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
   return v;                                                     // lane 0 holds the sum
 }
 
-__global__ void __launch_bounds__(kBlockThreads) k_tp_reproject(const TemporalArgs a) {
+// kFaces: the triangle case of the contract's step 2 (option "temporal_face_motion"); false is the kernel without it, and what runs
+// whenever no face can have moved.
+template <bool kFaces> __global__ void __launch_bounds__(kBlockThreads) k_tp_reproject(const TemporalArgs a) {
   int x, y;
   const bool inside = image_pixel(a.k.width, a.k.height, x, y);   // no early return: the whole wave takes part in the reduction
-  bool geometry = false, history = false;
+  bool geometry = false, history = false, movedFace = false;
   unsigned int hlen = 0;
   if (inside) {
     const int p = y * a.k.width + x;
     v4 col, guide, side;
     dn_decode(a.accum, a.albedo, a.normal, a.depth, a.hits, a.nAccumulation, a.nSamples, a.demodulate, p, col, guide, side);
-    const TpResult r = tp_reproject(a.t, a.prevCol, a.prevGuide, a.prevMom, a.motion, x, y, col, guide, a.primId[p], a.matId[p]);
+    const TpResult r = kFaces ? tp_reproject_faces(a.t, a.prevCol, a.prevGuide, a.prevMom, a.motion, a.faces, x, y, col, guide, a.primId[p], a.matId[p])
+                              : tp_reproject(a.t, a.prevCol, a.prevGuide, a.prevMom, a.motion, x, y, col, guide, a.primId[p], a.matId[p]);
     a.colA[p] = r.col; a.side[p] = side;
     a.histCol[p] = r.hist; a.histGuide[p] = guide; a.histMom[p] = r.mom;
     a.motionOut[2 * (size_t)p] = r.mvx; a.motionOut[2 * (size_t)p + 1] = r.mvy;
     a.historyOut[p] = r.hist.w;
-    geometry = r.geometry; history = r.history;
+    geometry = r.geometry; history = r.history; movedFace = r.movedFace;
     hlen = geometry ? (unsigned int)r.hist.w : 0u;
   }
   const unsigned int nGeo = __popcll(__ballot(geometry)), nHist = __popcll(__ballot(history));
   const unsigned int sumH = wave_sum(hlen);
-  __shared__ unsigned int part[kBlockThreads / 64][3];
+  unsigned int nMoved = 0;
+  if constexpr (kFaces) nMoved = __popcll(__ballot(movedFace));
+  __shared__ unsigned int part[kBlockThreads / 64][kFaces ? 4 : 3];
   const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { part[wave][0] = nGeo; part[wave][1] = nHist; part[wave][2] = sumH; }
+  if ((threadIdx.x & 63) == 0) {
+    part[wave][0] = nGeo; part[wave][1] = nHist; part[wave][2] = sumH;
+    if constexpr (kFaces) part[wave][3] = nMoved;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     uint4 r = make_uint4(0u, 0u, 0u, 0u);
-    for (int w = 0; w < kBlockThreads / 64; w++) { r.x += part[w][0]; r.y += part[w][1]; r.z += part[w][2]; }
+    for (int w = 0; w < kBlockThreads / 64; w++) {
+      r.x += part[w][0]; r.y += part[w][1]; r.z += part[w][2];
+      if constexpr (kFaces) r.w += part[w][3];
+    }
     a.partials[blockIdx.y * gridDim.x + blockIdx.x] = r;       // at most 256 pixels x maxHistory 65536 = 2^24 per workgroup
   }
 }
@@ -79,7 +90,8 @@ __global__ void __launch_bounds__(kBlockThreads) k_tp_reduce(const uint4* __rest
 
 hipError_t launch_temporal(hipStream_t stream, const TemporalArgs& a) {
   const dim3 grid = image_grid(a.k.width, a.k.height);
-  k_tp_reproject<<<grid, kBlockThreads, 0, stream>>>(a);
+  if (a.faces.nTracked > 0) k_tp_reproject<true><<<grid, kBlockThreads, 0, stream>>>(a);
+  else k_tp_reproject<false><<<grid, kBlockThreads, 0, stream>>>(a);
   k_tp_reduce<<<1, kBlockThreads, 0, stream>>>(a.partials, (int)(grid.x * grid.y), a.counters);
   return launch_atrous(stream, a.k, a.colA, a.colB, a.histGuide, a.side, a.iterations, true, a.out);
 }
