@@ -3,14 +3,7 @@
 #   make device     -> minimaloptix_amd/lib/libmoptix.so        (hipcc --offload-arch=gfx950)
 #   make host       -> minimaloptix_amd/lib/libmoptix_host.so, minimaloptix_amd/lib/moptix_render
 #   make oracle     -> oracle/liboracle.so                      (test infrastructure)
-#   make hostsim    -> tests/hostsim/libhostsim.so              (test infrastructure)
-#   make aovsim     -> tests/aovsim/libaovsim.so                (test infrastructure: CPU mirror of the AOV kernel)
-#   make denoisesim -> tests/denoisesim/libdenoisesim.so        (test infrastructure: CPU mirror of the denoiser kernels)
-#   make temporalsim -> tests/temporalsim/libtemporalsim.so     (test infrastructure: CPU mirror of the temporal-accumulation kernels)
-#   make facemotionsim -> tests/facemotionsim/libfacemotionsim.so (test infrastructure: CPU mirror of moptix_denoise_temporal with per-face motion)
-#   make adaptivesim -> tests/adaptivesim/libadaptivesim.so     (test infrastructure: CPU mirror of the adaptive-sampling kernels and passes)
-#   make querysim   -> tests/querysim/libquerysim.so            (test infrastructure: CPU mirror of the ray-query kernel)
-#   make refitsim   -> tests/refitsim/librefitsim.so            (test infrastructure: CPU mirror of the mesh refit)
+#   make hostsim    -> tests/hostsim/libhostsim.so              (test infrastructure: the CPU mirrors of the kernels, one library)
 #   make loopback   -> tests/rccl_loopback/librccl_loopback.so  (test infrastructure: N ranks on one GPU without RCCL)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -37,7 +30,7 @@ HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(
 HOST_OBJS := $(patsubst $(HOST)/%.cpp,build/host_%.o,$(HOST_SRCS))
 HOST_HDRS := $(wildcard $(HOST)/*.h) $(wildcard $(CSRC)/pt_*.h) include/moptix.h include/moptix_host.h
 
-all: device host oracle hostsim aovsim denoisesim temporalsim facemotionsim adaptivesim querysim refitsim loopback
+all: device host oracle hostsim loopback
 
 device: $(LIBDIR)/$(LIBNAME)
 host: $(LIBDIR)/libmoptix_host.so $(LIBDIR)/moptix_render
@@ -45,20 +38,6 @@ oracle:
 	$(MAKE) -C oracle -s
 hostsim:
 	$(MAKE) -C tests/hostsim -s
-aovsim:
-	$(MAKE) -C tests/aovsim -s
-denoisesim:
-	$(MAKE) -C tests/denoisesim -s
-temporalsim:
-	$(MAKE) -C tests/temporalsim -s
-facemotionsim:
-	$(MAKE) -C tests/facemotionsim -s
-adaptivesim:
-	$(MAKE) -C tests/adaptivesim -s
-querysim:
-	$(MAKE) -C tests/querysim -s
-refitsim:
-	$(MAKE) -C tests/refitsim -s
 loopback:
 	$(MAKE) -C tests/rccl_loopback -s
 
@@ -90,6 +69,6 @@ $(LIBDIR)/moptix_render: $(HOST)/main.cpp $(LIBDIR)/libmoptix_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST)/main.cpp -L$(LIBDIR) -lmoptix_host -lmoptix -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/aovsim/libaovsim.so tests/denoisesim/libdenoisesim.so tests/temporalsim/libtemporalsim.so tests/facemotionsim/libfacemotionsim.so tests/adaptivesim/libadaptivesim.so tests/querysim/libquerysim.so tests/refitsim/librefitsim.so tests/rccl_loopback/librccl_loopback.so
+	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/rccl_loopback/librccl_loopback.so
 
-.PHONY: all device host oracle hostsim aovsim denoisesim temporalsim facemotionsim adaptivesim querysim refitsim loopback clean
+.PHONY: all device host oracle hostsim loopback clean

@@ -1,36 +1,12 @@
-"""Bindings of tests/adaptivesim (the CPU mirror of moptix_render_adaptive) and helpers for the adaptive-sampling tests."""
+"""The adaptive sampling of the CPU mirror (tests/hostsim/adaptivesim.cpp) and helpers for the adaptive-sampling tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from common import REPO, K, hostsim_render
-
-_DIR = os.path.join(REPO, "tests", "adaptivesim")
-_lib = None
+from common import K, _ptr, hostsim_handle, hostsim_lib, hostsim_render
 
 ADAPTIVE_DEFAULTS = dict(threshold=0.03, min_samples=16, batch=64)
 STATS_KEYS = ("passes", "samples_traced", "samples_uniform", "active_pixels_last", "converged_pixels", "min_count", "max_count")
-
-
-def adaptivesim_lib():
-    global _lib
-    if _lib is None:
-        path = os.path.join(_DIR, "libadaptivesim.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _DIR, "-s"])
-        L = C.CDLL(path)
-        f32p, u32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
-        L.adaptivesim_create.restype = C.c_void_p
-        L.adaptivesim_destroy.argtypes = [C.c_void_p]
-        L.adaptivesim_clear.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.adaptivesim_check_params.argtypes = [C.POINTER(K.AdaptiveParams)]
-        L.adaptivesim_render.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, C.c_int, C.POINTER(K.AdaptiveParams), C.POINTER(K.AdaptiveStats)]
-        L.adaptivesim_read.argtypes = [C.c_void_p, f32p, u32p, f32p, f32p, u8p]
-        L.adaptivesim_mean.argtypes = [C.c_void_p, f32p, u8p]
-        _lib = L
-    return _lib
 
 
 def adaptive_params(threshold=None, min_samples=None, batch=None):
@@ -42,11 +18,7 @@ def adaptive_params(threshold=None, min_samples=None, batch=None):
 def check_params(threshold, min_samples, batch):
     """The argument check of moptix_render_adaptive, as the mirror carries it: MOPTIX_OK or ERR_INVALID."""
     p = K.AdaptiveParams(float(threshold), int(min_samples), int(batch))
-    return adaptivesim_lib().adaptivesim_check_params(C.byref(p))
-
-
-def _ptr(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+    return hostsim_lib().adaptivesim_check_params(C.byref(p))
 
 
 class AdaptiveSim:
@@ -54,24 +26,24 @@ class AdaptiveSim:
     clear() is adaptive_clear, read() is accum_read + adaptive_read."""
 
     def __init__(self, width, height):
-        self._h = C.c_void_p(adaptivesim_lib().adaptivesim_create())
+        self._h = C.c_void_p(hostsim_lib().adaptivesim_create())
         self.width, self.height = int(width), int(height)
         self.clear()
 
     def __del__(self):
         if getattr(self, "_h", None):
-            adaptivesim_lib().adaptivesim_destroy(self._h)
+            hostsim_lib().adaptivesim_destroy(self._h)
             self._h = None
 
     def clear(self):
-        adaptivesim_lib().adaptivesim_clear(self._h, self.width, self.height)
+        hostsim_lib().adaptivesim_clear(self._h, self.width, self.height)
 
     def render(self, samples, threshold=None, min_samples=None, batch=None):
         """samples: (nSeeds, H, W, 3) float32, the image each seed adds to a zero accumulator.  Returns the stats dict."""
         samples = np.ascontiguousarray(samples, np.float32).reshape(-1, self.height, self.width, 3)
         p = adaptive_params(threshold, min_samples, batch)
         st = K.AdaptiveStats()
-        rc = adaptivesim_lib().adaptivesim_render(self._h, self.width, self.height, _ptr(samples), len(samples), C.byref(p), C.byref(st))
+        rc = hostsim_lib().adaptivesim_render(self._h, self.width, self.height, _ptr(samples), len(samples), C.byref(p), C.byref(st))
         assert rc == 0, rc
         return st.as_dict()
 
@@ -79,19 +51,20 @@ class AdaptiveSim:
         h, w = self.height, self.width
         out = dict(accum=np.empty((h, w, 3), np.float32), count=np.empty((h, w), np.uint32), moments=np.empty((h, w, 2), np.float32),
                    error=np.empty((h, w), np.float32), converged=np.empty((h, w), np.uint8))
-        adaptivesim_lib().adaptivesim_read(self._h, _ptr(out["accum"]), _ptr(out["count"], C.c_uint32), _ptr(out["moments"]), _ptr(out["error"]),
+        hostsim_lib().adaptivesim_read(self._h, _ptr(out["accum"]), _ptr(out["count"], C.c_uint32), _ptr(out["moments"]), _ptr(out["error"]),
                                            _ptr(out["converged"], C.c_uint8))
         return out
 
     def mean(self):
         m = np.empty((self.height, self.width, 3), np.float32); rgb8 = np.empty((self.height, self.width, 3), np.uint8)
-        adaptivesim_lib().adaptivesim_mean(self._h, _ptr(m), _ptr(rgb8, C.c_uint8))
+        hostsim_lib().adaptivesim_mean(self._h, _ptr(m), _ptr(rgb8, C.c_uint8))
         return m, rgb8
 
 
 def hostsim_samples(hs, seeds):
     """(nSeeds, H, W, 3): hostsim_render with one seed at a time into a zero accumulator -- that IS the clamped sample."""
-    return np.stack([hostsim_render(hs, [int(s)])[0] for s in seeds])
+    sim = hostsim_handle(hs)                                 # the tree is built once, not once per seed
+    return np.stack([hostsim_render(sim, [int(s)])[0] for s in seeds])
 
 
 def sequential_sums(samples):

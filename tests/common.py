@@ -17,6 +17,8 @@ from oracle import oracle as O                   # noqa: E402
 _HOSTSIM_DIR = os.path.join(REPO, "tests", "hostsim")
 _hostsim = None
 
+AOV_NAMES = ("albedo", "normal", "depth", "hits", "primId", "matId")
+
 
 class HostsimScene(C.Structure):
     _fields_ = [("params", K.Params),
@@ -35,20 +37,70 @@ class HostsimBvhOut(C.Structure):
                 ("nNodes", C.c_int32), ("rootRef", C.c_int32), ("depth", C.c_int32), ("nodes64", C.c_void_p)]
 
 
+class AovsimBuffers(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in AOV_NAMES] + [("samples", C.c_uint64)]
+
+
+class RefitsimOut(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("nodes64", C.c_void_p), ("tris", C.c_void_p), ("shade", C.c_void_p),
+                ("nNodes", C.c_int32), ("rootRef", C.c_int32), ("has64", C.c_int32), ("sahCost", C.c_double), ("sahCostBuilt", C.c_double)]
+
+
 def hostsim_lib():
+    """tests/hostsim/libhostsim.so, every CPU mirror in one library: the only loader, and every signature in one place."""
     global _hostsim
     if _hostsim is None:
         path = os.environ.get("HOSTSIM_LIB", os.path.join(_HOSTSIM_DIR, "libhostsim.so"))
         if not os.path.exists(path):
             subprocess.check_call(["make", "-C", _HOSTSIM_DIR, "-s"])
         L = C.CDLL(path)
-        L.hostsim_render.argtypes = [C.POINTER(HostsimScene), C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                     C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
-        L.hostsim_render_timed.argtypes = [C.POINTER(HostsimScene), C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                           C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
-        L.hostsim_build_bvh.argtypes = [C.POINTER(HostsimScene), C.c_int, C.POINTER(HostsimBvhOut)]
+        vp, f32p, i32p, u64p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+
+        def sig(name, argtypes, restype=C.c_int):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes, restype
+        # the built scene: a handle, and what traces on it (hostsim.cpp, aovsim.cpp, querysim.cpp, refitsim.cpp)
+        sig("hostsim_create", [C.POINTER(HostsimScene), C.c_int, C.c_int], vp)
+        sig("hostsim_free", [vp], None)
+        sig("hostsim_read_bvh", [vp, C.POINTER(HostsimBvhOut)])
+        sig("hostsim_debug_ray", [vp, f32p, f32p, C.c_float, C.c_int])
+        sig("hostsim_render", [vp, C.c_int, C.c_int, i32p, C.c_int, f32p, u64p, C.POINTER(C.c_double)])
+        sig("aovsim_render_aovs", [vp, C.c_int, i32p, C.c_int, C.POINTER(AovsimBuffers)])
+        sig("aovsim_camera_rays", [C.POINTER(HostsimScene), C.c_int32, f32p])
+        sig("querysim_query", [vp, C.c_int, f32p, C.c_int64, C.c_int, vp])
+        sig("refitsim_update", [vp, C.c_int32, C.c_int32, f32p, f32p])
+        sig("refitsim_refit", [vp])
+        sig("refitsim_read", [vp, C.POINTER(RefitsimOut)])
+        # the image-space mirrors (denoisesim.cpp, temporalsim.cpp, adaptivesim.cpp)
+        sig("denoisesim_run", [C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_float, C.POINTER(K.DenoiseParams), f32p])
+        sig("denoisesim_exp_ac", [f32p, f32p, C.c_int], None)
+        sig("denoisesim_pow_int", [f32p, C.c_int, f32p, C.c_int], None)
+        sig("temporalsim_create", [], vp)
+        for name in ("destroy", "reset", "clear_scene", "faces_changed"):
+            sig("temporalsim_" + name, [vp], None)
+        sig("temporalsim_set_option", [vp, C.c_int], None)
+        sig("temporalsim_frames", [vp], C.c_uint64)
+        sig("temporalsim_run", [vp, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, i32p, i32p, C.c_float, C.c_float, C.POINTER(K.CamParams),
+                                f32p, C.c_int, f32p, C.c_int, C.c_int, C.POINTER(K.DenoiseParams), C.POINTER(K.TemporalParams),
+                                f32p, f32p, f32p, f32p, u64p, u64p])
+        sig("adaptivesim_create", [], vp)
+        sig("adaptivesim_destroy", [vp], None)
+        sig("adaptivesim_clear", [vp, C.c_int, C.c_int], None)
+        sig("adaptivesim_check_params", [C.POINTER(K.AdaptiveParams)])
+        sig("adaptivesim_render", [vp, C.c_int, C.c_int, f32p, C.c_int, C.POINTER(K.AdaptiveParams), C.POINTER(K.AdaptiveStats)])
+        sig("adaptivesim_read", [vp, f32p, u32p, f32p, f32p, u8p], None)
+        sig("adaptivesim_mean", [vp, f32p, u8p], None)
         _hostsim = L
     return _hostsim
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _ptr(a, t=C.c_float):
+    return a.ctypes.data_as(C.POINTER(t))
 
 
 def _hostsim_scene(hs):
@@ -80,18 +132,38 @@ HOSTSIM_COUNTERS = ("samples", "primaryRays", "bounceRays", "shadowRays", "nodeF
                     "lightLoads", "analyticTests")
 
 
-def hostsim_render(hs, seeds, leaf_size=4, accum=None, node_format=128):
-    """node_format 64: the CPU build walks the 64-byte nodes (pt_types.h Node64), as the packet kernel does by default."""
-    hostsim_lib().hostsim_set_node_format(int(node_format))
-    s, keep = _hostsim_scene(hs)
+class HostsimHandle:
+    """A scene built by the mirror's builder (hostsim_create copies what it needs): what the render, the AOV render, the queries, the
+    BVH read-out and the refit run on.  builder: 0 = Morton radix tree, 1 = binned SAH (the device default; moptix option "builder")."""
+
+    def __init__(self, hs, leaf_size=4, builder=1):
+        s, keep = _hostsim_scene(hs)
+        self.width, self.height, self.n_faces = hs.width, hs.height, int(s.nFaces)
+        self._h = C.c_void_p(hostsim_lib().hostsim_create(C.byref(s), int(leaf_size), int(builder)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            hostsim_lib().hostsim_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def hostsim_handle(hs, leaf_size=4, builder=1):
+    """`hs` itself where it is a built scene already (leaf_size and builder were given when it was built), else one built from it."""
+    return hs if isinstance(hs, HostsimHandle) else HostsimHandle(hs, leaf_size, builder)
+
+
+def hostsim_render(hs, seeds, leaf_size=4, accum=None, node_format=128, builder=1, packet=0):
+    """node_format 64: the CPU build walks the 64-byte nodes (pt_types.h Node64), as the packet kernel does by default.
+    packet 1: the per-bounce state machine of pt_packet.h (kernel variant 4) instead of the per-ray one."""
+    sim = hostsim_handle(hs, leaf_size, builder)
     seeds = np.ascontiguousarray(np.asarray(seeds, np.int32))
     if accum is None:
-        accum = np.zeros((hs.height, hs.width, 3), np.float32)
+        accum = np.zeros((sim.height, sim.width, 3), np.float32)
     cnt = (C.c_uint64 * 9)()
     timing = (C.c_double * 3)()
-    rc = hostsim_lib().hostsim_render_timed(C.byref(s), leaf_size, seeds.ctypes.data_as(C.POINTER(C.c_int32)), len(seeds),
-                                            accum.ctypes.data_as(C.POINTER(C.c_float)), cnt, timing)
-    hostsim_lib().hostsim_set_node_format(128)
+    rc = hostsim_lib().hostsim_render(sim._h, int(node_format), int(packet), _ptr(seeds, C.c_int32), len(seeds), _ptr(accum), cnt, timing)
     assert rc == 0
     out = dict(zip(HOSTSIM_COUNTERS, [int(x) for x in cnt]))
     out.update(build_s=timing[0], render_s=timing[1], threads=int(timing[2]))
@@ -112,20 +184,88 @@ def node64_boxes(n64):
 
 def hostsim_bvh(hs, leaf_size=4, builder=1, want_nodes64=False):
     """builder: 0 = Morton radix tree, 1 = binned SAH (the device default; moptix option "builder")."""
-    hostsim_lib().hostsim_set_builder(int(builder))
-    s, keep = _hostsim_scene(hs)
-    nf = max(1, s.nFaces)
+    sim = hostsim_handle(hs, leaf_size, builder)
+    nf = max(1, sim.n_faces)
     nodes = np.zeros((nf, 32), np.uint32); tris = np.zeros((nf, 12), np.uint32); prim = np.zeros(nf, np.int32)
     out = HostsimBvhOut()
-    out.nodes, out.tris, out.triPrim = nodes.ctypes.data, tris.ctypes.data, prim.ctypes.data_as(C.POINTER(C.c_int32))
+    out.nodes, out.tris, out.triPrim = nodes.ctypes.data, tris.ctypes.data, _ptr(prim, C.c_int32)
     n64 = np.zeros((nf, 16), np.uint32)
     out.nodes64 = n64.ctypes.data if want_nodes64 else None
-    rc = hostsim_lib().hostsim_build_bvh(C.byref(s), leaf_size, C.byref(out))
-    hostsim_lib().hostsim_set_builder(1)
-    assert rc == 0
+    assert hostsim_lib().hostsim_read_bvh(sim._h, C.byref(out)) == 0
     if want_nodes64:
-        return nodes[:out.nNodes], tris[:s.nFaces], prim[:s.nFaces], out.rootRef, out.depth, n64[:out.nNodes]
-    return nodes[:out.nNodes], tris[:s.nFaces], prim[:s.nFaces], out.rootRef, out.depth
+        return nodes[:out.nNodes], tris[:sim.n_faces], prim[:sim.n_faces], out.rootRef, out.depth, n64[:out.nNodes]
+    return nodes[:out.nNodes], tris[:sim.n_faces], prim[:sim.n_faces], out.rootRef, out.depth
+
+
+class MovedScene:
+    """hs with other face positions, other spheres and / or other params (another camera): what the oracle, the CPU mirrors and a
+    context's upload see of a HostScene, over a copy of its flat arrays.
+    The faces carry the move (one vertex per corner), so a move of a face range may tear vertices apart that faces share, exactly as
+    moptix_update_faces on that range does.  face_nrm: other normals too ([nFaces, 9]; a face without normals keeps none, as
+    moptix_update_faces leaves it).  drop_normals: a mask of faces that lose their normals (they shade flat).  new_faces: other faces altogether (no normals, no texcoords, material 0)."""
+
+    def __init__(self, hs, face_pos=None, new_faces=False, face_nrm=None, drop_normals=None, spheres=None, params=None):
+        self._base = hs
+        self.kind, self.sizes, self.accel = hs.kind, hs.sizes, hs.accel
+        self.params = hs.params if params is None else params
+        self.aabb_min, self.aabb_max = hs.aabb_min, hs.aabb_max
+        f = dict(hs.flat())
+        if spheres is not None:
+            f["spheres"] = spheres
+        nf = len(f["vIdx"])
+        if face_pos is not None:
+            face_pos = np.ascontiguousarray(np.asarray(face_pos, np.float32).reshape(-1, 9))
+            nf = len(face_pos)
+            f["positions"] = np.ascontiguousarray(face_pos.reshape(-1, 3))      # one vertex per corner
+            f["vIdx"] = np.arange(3 * nf, dtype=np.int32).reshape(nf, 3)
+        if drop_normals is not None:
+            f["nIdx"] = np.where(np.asarray(drop_normals, bool)[:, None], np.int32(-1), f["nIdx"]).astype(np.int32)
+        if face_nrm is not None:
+            has = (np.asarray(f["nIdx"]) >= 0).all(axis=1)
+            f["normals"] = np.ascontiguousarray(np.asarray(face_nrm, np.float32).reshape(-1, 3))      # one normal per corner
+            f["nIdx"] = np.where(has[:, None], np.arange(3 * nf, dtype=np.int32).reshape(nf, 3), np.int32(-1)).astype(np.int32)
+        if new_faces:
+            f["nIdx"] = np.full((nf, 3), -1, np.int32); f["tIdx"] = np.full((nf, 3), -1, np.int32); f["faceMat"] = np.zeros(nf, np.int32)
+        self._flat = f
+
+    width = property(lambda self: int(self.params.width))
+    height = property(lambda self: int(self.params.height))
+
+    def flat(self):
+        return self._flat
+
+    to_dict = M.HostScene.to_dict
+    face_arrays = M.HostScene.face_arrays
+    face_uvs = M.HostScene.face_uvs
+
+    def upload(self, ctx):
+        """mohost_scene_upload's sequence of calls (host/scenes.cpp upload) from the flat arrays: one moptix_add_mesh per run of faces
+        with one material, which numbers the faces as the original upload does."""
+        L, h, f, s = K.device_lib(), ctx._h, self._flat, self.sizes
+        chk = ctx._chk
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        chk(L.moptix_clear_scene(h)); chk(L.moptix_set_params(h, C.byref(self.params)))
+        for t in f["textures"]:
+            t = np.ascontiguousarray(t, np.float32)
+            chk(L.moptix_add_texture(h, fp(t), t.shape[1], t.shape[0], None))
+        for i in range(s.nMaterials):
+            chk(L.moptix_add_material(h, C.byref(f["materials"][i]), None))
+        if s.nSpheres:
+            chk(L.moptix_add_spheres(h, f["spheres"], ip(np.ascontiguousarray(f["sphereMat"], np.int32)), s.nSpheres))
+        if s.nQuads:
+            chk(L.moptix_add_quads(h, f["quads"], ip(np.ascontiguousarray(f["quadMat"], np.int32)), s.nQuads))
+        pos = np.ascontiguousarray(f["positions"], np.float32); nrm = np.ascontiguousarray(f["normals"], np.float32)
+        uv = np.ascontiguousarray(f["texcoords"], np.float32)
+        fm = np.asarray(f["faceMat"], np.int32)
+        cuts = [0] + [i for i in range(1, len(fm)) if fm[i] != fm[i - 1]] + [len(fm)] if len(fm) else [0]
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            vi = np.ascontiguousarray(f["vIdx"][a:b], np.int32); ni = np.ascontiguousarray(f["nIdx"][a:b], np.int32)
+            ti = np.ascontiguousarray(f["tIdx"][a:b], np.int32)
+            chk(L.moptix_add_mesh(h, fp(pos), len(pos), fp(nrm) if len(nrm) else None, len(nrm), fp(uv) if len(uv) else None, len(uv),
+                                  ip(vi), ip(ni), ip(ti), b - a, int(fm[a])))
+        chk(L.moptix_set_lights(h, f["lights"] if s.nLights else None, s.nLights))
+        chk(L.moptix_build_accel(h, self.accel.encode()))
 
 
 def oracle_scene(hs, brute_force_tris=False):

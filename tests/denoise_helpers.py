@@ -1,39 +1,11 @@
-"""Bindings of tests/denoisesim (the CPU mirror of the denoiser kernels) for the denoiser tests."""
+"""The denoiser of the CPU mirror (tests/hostsim/denoisesim.cpp) for the denoiser tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from common import REPO, K
-
-_DENOISESIM_DIR = os.path.join(REPO, "tests", "denoisesim")
-_denoisesim = None
+from common import K, _f32, _ptr, hostsim_lib
 
 DEFAULTS = dict(iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0, demodulate=False)
-
-
-def denoisesim_lib():
-    global _denoisesim
-    if _denoisesim is None:
-        path = os.path.join(_DENOISESIM_DIR, "libdenoisesim.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _DENOISESIM_DIR, "-s"])
-        L = C.CDLL(path)
-        f32p = C.POINTER(C.c_float)
-        L.denoisesim_run.argtypes = [C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_float, C.POINTER(K.DenoiseParams), f32p]
-        L.denoisesim_exp_ac.argtypes = [f32p, f32p, C.c_int]
-        L.denoisesim_pow_int.argtypes = [f32p, C.c_int, f32p, C.c_int]
-        _denoisesim = L
-    return _denoisesim
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, np.float32)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def denoisesim(accum, aovs, n_accumulation, n_samples, iterations=5, normal_power=128, sigma_luminance=4.0, sigma_depth=1.0,
@@ -46,7 +18,7 @@ def denoisesim(accum, aovs, n_accumulation, n_samples, iterations=5, normal_powe
     assert ins[0].size == ins[1].size == 3 * h * w and ins[2].size == ins[3].size == h * w
     out = np.empty((h, w, 3), np.float32)
     p = K.DenoiseParams(int(iterations), int(normal_power), 1 if demodulate else 0, float(sigma_luminance), float(sigma_depth))
-    rc = denoisesim_lib().denoisesim_run(w, h, _ptr(accum), *[_ptr(a) for a in ins], float(n_accumulation), float(n_samples), C.byref(p), _ptr(out))
+    rc = hostsim_lib().denoisesim_run(w, h, _ptr(accum), *[_ptr(a) for a in ins], float(n_accumulation), float(n_samples), C.byref(p), _ptr(out))
     assert rc == 0
     return out
 
@@ -54,14 +26,14 @@ def denoisesim(accum, aovs, n_accumulation, n_samples, iterations=5, normal_powe
 def exp_ac(x):
     x = _f32(x).reshape(-1)
     y = np.empty_like(x)
-    denoisesim_lib().denoisesim_exp_ac(_ptr(x), _ptr(y), len(x))
+    hostsim_lib().denoisesim_exp_ac(_ptr(x), _ptr(y), len(x))
     return y
 
 
 def pow_int(x, e):
     x = _f32(x).reshape(-1)
     y = np.empty_like(x)
-    denoisesim_lib().denoisesim_pow_int(_ptr(x), int(e), _ptr(y), len(x))
+    hostsim_lib().denoisesim_pow_int(_ptr(x), int(e), _ptr(y), len(x))
     return y
 
 

@@ -1,9 +1,12 @@
 // aovsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the AOV kernel (minimaloptix_amd/csrc/aovkernel.hip): the same per-pixel
 // code (pt_aov.h over pt_path.h's camera ray and traversal), compiled for the host and run one pixel at a time, on the scene and
-// tree that tests/hostsim builds (its source is included unchanged).  The GPU tests compare the kernel's buffers with these bit
-// for bit.  It is not part of the product: nothing under minimaloptix_amd/ builds or loads it.
-#include "../hostsim/hostsim.cpp"
+// tree of a hostsim_create handle (hostsim.h).  The GPU tests compare the kernel's buffers with these bit for bit.  It is not part
+// of the product: nothing under minimaloptix_amd/ builds or loads it.
+#include <cstring>
+#include "hostsim.h"
 #include "../../minimaloptix_amd/csrc/pt_aov.h"
+
+using namespace hostsim;
 
 extern "C" {
 
@@ -46,13 +49,11 @@ void aov_pixel(const SceneView& sc, int pix, const int32_t* seeds, int n, bool w
 
 extern "C" {
 
-// moptix_render_aovs on the CPU: adds one sample per seed to every pixel of the whole frame.  nodeFormat 64 walks the 64-byte
-// nodes where the tree has them (as the kernel does by default), 128 the 128-byte ones.
-int aovsim_render_aovs(const hostsim_scene* s, int leafSize, int nodeFormat, const int32_t* seeds, int n, aovsim_buffers* b) {
-  if (!s || !b || n < 0 || (n > 0 && !seeds)) return -1;
-  HostScene hs; make_scene(*s, leafSize, hs);
-  const SceneView& sc = hs.view;
-  const bool n64 = nodeFormat == 64 && sc.nodes64 != nullptr;
+// moptix_render_aovs on the CPU: adds one sample per seed to every pixel of the whole frame.
+int aovsim_render_aovs(void* h, int nodeFormat, const int32_t* seeds, int n, aovsim_buffers* b) {
+  if (!h || !b || n < 0 || (n > 0 && !seeds)) return -1;
+  const SceneView& sc = static_cast<HostSim*>(h)->hs.view;
+  const bool n64 = walks_node64(sc, nodeFormat);
   const bool writeIds = b->samples == 0;
   const int nPix = sc.width * sc.height;
 #pragma omp parallel for schedule(dynamic, 64)

@@ -13,46 +13,12 @@
 #include <vector>
 #include <functional>
 #include <omp.h>
-#include "../../minimaloptix_amd/csrc/pt_path.h"
 #include "../../minimaloptix_amd/csrc/pt_packet.h"
-#include "../../minimaloptix_amd/csrc/pt_lbvh.h"
-#include "../../minimaloptix_amd/csrc/pt_upload.h"
+#include "hostsim.h"
 
-using namespace pt;
-
-extern "C" {
-
-struct hostsim_scene {
-  moptix_params params;
-  int32_t nMaterials; const moptix_material* materials;
-  int32_t nSpheres; const moptix_sphere_params* spheres; const int32_t* sphereMat;
-  int32_t nQuads; const moptix_quad_params* quads; const int32_t* quadMat;
-  int32_t nLights; const moptix_light_params* lights;
-  int32_t nFaces;
-  const float* facePos;      // 9 floats per face: p0 p1 p2
-  const float* faceNrm;      // 9 floats per face (ignored where faceHasNrm == 0); may be NULL
-  const int32_t* faceHasNrm; // may be NULL
-  const int32_t* faceMat;
-  const float* faceUV;       // 6 floats per face (u0 v0 u1 v1 u2 v2); may be NULL
-  const int32_t* faceHasUV;  // may be NULL
-  int32_t nTextures; const int32_t* texSize;   // width,height per texture
-  const float* const* texels;                  // nTextures pointers to 4*w*h floats
-};
-
-struct hostsim_bvh_out {      // caller-allocated: nodes >= max(1,nFaces-1)*128 B, tris nFaces*48 B
-  void* nodes; void* tris; int32_t* triPrim;
-  int32_t nNodes, rootRef, depth;
-  void* nodes64;                // may be NULL: the same nodes compressed, nNodes*64 B
-};
-
-}  // extern "C"
+using namespace hostsim;
 
 namespace {
-
-struct HostBVH {
-  std::vector<Node128> nodes; std::vector<Node64> nodes64; std::vector<Tri48> tris; std::vector<TriShade> shade;
-  int rootRef = kEmptyRef; int depth = 0;
-};
 
 static int subtree_depth(const std::vector<Node128>& nodes, int ref) {
   if (ref < 0) return 0;
@@ -71,9 +37,9 @@ static int subtree_depth(const std::vector<Node128>& nodes, int ref) {
 // Host mirror of the device's binned-SAH topology (lbvh.hip k_sah_level / k_sah_finalize; shared functions and the
 // definition of the algorithm: pt_lbvh.h).  order: Morton order on entry, final order on return; nodes: n-1 entries.
 struct SahTask { int node, first, count; v3 cbLo, cbHi; };
-static int g_forcedRootSplit = 0;     // device: SahTask::force of the root task
+// forcedRootSplit: the device's SahTask::force of the root task
 static void build_sah_topology(const std::vector<v3>& lo, const std::vector<v3>& hi, std::vector<int>& order, v3 cbLo, v3 cbHi,
-                               int leafSize, std::vector<KarrasNode>& nodes, std::vector<int>& parentI, std::vector<int>& parentL) {
+                               int leafSize, int forcedRootSplit, std::vector<KarrasNode>& nodes, std::vector<int>& parentI, std::vector<int>& parentL) {
   const int n = (int)order.size();
   nodes.assign(n - 1, KarrasNode{ 0, 0, 0, 0 }); parentI.assign(n - 1, -1); parentL.assign(n, -1);
   std::vector<SahTask> tasks{ SahTask{ 0, 0, n, cbLo, cbHi } }, next;
@@ -90,8 +56,8 @@ static void build_sah_topology(const std::vector<v3>& lo, const std::vector<v3>&
       // HOSTSIM_SWEEP=2 adds the leaf-cost term (a split is taken only if cheaper than the range as one leaf is NOT used here: the array
       // form needs the full topology, and leaves are collapsed by size afterwards as on the device).
       static const int sweepMode = getenv("HOSTSIM_SWEEP") ? atoi(getenv("HOSTSIM_SWEEP")) : 0;
-      const bool forced = level == 0 && g_forcedRootSplit > 0;
-      if (forced) { sp.axis = -1; sp.nLeft = g_forcedRootSplit; }
+      const bool forced = level == 0 && forcedRootSplit > 0;
+      if (forced) { sp.axis = -1; sp.nLeft = forcedRootSplit; }
       const bool swept = !forced && sweepMode && t.count > leafSize && level < kSahLevels;
       if (swept) {
         float bestCost = 3.0e38f; int bestAxis = -1, bestK = 0;
@@ -169,8 +135,6 @@ static void build_sah_topology(const std::vector<v3>& lo, const std::vector<v3>&
 }
 
 static int g_debugPixel = getenv("HOSTSIM_DEBUG_PIXEL") ? atoi(getenv("HOSTSIM_DEBUG_PIXEL")) : -1;   // every ray of this pixel to stderr
-static int g_packet = 0;      // 1 = the per-bounce state machine of pt_packet.h (kernel variant 4) instead of the per-ray one
-static int g_builder = 1;     // 0 = Morton radix tree (Karras), 1 = binned SAH over the Morton order (device default)
 
 // HOSTSIM_ESC=<k> -- a YARDSTICK (tools/tree_yardstick.py), not the device's builder: early split clipping.  A triangle whose box is large for what
 // it holds -- a needle lying diagonally -- is referenced by several boxes, each the bounds of the triangle clipped to one half of the previous box
@@ -214,7 +178,9 @@ static void esc_split(const v3 tri[3], v3 lo, v3 hi, double triArea2, double k, 
   if (l1.x <= h1.x) esc_split(tri, l1, h1, triArea2, k, depth + 1, face, refFace, rlo, rhi);
 }
 
-static void build_lbvh(const hostsim_scene& s, int leafSize, HostBVH& out) {
+}  // namespace
+
+void hostsim::build_lbvh(const hostsim_scene& s, int leafSize, int builder, HostBVH& out) {
   out.nodes.clear(); out.nodes64.clear(); out.tris.clear(); out.shade.clear(); out.rootRef = kEmptyRef; out.depth = 0;
   if (s.nFaces <= 0) return;
   // references: one per face, or (HOSTSIM_ESC) several clipped boxes of one face
@@ -249,12 +215,12 @@ static void build_lbvh(const hostsim_scene& s, int leafSize, HostBVH& out) {
   for (int f = 0; f < n; f++) keys[f] = morton_key(cen[f], clo, invExt, bitsPerAxis, idxBits, f) | (tri_is_big(lo[f], hi[f], slo, shi) ? 0ull : kSmallKeyBit);
   std::sort(keys.begin(), keys.end());
   std::vector<KarrasNode> sahNodes; std::vector<int> sahParentI, sahParentL;
-  const bool useSah = g_builder == 1 && n > 1;
+  const bool useSah = builder == 1 && n > 1;
   if (useSah) {
     std::vector<int> order(n);
     for (int k = 0; k < n; k++) order[k] = key_face(keys[k], idxBits);
-    g_forcedRootSplit = big_key_count(keys.data(), n);      // large triangles first (pt_lbvh.h kSmallKeyBit): the root's range is split between them and the others
-    build_sah_topology(lo, hi, order, clo, chi, leafSize, sahNodes, sahParentI, sahParentL);
+    // large triangles first (pt_lbvh.h kSmallKeyBit): the root's range is split between them and the others
+    build_sah_topology(lo, hi, order, clo, chi, leafSize, big_key_count(keys.data(), n), sahNodes, sahParentI, sahParentL);
     for (int k = 0; k < n; k++) keys[k] = (uint64_t)order[k];              // the device keeps the face index only, too
   }
 
@@ -349,35 +315,12 @@ static void build_lbvh(const hostsim_scene& s, int leafSize, HostBVH& out) {
     if (!compress_node(out.nodes[i], out.nodes64[i])) { out.nodes64.clear(); break; }      // too wide for the grid: no 64-byte form (as lbvh.hip)
 }
 
-static int g_node64 = 0;        // hostsim_set_node_format: 1 = walk the 64-byte nodes, as the packet kernel does by default
-
-struct LocalStack {
-  int data[256];
-  inline void store(int sp, int v) { data[sp] = v; }
-  inline int load(int sp) const { return data[sp]; }
-  inline bool roomy(int) const { return true; }
-  inline void store_fast(int sp, int v) { data[sp] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  inline bool fits_fast(int, int) const { return false; }
-  inline int peek_fast(int) const { return 0; }
-};
-
-static inline void host_trav_step(const SceneView& sc, const PathState& ps, Trav& tv, LocalStack& st, Counters& ct) {
-  if (g_node64 && sc.nodes64) trav_step<true, true>(sc, ps, tv, st, ct); else trav_step<true, false>(sc, ps, tv, st, ct);
-}
-
-struct HostScene {
-  std::vector<DevMaterial> mats; std::vector<DevSphere> spheres; std::vector<int> sphereMat;
-  std::vector<DevQuad> quads; std::vector<DevLight> lights; HostBVH bvh; SceneView view;
-  std::vector<TriUV> faceUV; std::vector<DevTexture> textures;
-};
-
-static void make_scene(const hostsim_scene& s, int leafSize, HostScene& hs) {
+void hostsim::make_scene(const hostsim_scene& s, int leafSize, int builder, HostScene& hs) {
   for (int i = 0; i < s.nMaterials; i++) hs.mats.push_back(make_dev_material(s.materials[i]));
   for (int i = 0; i < s.nSpheres; i++) { hs.spheres.push_back(make_dev_sphere(s.spheres[i])); hs.sphereMat.push_back(s.sphereMat[i]); }
   for (int i = 0; i < s.nQuads; i++) hs.quads.push_back(make_dev_quad(s.quads[i], s.quadMat[i]));
   for (int i = 0; i < s.nLights; i++) hs.lights.push_back(make_dev_light(s.lights[i]));
-  build_lbvh(s, leafSize, hs.bvh);
+  build_lbvh(s, leafSize, builder, hs.bvh);
   SceneView& v = hs.view;
   memset(&v, 0, sizeof(v));
   v.width = (int)s.params.width; v.height = (int)s.params.height;
@@ -404,21 +347,38 @@ static void make_scene(const hostsim_scene& s, int leafSize, HostScene& hs) {
     hs.faceUV.push_back(uv);
   }
   v.triUV = anyUV ? hs.faceUV.data() : nullptr;
-  for (int t = 0; t < s.nTextures; t++)
-    hs.textures.push_back(DevTexture{ reinterpret_cast<const v4*>(s.texels[t]), s.texSize[2 * t], s.texSize[2 * t + 1] });
+  for (int t = 0; t < s.nTextures; t++) {
+    hs.texels.emplace_back(s.texels[t], s.texels[t] + 4 * (size_t)s.texSize[2 * t] * (size_t)s.texSize[2 * t + 1]);
+    hs.textures.push_back(DevTexture{ reinterpret_cast<const v4*>(hs.texels[t].data()), s.texSize[2 * t], s.texSize[2 * t + 1] });
+  }
   v.nTextures = s.nTextures; v.textures = hs.textures.data();
 }
 
-}  // namespace
-
 extern "C" {
 
-void hostsim_set_builder(int builder) { g_builder = builder; }
-void hostsim_set_node_format(int bytes) { g_node64 = bytes == 64; }
-void hostsim_set_packet(int packet) { g_packet = packet; }
+struct hostsim_bvh_out {      // caller-allocated: nodes >= max(1,nFaces-1)*128 B, tris nFaces*48 B
+  void* nodes; void* tris; int32_t* triPrim;
+  int32_t nNodes, rootRef, depth;
+  void* nodes64;                // may be NULL: the same nodes compressed, nNodes*64 B
+};
 
-int hostsim_build_bvh(const hostsim_scene* s, int leafSize, hostsim_bvh_out* out) {
-  HostBVH b; build_lbvh(*s, leafSize, b);
+// The scene as built, on one thread; the scene's arrays are copied.  Everything that traces takes the handle this returns.
+void* hostsim_create(const hostsim_scene* s, int leafSize, int builder) {
+  HostSim* sim = new HostSim();
+  const double t0 = omp_get_wtime();
+  make_scene(*s, leafSize, builder, sim->hs);
+  sim->buildSeconds = omp_get_wtime() - t0;
+  const size_t n = (size_t)(s->nFaces > 0 ? s->nFaces : 0);
+  sim->facePos.assign(s->facePos, s->facePos + 9 * n);
+  sim->faceNrm.assign(9 * n, 0.f); sim->faceHasNrm.assign(n, 0);
+  for (size_t f = 0; f < n; f++)
+    if (s->faceNrm && s->faceHasNrm && s->faceHasNrm[f]) { sim->faceHasNrm[f] = 1; memcpy(&sim->faceNrm[9 * f], s->faceNrm + 9 * f, 9 * sizeof(float)); }
+  return sim;
+}
+void hostsim_free(void* h) { delete static_cast<HostSim*>(h); }
+
+int hostsim_read_bvh(void* h, hostsim_bvh_out* out) {
+  const HostBVH& b = static_cast<HostSim*>(h)->hs.bvh;
   out->nNodes = (int)b.nodes.size(); out->rootRef = b.rootRef; out->depth = b.depth;
   if (out->nodes && !b.nodes.empty()) memcpy(out->nodes, b.nodes.data(), b.nodes.size() * sizeof(Node128));
   if (out->nodes64 && !b.nodes64.empty()) memcpy(out->nodes64, b.nodes64.data(), b.nodes64.size() * sizeof(Node64));
@@ -427,12 +387,10 @@ int hostsim_build_bvh(const hostsim_scene* s, int leafSize, hostsim_bvh_out* out
   return 0;
 }
 
-
 // Debugging aid: where does a ray lose a triangle?  Prints, for every node on the way from the root to the leaf that holds
 // face `prim`, the slab test of the child that leads there (with tbest = tmax), then the triangle test itself.
-extern "C" int hostsim_debug_ray(const hostsim_scene* s, int leafSize, const float o[3], const float d[3], float tmin, int prim) {
-  HostScene hs; make_scene(*s, leafSize, hs);
-  const HostBVH& b = hs.bvh;
+int hostsim_debug_ray(void* h, const float o[3], const float d[3], float tmin, int prim) {
+  const HostBVH& b = static_cast<HostSim*>(h)->hs.bvh;
   if (prim < 0) { prim = b.tris[-prim].prim; fprintf(stderr, "[hostsim] triangle record %d is face %d\n", -prim, prim); return prim; }   // record index -> face
   std::vector<std::pair<int, int>> path, cur;      // (node, child)
   bool found = false;
@@ -478,15 +436,17 @@ extern "C" int hostsim_debug_ray(const hostsim_scene* s, int leafSize, const flo
   return 0;
 }
 
+// The beauty render on the tree as it stands.  packet: 1 = the per-bounce state machine of pt_packet.h (kernel variant 4) instead of
+// the per-ray one.
 // counters: samples, primary, bounce, shadow, nodeFetches, triTests, closestHits, lightLoads, analyticTests
-// timing (may be NULL): [0] seconds of scene set-up + LBVH build (single thread), [1] seconds of rendering (all OpenMP
-// threads), [2] the number of threads used -- bench.py's cpu_baseline: "a CPU build of the same megakernel", BVH build
+// timing (may be NULL): [0] seconds hostsim_create took for scene set-up + LBVH build (single thread), [1] seconds of rendering (all
+// OpenMP threads), [2] the number of threads used -- bench.py's cpu_baseline: "a CPU build of the same megakernel", BVH build
 // excluded from the rate and reported separately.
-int hostsim_render_timed(const hostsim_scene* s, int leafSize, const int32_t* seeds, int nSeeds, float* accum, uint64_t counters[9], double timing[3]) {
-  const double t0 = omp_get_wtime();
-  HostScene hs; make_scene(*s, leafSize, hs);
+int hostsim_render(void* h, int nodeFormat, int packet, const int32_t* seeds, int nSeeds, float* accum, uint64_t counters[9], double timing[3]) {
+  const HostSim* sim = static_cast<HostSim*>(h);
   const double t1 = omp_get_wtime();
-  const SceneView& sc = hs.view;
+  const SceneView& sc = sim->hs.view;
+  const bool n64 = walks_node64(sc, nodeFormat);
   uint64_t tot[9] = { 0 };
   const int nPix = sc.width * sc.height;
 #pragma omp parallel
@@ -510,29 +470,29 @@ int hostsim_render_timed(const hostsim_scene* s, int leafSize, const int32_t* se
           if (++sIdx >= nSeeds) break;
           begin_sample<true>(sc, ps, seeds[sIdx], ct);
           packet_primary(pk);
-        } else if (ps.mode == M_TRACE && g_packet) {
+        } else if (ps.mode == M_TRACE && packet) {
           // the packet's rays, each on its own: shadow rays in light order, then the continuation
           for (int i = 0; i < pk.nShadow; i++) {
             PathState r = ps; Trav ts; memset(&ts, 0, sizeof(ts));
             r.d = pk.sd[i]; r.tmin = sc.epsT; r.tmax = pk.stmax[i]; r.kind = RK_SHADOW;
             trav_begin<true>(sc, r, ts, ct);
-            while (ts.node != kTravDone) host_trav_step(sc, r, ts, st, ct);
+            while (ts.node != kTravDone) host_trav_step(sc, r, ts, st, ct, n64);
             att[i] = ts.att;
           }
           if (pk.hasBounce) {
             ps.kind = RK_RADIANCE;
             trav_begin<true>(sc, ps, tv, ct);
-            while (tv.node != kTravDone) host_trav_step(sc, ps, tv, st, ct);
+            while (tv.node != kTravDone) host_trav_step(sc, ps, tv, st, ct, n64);
           }
           ps.mode = M_RESULT;
         } else if (ps.mode == M_TRACE) {
           trav_begin<true>(sc, ps, tv, ct);
-          while (tv.node != kTravDone) host_trav_step(sc, ps, tv, st, ct);
+          while (tv.node != kTravDone) host_trav_step(sc, ps, tv, st, ct, n64);
           if (pix == g_debugPixel)
             fprintf(stderr, "[hostsim] pixel %d depth %d kind %d o %.9g %.9g %.9g d %.9g %.9g %.9g tmin %.9g tmax %.9g -> t %.9g prim %d tri %d att %.9g %.9g %.9g\n", pix, ps.depth,
                     (int)ps.kind, ps.o.x, ps.o.y, ps.o.z, ps.d.x, ps.d.y, ps.d.z, ps.tmin, ps.tmax, tv.tbest, tv.bestPrim, tv.bestTri, tv.att.x, tv.att.y, tv.att.z);
           ps.mode = M_RESULT;
-        } else if (ps.mode == M_RESULT && g_packet) {
+        } else if (ps.mode == M_RESULT && packet) {
           on_result_packet<true>(sc, ps, pk, tv, att, ct, PacketSink{ pk });
         } else if (ps.mode == M_RESULT) {
           on_result<true>(sc, ps, tv, ct);
@@ -549,12 +509,8 @@ int hostsim_render_timed(const hostsim_scene* s, int leafSize, const int32_t* se
     for (int i = 0; i < 9; i++) tot[i] += loc[i];
   }
   if (counters) for (int i = 0; i < 9; i++) counters[i] = tot[i];
-  if (timing) { timing[0] = t1 - t0; timing[1] = omp_get_wtime() - t1; timing[2] = (double)omp_get_max_threads(); }
+  if (timing) { timing[0] = sim->buildSeconds; timing[1] = omp_get_wtime() - t1; timing[2] = (double)omp_get_max_threads(); }
   return 0;
-}
-
-int hostsim_render(const hostsim_scene* s, int leafSize, const int32_t* seeds, int nSeeds, float* accum, uint64_t counters[9]) {
-  return hostsim_render_timed(s, leafSize, seeds, nSeeds, accum, counters, nullptr);
 }
 
 }  // extern "C"

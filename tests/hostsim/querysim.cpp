@@ -1,9 +1,12 @@
 // querysim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the ray-query kernel (minimaloptix_amd/csrc/querykernel.hip): the same
-// per-ray code (pt_query.h over pt_path.h's traversal), compiled for the host and run one ray at a time, on the scene and tree that
-// tests/hostsim builds (its source is included unchanged).  The GPU tests compare the kernel's output with this bit for bit.  It is
-// not part of the product: nothing under minimaloptix_amd/ builds or loads it.
-#include "../hostsim/hostsim.cpp"
+// per-ray code (pt_query.h over pt_path.h's traversal), compiled for the host and run one ray at a time, on the scene and tree of a
+// hostsim_create handle (hostsim.h).  The GPU tests compare the kernel's output with this bit for bit.  It is not part of the
+// product: nothing under minimaloptix_amd/ builds or loads it.
+#include <cstring>
+#include "hostsim.h"
 #include "../../minimaloptix_amd/csrc/pt_query.h"
+
+using namespace hostsim;
 
 namespace {
 
@@ -24,13 +27,11 @@ void query_one(const SceneView& sc, const float* r, void* out, size_t i) {
 
 extern "C" {
 
-// moptix_query_rays on the CPU.  rays: n x 8 floats; mode 0 = closest (out: n x 32-byte hit records), 1 = any (out: n x int32);
-// nodeFormat 64 walks the 64-byte nodes where the tree has them (as the kernel does by default), 128 the 128-byte ones.
-int querysim_query(const hostsim_scene* s, int leafSize, int nodeFormat, const float* rays, int64_t n, int mode, void* out) {
-  if (!s || n < 0 || (n > 0 && (!rays || !out)) || (mode != QUERY_CLOSEST && mode != QUERY_ANY)) return -1;
-  HostScene hs; make_scene(*s, leafSize, hs);
-  const SceneView& sc = hs.view;
-  const bool n64 = nodeFormat == 64 && sc.nodes64 != nullptr;
+// moptix_query_rays on the CPU.  rays: n x 8 floats; mode 0 = closest (out: n x 32-byte hit records), 1 = any (out: n x int32).
+int querysim_query(void* h, int nodeFormat, const float* rays, int64_t n, int mode, void* out) {
+  if (!h || n < 0 || (n > 0 && (!rays || !out)) || (mode != QUERY_CLOSEST && mode != QUERY_ANY)) return -1;
+  const SceneView& sc = static_cast<HostSim*>(h)->hs.view;
+  const bool n64 = walks_node64(sc, nodeFormat);
 #pragma omp parallel for schedule(dynamic, 64)
   for (int64_t i = 0; i < n; i++) {
     const float* r = rays + 8 * (size_t)i;

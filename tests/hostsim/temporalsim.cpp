@@ -1,15 +1,17 @@
-// facemotionsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of moptix_denoise_temporal with the option "temporal_face_motion"
-// (minimaloptix_amd/csrc/facemotionkernel.hip, temporalkernel.hip and the bookkeeping of api_temporal.hip): ../temporalsim's frame loop
-// plus the face snapshot, the per-face records and the rules that decide whether the face pass runs, over the same per-face and
-// per-pixel code (pt_temporal.h) compiled for the host.  The GPU tests compare the device's output with this bit for bit.  It is not
-// part of the product: nothing under minimaloptix_amd/ builds or loads it.
+// temporalsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of moptix_denoise_temporal (minimaloptix_amd/csrc/temporalkernel.hip,
+// facemotionkernel.hip and the history bookkeeping of api_temporal.hip): the same per-pixel and per-face code (pt_temporal.h,
+// pt_denoise.h), compiled for the host and run pass by pass over caller-given float arrays, in the order the kernels run it (the
+// a-trous passes: atrous_host.h), with the history kept in an object between calls.  With the option "temporal_face_motion" (off by
+// default) it also keeps the face snapshot, the per-face records and the rules that decide whether the face pass runs.
+// The GPU tests compare the device's output with this bit for bit.  It is not part of the product: nothing under minimaloptix_amd/
+// builds or loads it.
 #include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
 
 #include "../../include/moptix.h"
-#include "../denoisesim/atrous_host.h"
+#include "atrous_host.h"
 
 using namespace pt;
 
@@ -43,21 +45,25 @@ TpCamera to_camera(const moptix_cam_params& c) {
 
 extern "C" {
 
-void* facemotionsim_create() { return new Sim; }
-void facemotionsim_destroy(void* s) { delete (Sim*)s; }
-void facemotionsim_reset(void* s) { ((Sim*)s)->drop(); }                                  // moptix_temporal_reset
-void facemotionsim_clear_scene(void* s) { ((Sim*)s)->drop(); ((Sim*)s)->changed = true; } // moptix_clear_scene
-void facemotionsim_faces_changed(void* s) { ((Sim*)s)->changed = true; }                  // moptix_update_faces*, moptix_build_accel
-void facemotionsim_set_option(void* s, int v) { ((Sim*)s)->option = v; if (!v) ((Sim*)s)->faceHave = false; }
-uint64_t facemotionsim_frames(void* s) { return ((Sim*)s)->frames; }
+void* temporalsim_create() { return new Sim; }
+void temporalsim_destroy(void* s) { delete (Sim*)s; }
+void temporalsim_reset(void* s) { ((Sim*)s)->drop(); }                                  // moptix_temporal_reset
+void temporalsim_clear_scene(void* s) { ((Sim*)s)->drop(); ((Sim*)s)->changed = true; } // moptix_clear_scene
+void temporalsim_faces_changed(void* s) { ((Sim*)s)->changed = true; }                  // moptix_update_faces*, moptix_build_accel
+void temporalsim_set_option(void* s, int v) { ((Sim*)s)->option = v; if (!v) ((Sim*)s)->faceHave = false; }
+uint64_t temporalsim_frames(void* s) { return ((Sim*)s)->frames; }
 
-// temporalsim_run plus: facePos, 9 floats for each of the nFaces faces on the device as they stand now; firstFace = nSpheres + nQuads;
-// faceStats[3] = tracked faces, moved faces, moved pixels.
-int facemotionsim_run(void* state, int width, int height, const float* accum, const float* albedo, const float* normal, const float* depth,
-                      const float* hits, const int32_t* primId, const int32_t* matId, float nAccumulation, float nSamples,
-                      const moptix_cam_params* cam, const float* centres, int nSpheres, const float* facePos, int nFaces, int firstFace,
-                      const moptix_denoise_params* prm, const moptix_temporal_params* tprm, float* out, float* motionOut, float* historyOut,
-                      float* pre, uint64_t* counters, uint64_t* faceStats) {
+// moptix_denoise_temporal on the CPU over host arrays in the accumulation buffer's layout.  centres: nSpheres * 3 floats (the context's
+// spheres now).  facePos (may be NULL with nFaces = 0): 9 floats for each of the nFaces faces on the device as they stand now; firstFace
+// = nSpheres + nQuads.  Outputs, each optional: out W*H*3; motion W*H*2; history W*H; pre W*H*4 = {I_acc, v} as the first a-trous
+// iteration reads them (after the prepass; before it with iterations = 0); counters[4] = geometry, history, disoccluded pixels, sum
+// of h over the geometry pixels; faceStats[3] = tracked faces, moved faces, moved pixels.  Parameters are taken as given (the C ABI
+// checks their ranges).
+int temporalsim_run(void* state, int width, int height, const float* accum, const float* albedo, const float* normal, const float* depth,
+                    const float* hits, const int32_t* primId, const int32_t* matId, float nAccumulation, float nSamples,
+                    const moptix_cam_params* cam, const float* centres, int nSpheres, const float* facePos, int nFaces, int firstFace,
+                    const moptix_denoise_params* prm, const moptix_temporal_params* tprm, float* out, float* motionOut, float* historyOut,
+                    float* pre, uint64_t* counters, uint64_t* faceStats) {
   Sim* s = (Sim*)state;
   if (!s || width <= 0 || height <= 0 || !accum || !albedo || !normal || !depth || !hits || !primId || !matId || !cam || !prm || !tprm ||
       (nSpheres > 0 && !centres) || nFaces < 0 || (nFaces > 0 && !facePos))

@@ -1,37 +1,17 @@
-"""Bindings of tests/querysim (the CPU mirror of the ray-query kernel) and the ray sets of the query tests."""
-import ctypes as C
-import os
-import subprocess
-
+"""The ray queries of the CPU mirror (tests/hostsim/querysim.cpp) and the ray sets of the query tests."""
 import numpy as np
 
-from common import M, REPO, HostsimScene, _hostsim_scene
-
-_QUERYSIM_DIR = os.path.join(REPO, "tests", "querysim")
-_querysim = None
+from common import M, _f32, _ptr, hostsim_handle, hostsim_lib
 
 HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("ng", np.float32, (3,))])
 
 
-def querysim_lib():
-    global _querysim
-    if _querysim is None:
-        path = os.path.join(_QUERYSIM_DIR, "libquerysim.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _QUERYSIM_DIR, "-s"])
-        L = C.CDLL(path)
-        L.querysim_query.argtypes = [C.POINTER(HostsimScene), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int, C.c_void_p]
-        _querysim = L
-    return _querysim
-
-
 def querysim(hs, rays, mode="closest", node_format=64, leaf_size=4):
-    """moptix_query_rays on the CPU: a HIT_DTYPE record array ("closest") or an int32 array ("any")."""
-    s, keep = _hostsim_scene(hs)
-    rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
+    """moptix_query_rays on the CPU: a HIT_DTYPE record array ("closest") or an int32 array ("any").  hs: a scene, or a built one."""
+    sim = hostsim_handle(hs, leaf_size)
+    rays = _f32(np.asarray(rays, np.float32).reshape(-1, 8))
     out = np.zeros(len(rays), HIT_DTYPE if mode == "closest" else np.int32)
-    rc = querysim_lib().querysim_query(C.byref(s), int(leaf_size), int(node_format), rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays),
-                                       0 if mode == "closest" else 1, C.c_void_p(out.ctypes.data))
+    rc = hostsim_lib().querysim_query(sim._h, int(node_format), _ptr(rays), len(rays), 0 if mode == "closest" else 1, out.ctypes.data)
     assert rc == 0
     return out
 

@@ -1,5 +1,5 @@
 """Adaptive sampling without a GPU: the defaults and the argument check, the CPU mirror of the kernels and the pass schedule
-(tests/adaptivesim) against the semantics of include/moptix.h -- the threshold-0 anchor, the prefix property, the moments -- and what
+(tests/hostsim/adaptivesim.cpp) against the semantics of include/moptix.h -- the threshold-0 anchor, the prefix property, the moments -- and what
 adaptive sampling buys at equal cost on the denoiser tests' scenes."""
 import ctypes as C
 

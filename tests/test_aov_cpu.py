@@ -1,4 +1,4 @@
-"""First-hit AOVs (include/moptix.h "first-hit AOVs") without a GPU: the CPU mirror of the AOV kernel (tests/aovsim, the kernel's own
+"""First-hit AOVs (include/moptix.h "first-hit AOVs") without a GPU: the CPU mirror of the AOV kernel (tests/hostsim/aovsim.cpp, the kernel's own
 per-pixel code from pt_aov.h) against the oracle and against the semantics table, and the C ABI's boundary errors."""
 import ctypes as C
 import os

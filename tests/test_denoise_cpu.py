@@ -1,4 +1,4 @@
-"""The denoiser (include/moptix.h "denoiser") without a GPU: exp_ac against float64 exp, the CPU mirror of the kernels (tests/denoisesim,
+"""The denoiser (include/moptix.h "denoiser") without a GPU: exp_ac against float64 exp, the CPU mirror of the kernels (tests/hostsim/denoisesim.cpp,
 the kernels' own per-pixel code from pt_denoise.h) against an independent float64 implementation of the semantics written here from the
 header's text, the filter's properties, its quality on path-traced frames, and the C ABI's host-only entry points."""
 import ctypes as C

@@ -1,18 +1,16 @@
 """Per-face motion in the temporal stage (include/moptix.h, step 2 of "denoiser: temporal accumulation", option "temporal_face_motion")
-without a GPU: the CPU mirror of the whole call (tests/facemotionsim, the kernels' own per-face and per-pixel code from pt_temporal.h)
-against the mirror of the call without the option (tests/temporalsim), against the camera path that the temporal tests already cover,
+without a GPU: the CPU mirror of the whole call (tests/hostsim/temporalsim.cpp with its option on, the kernels' own per-face and per-pixel code from pt_temporal.h)
+against the mirror of the call without the option (the same mirror with the option off), against the camera path that the temporal tests already cover,
 on a mesh of small triangles that moves fast, and on the edge cases of the snapshot's life.  Measured values: profiles/r14_face_motion.txt."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from common import M, K, hostsim_render, rmse
+from common import M, K, MovedScene, hostsim_render, rmse
 from aov_helpers import aovsim_render
 from temporal_helpers import TemporalSim, cam_of, cam_params, centres_of, copy_spheres, moved_camera, sphere_array
-from temporal_helpers import MovedScene as MovedSpheres
-from refit_helpers import MovedScene
-from facemotion_helpers import FaceMotionSim, first_face, grid_mesh_scene, translated, with_params
+from facemotion_helpers import first_face, grid_mesh_scene, translated
 
 F = np.float64
 
@@ -48,7 +46,7 @@ def sphere_sequence():
         p = K.Params.from_buffer_copy(hs.params)
         K.host_lib().mohost_video_camera(angle.value, w / h, C.byref(p.cam))
         frame = copy_spheres(sph, n)
-        scene = MovedSpheres(hs, spheres=frame, params=p)
+        scene = MovedScene(hs, spheres=frame, params=p)
         seeds = M.launch_seeds(2, 0, 100 * k)
         accum, aovs = _render(scene, seeds)
         frames.append((accum, aovs, cam_of(p), centres_of(frame, n)))
@@ -63,7 +61,7 @@ def test_without_a_moved_face_the_mirror_gives_temporalsims_bits(sphere_sequence
     rng = np.random.RandomState(3)
     faces = rng.rand(40, 9).astype(np.float32)
     # every pixel of some frames points at a face: ids past the spheres are faces 0 .. 39
-    sim, ref = FaceMotionSim(1 if mode == "on_unmoved" else 0), TemporalSim()
+    sim, ref = TemporalSim(option=1 if mode == "on_unmoved" else 0), TemporalSim()
     for k, (accum, aovs, cam, centres) in enumerate(frames):
         a = dict(aovs)
         a["primId"] = np.where(aovs["primId"] >= 0, aovs["primId"] + (n if k % 2 else 0), -1).astype(np.int32)
@@ -113,7 +111,7 @@ def test_rigid_translation_of_the_mesh_equals_a_translation_of_the_previous_came
     seeds0, seeds1 = M.launch_seeds(2, 0, 0), M.launch_seeds(2, 0, 100)
     before = translated(base, -T)
     # run A: the mesh at base - T, then at base; the camera stays
-    sim_a = FaceMotionSim(1)
+    sim_a = TemporalSim(option=1)
     s0 = MovedScene(hs, before, new_faces=(kind == "grid"))
     acc, aov = _render(s0, seeds0)
     sim_a.run(acc, aov, 2, aov["samples"], cam_of(hs.params), face_pos=before, first_face=ff)
@@ -124,7 +122,7 @@ def test_rigid_translation_of_the_mesh_equals_a_translation_of_the_previous_came
     # run B: the mesh at base in both frames; the previous camera is translated by +T
     sim_b = TemporalSim()
     pb = moved_camera(hs.params, T)
-    sb = with_params(MovedScene(hs, base, new_faces=(kind == "grid")), pb)
+    sb = MovedScene(hs, base, new_faces=(kind == "grid"), params=pb)
     accb, aovb = _render(sb, seeds0)
     sim_b.run(accb, aovb, 2, aovb["samples"], cam_of(pb))
     b = sim_b.run(acc1, aov1, 2, aov1["samples"], cam_of(hs.params))
@@ -154,7 +152,7 @@ def _tracking_run(option):
     base = sc.face_arrays()[0].copy()
     ff = first_face(sc)
     step = np.float32([1.5 * 0.9 / 16, 0.0, 0.0])                     # one and a half quads per frame
-    sim = FaceMotionSim(option)
+    sim = TemporalSim(option=option)
     prev_ids, own, n = None, 0, 0
     for k in range(3):
         fp = translated(base, step * np.float32(k))
@@ -220,7 +218,7 @@ def _two_calls(sim, faces0, faces1, prim, **kw):
 def test_a_moved_face_shifts_its_pixels_by_its_own_motion():
     """The big triangle moves 3 pixels to the right: every pixel finds its history 3 pixels to the left, as under a camera that moved
     3 pixels to the left."""
-    got = _two_calls(FaceMotionSim(1), BIG, translated(BIG, (3 * PIXEL, 0, 0)), 0)
+    got = _two_calls(TemporalSim(option=1), BIG, translated(BIG, (3 * PIXEL, 0, 0)), 0)
     has = got["history"] == 2
     assert has[:, 3:].all() and not has[:, :3].any()
     assert np.abs(got["motion"][..., 0][has] - 3).max() <= 1e-4 and np.abs(got["motion"][..., 1][has]).max() <= 1e-4
@@ -264,7 +262,7 @@ def test_a_deformed_face_moves_each_pixel_by_the_affine_motion_at_its_world_poin
     clamped to [-1, 2]."""
     now = BIG if case == "inside" else np.float32([[-0.5, -0.5, -4, 0.5, -0.5, -4, -0.5, 0.5, -4]])
     prev = (now.reshape(3, 3) - AFFINE_D).astype(np.float32).reshape(1, 9)
-    got = _two_calls(FaceMotionSim(1), prev, now, 0)
+    got = _two_calls(TemporalSim(option=1), prev, now, 0)
     want, bu, bv = _expected_motion(now, prev)
     has = got["history"] == 2
     assert got["face_info"] == dict(tracked_faces=1, moved_faces=1, moved_pixels=H * W) and has.sum() > 0.5 * H * W
@@ -291,11 +289,11 @@ def test_a_zero_area_face_that_moves_takes_its_first_vertex_displacement():
     for degenerate in (np.float32([[1, 1, -4] * 3]), np.float32([[0, 0, -4, 1, 0, -4, 2, 0, -4]])):      # now a point; now a segment
         before = (degenerate.reshape(3, 3) - d).astype(np.float32).reshape(1, 9)                          # a proper triangle before the move
         d0 = degenerate[0, :3] - before[0, :3]
-        got = _two_calls(FaceMotionSim(1), before, degenerate, 0)
+        got = _two_calls(TemporalSim(option=1), before, degenerate, 0)
         # the reference run: BIG's vertices are small integers, so that adding d0 and subtracting again gives d0 exactly
         ref_before = (BIG.reshape(3, 3) - d0).astype(np.float32)
         assert np.array_equal(BIG.reshape(3, 3) - ref_before, np.tile(d0, (3, 1)))
-        want = _two_calls(FaceMotionSim(1), ref_before.reshape(1, 9), BIG, 0)
+        want = _two_calls(TemporalSim(option=1), ref_before.reshape(1, 9), BIG, 0)
         assert np.array_equal(_bits(got["motion"]), _bits(want["motion"])) and np.array_equal(_bits(got["out"]), _bits(want["out"]))
         assert got["face_info"] == dict(tracked_faces=1, moved_faces=1, moved_pixels=H * W)
         assert (got["history"] == 2).any() and np.abs(got["motion"][..., 0][got["history"] == 2] - 2).max() <= 1e-4
@@ -304,7 +302,7 @@ def test_a_zero_area_face_that_moves_takes_its_first_vertex_displacement():
 def test_a_face_moved_and_moved_back_has_no_displacement():
     """Call 2 sees the move; before call 3 the face moves away and back: the face pass runs, finds nine zeros, and the call gives
     TemporalSim's bits (the static shortcut)."""
-    sim, idle = FaceMotionSim(1), FaceMotionSim(1)          # `idle` gets no update before its third call: its face pass does not run
+    sim, idle = TemporalSim(option=1), TemporalSim(option=1)          # `idle` gets no update before its third call: its face pass does not run
     there = translated(BIG, (2 * PIXEL, 0, 0))
     for k, faces in enumerate((BIG, there)):
         a, v, s = _plane(H, W, 0, seed=1 + k)
@@ -323,7 +321,7 @@ def test_a_face_moved_and_moved_back_has_no_displacement():
 
 
 def test_a_face_count_change_keeps_the_history_and_tracks_nothing_in_that_call():
-    sim = FaceMotionSim(1)
+    sim = TemporalSim(option=1)
     two = np.concatenate([BIG, translated(BIG, (0, 0, -1))])
     a, v, s = _plane(H, W, 0, seed=1)
     sim.run(a, v, 1.0, s, _camera(W, H), face_pos=BIG, iterations=0)
@@ -339,7 +337,7 @@ def test_a_face_count_change_keeps_the_history_and_tracks_nothing_in_that_call()
 
 
 def test_turning_the_option_off_drops_the_snapshot():
-    sim = FaceMotionSim(1)
+    sim = TemporalSim(option=1)
     a, v, s = _plane(H, W, 0, seed=1)
     sim.run(a, v, 1.0, s, _camera(W, H), face_pos=BIG, iterations=0)
     sim.set_option(0); sim.set_option(1)
@@ -357,7 +355,7 @@ def test_spheres_and_quads_beside_moved_triangles_keep_their_own_rules():
     """Columns 0-9: sphere 0 (its centre moves one pixel up), 10-19: quad (id 1: never moves), 20-31: face 0 (moves 2 pixels right).
     The sphere's and the quad's pixels have TemporalSim's bits; the triangle's pixels move by 2."""
     prim = np.where(np.arange(W) < 10, 0, np.where(np.arange(W) < 20, 1, 2))[None, :]
-    sim, ref = FaceMotionSim(1), TemporalSim()
+    sim, ref = TemporalSim(option=1), TemporalSim()
     cen0, cen1 = np.float32([[0, 0, -4]]), np.float32([[0, PIXEL, -4]])
     a, v, s = _plane(H, W, prim, seed=1)
     sim.run(a, v, 1.0, s, _camera(W, H), cen0, face_pos=BIG, first_face=2, iterations=0); ref.run(a, v, 1.0, s, _camera(W, H), cen0, iterations=0)
@@ -382,7 +380,7 @@ def test_frame_quality_numbers_of_a_translating_coffee_mesh():
     base = hs.face_arrays()[0].copy()
     ff = first_face(hs)
     step = np.float32([0.01, 0.0, 0.0])
-    sims = {1: FaceMotionSim(1), 0: FaceMotionSim(0)}
+    sims = {1: TemporalSim(option=1), 0: TemporalSim(option=0)}
     for k in range(frames):
         fp = translated(base, step * np.float32(k))
         scene = MovedScene(hs, fp)

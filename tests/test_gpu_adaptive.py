@@ -1,6 +1,6 @@
 """Adaptive sampling on the MI355X (adaptivekernel.hip, api_adaptive.hip): a shortened order list renders exactly the active pixels
 through the trace kernels as they are (every pixel holds the bits of a plain render of its own prefix of the seed list), threshold 0 is
-moptix_render, every buffer and the stats are the CPU mirror's (tests/adaptivesim) bit for bit, nothing else in the context changes,
+moptix_render, every buffer and the stats are the CPU mirror's (tests/hostsim/adaptivesim.cpp) bit for bit, nothing else in the context changes,
 state and argument errors, sub-passes under a small per-sample buffer."""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""First-hit AOVs on the MI355X (aovkernel.hip): bit for bit the CPU mirror of the kernel's code (tests/aovsim), the oracle's closest hits
+"""First-hit AOVs on the MI355X (aovkernel.hip): bit for bit the CPU mirror of the kernel's code (tests/hostsim/aovsim.cpp), the oracle's closest hits
 on the camera rays, and no effect on anything else the context holds."""
 import os
 import subprocess

@@ -1,4 +1,4 @@
-"""The denoiser on the MI355X (denoisekernel.hip): bit for bit the CPU mirror of the kernels' code (tests/denoisesim) on rendered and on
+"""The denoiser on the MI355X (denoisekernel.hip): bit for bit the CPU mirror of the kernels' code (tests/hostsim/denoisesim.cpp) on rendered and on
 synthetic inputs, no effect on anything else the context holds, binding, state errors and the CLI."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """Per-face motion in the temporal stage on the MI355X (facemotionkernel.hip, temporalkernel.hip's k_tp_reproject<true>): output,
-motion vectors, history lengths and both sets of counters bit for bit the CPU mirror of the whole call (tests/facemotionsim) on moving
+motion vectors, history lengths and both sets of counters bit for bit the CPU mirror of the whole call (tests/hostsim/temporalsim.cpp) on moving
 and deforming meshes, over the face counts at the wave and workgroup tails, with the option off (today's bits), on static frames,
 no effect on anything else the context holds, and the argument errors."""
 import ctypes as C
@@ -11,7 +11,7 @@ from common import M, K
 from temporal_helpers import TemporalSim, cam_of, moved_camera
 from denoise_helpers import synthetic_aovs
 from refit_helpers import moved_faces, strip_scene
-from facemotion_helpers import FaceMotionSim, first_face, translated
+from facemotion_helpers import first_face, translated
 
 pytestmark = pytest.mark.gpu
 
@@ -49,12 +49,9 @@ def _frame(ctx, seeds):
 
 
 def _check(ctx, sim, accum, aovs, s, n_acc, cam, centres, faces, ff, what, **kw):
-    """One denoise_temporal call against one call of the mirror (a FaceMotionSim, or a TemporalSim for today's behaviour)."""
+    """One denoise_temporal call against one call of the mirror (a TemporalSim, its option on or off)."""
     got = ctx.denoise_temporal(n_acc, **kw)
-    if isinstance(sim, FaceMotionSim):
-        want = sim.run(accum, aovs, n_acc, s, cam, centres, face_pos=faces, first_face=ff, **kw)
-    else:
-        want = dict(sim.run(accum, aovs, n_acc, s, cam, centres, **kw), face_info=dict(tracked_faces=0, moved_faces=0, moved_pixels=0))
+    want = sim.run(accum, aovs, n_acc, s, cam, centres, face_pos=faces, first_face=ff, **kw)
     _assert_bits(got, want["out"], (what, "out"))
     r = ctx.temporal_read()
     _assert_bits(r["motion"], want["motion"], (what, "motion"))
@@ -102,7 +99,7 @@ def test_gpu_face_motion_is_the_cpu_mirrors_bits_on_coffee(ctx, name, fmt, how, 
         sph = _add_spheres(ctx, centres0)
         n_sph = len(centres0)
     ff = n_sph + int(hs.sizes.nQuads)
-    sim = FaceMotionSim(1)
+    sim = TemporalSim(option=1)
     sim.faces_changed()
     first, count = 20000, 60000
     moved_px = 0
@@ -180,7 +177,7 @@ def _synthetic_sequence(ctx, n_faces, h, w, frames=3, refit=False):
     fill, s, prm = _bind_synthetic(ctx, scene, h, w)
     base = scene.face_arrays()[0].copy()
     ff = first_face(scene)
-    sim = FaceMotionSim(1)
+    sim = TemporalSim(option=1)
     sim.faces_changed()
     rng = np.random.RandomState(n_faces * 31 + h * 7 + w)
     yy, xx = np.mgrid[0:h, 0:w]
@@ -243,7 +240,7 @@ def test_option_off_with_moved_faces_is_todays_behaviour(ctx):
 
 @pytest.mark.timeout(300)
 def test_static_frames_after_motion_cost_nothing_and_apply_no_displacement(ctx):
-    sim = FaceMotionSim(1)
+    sim = TemporalSim(option=1)
     for hs, k, accum, aovs, s, faces in _moving_coffee(ctx, 1):
         sim.faces_changed()
         want = _check(ctx, sim, accum, aovs, s, 2, cam_of(hs.params), None, faces, first_face(hs), ("moving", k))

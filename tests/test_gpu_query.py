@@ -1,4 +1,4 @@
-"""Ray queries on the MI355X (querykernel.hip): bit for bit the CPU mirror of the kernel's code (tests/querysim), the oracle's closest
+"""Ray queries on the MI355X (querykernel.hip): bit for bit the CPU mirror of the kernel's code (tests/hostsim/querysim.cpp), the oracle's closest
 hits, the AOV pass's ids on the camera rays and moptix_debug_trace's answers -- every ray, exactly."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-"""Mesh updates and the in-place refit on the MI355X (refitkernel.hip): the refitted arrays are the CPU mirror's (tests/refitsim) byte for
+"""Mesh updates and the in-place refit on the MI355X (refitkernel.hip): the refitted arrays are the CPU mirror's (tests/hostsim/refitsim.cpp) byte for
 byte, an identity refit reproduces the built tree, and what renders, AOVs and queries compute on a refitted tree is what a context that
 loaded the moved scene from scratch computes."""
 import ctypes as C
@@ -6,9 +6,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from common import M, oracle_scene
+from common import M, MovedScene, oracle_scene
 from query_helpers import HIT_DTYPE, coffee_rays, same_bits
-from refit_helpers import MovedScene, RefitSim, displace, moved_faces, new_normals, same_words, strip_scene, wide_strip
+from refit_helpers import RefitSim, displace, moved_faces, new_normals, same_words, strip_scene, wide_strip
 
 pytestmark = pytest.mark.gpu
 K = M._capi

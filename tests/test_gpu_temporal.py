@@ -1,5 +1,5 @@
 """Temporal accumulation on the MI355X (temporalkernel.hip): output, motion vectors, history lengths and counters bit for bit the CPU
-mirror of the kernels' code (tests/temporalsim) over moving sequences and on synthetic inputs, the anchor to Context.denoise, no
+mirror of the kernels' code (tests/hostsim/temporalsim.cpp) over moving sequences and on synthetic inputs, the anchor to Context.denoise, no
 effect on anything else the context holds, binding, state errors, the history's life."""
 import ctypes as C
 

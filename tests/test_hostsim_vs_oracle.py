@@ -116,14 +116,9 @@ def test_a_tree_too_wide_for_the_node_grid_has_no_compressed_form(tmp_path):
 def test_sah_topology_needs_fewer_node_fetches_and_gives_the_same_image():
     """The binned-SAH topology (what the reference gets from "Trbvh") against the plain Morton radix tree: same bits
     (the hit is independent of the tree), at least 15 % fewer four-wide node fetches per ray on the coffee scene."""
-    from common import hostsim_lib
     hs = M.HostScene("file:coffee", 160, 90)
     seeds = M.launch_seeds(2)
-    try:
-        hostsim_lib().hostsim_set_builder(0)
-        a, ca = hostsim_render(hs, seeds)
-    finally:
-        hostsim_lib().hostsim_set_builder(1)
+    a, ca = hostsim_render(hs, seeds, builder=0)
     b, cb = hostsim_render(hs, seeds)
     assert np.array_equal(a, b)
     assert cb["nodeFetches"] < 0.85 * ca["nodeFetches"] and cb["triTests"] <= ca["triTests"]

@@ -1,4 +1,4 @@
-"""Ray queries without a GPU: the CPU mirror of the query kernel (tests/querysim: pt_query.h compiled for the host, on the host mirror
+"""Ray queries without a GPU: the CPU mirror of the query kernel (tests/hostsim/querysim.cpp: pt_query.h compiled for the host, on the host mirror
 of the builder's tree) against the CPU oracle's closest hits -- every ray, exactly -- and its hit attributes against the scene's own
 arrays, in numpy."""
 import numpy as np

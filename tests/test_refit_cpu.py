@@ -1,12 +1,12 @@
-"""The mesh refit without a GPU: the CPU mirror (tests/refitsim: pt_refit.h compiled for the host, on the host mirror of the builder's tree)
+"""The mesh refit without a GPU: the CPU mirror (tests/hostsim/refitsim.cpp: pt_refit.h compiled for the host, on the host mirror of the builder's tree)
 against fresh builds of the same positions -- the refitted tree is a valid tree, its triangle records are a fresh build's, and what a
 render or a query computes on it does not depend on which of the two trees it walks (rule D5)."""
 import numpy as np
 import pytest
 
-from common import M, hostsim_bvh, hostsim_render, tree_containment_errors
+from common import M, MovedScene, hostsim_bvh, hostsim_render, tree_containment_errors
 from query_helpers import coffee_rays, querysim, same_bits
-from refit_helpers import MovedScene, RefitSim, displace, extent, moved_faces, new_normals, same_words, wide_strip
+from refit_helpers import RefitSim, displace, extent, moved_faces, new_normals, same_words, wide_strip
 
 K = M._capi
 TREES = [(1, 0), (1, 1), (4, 0), (4, 1), (8, 0), (8, 1)]                      # (leaf size, builder)

@@ -1,5 +1,5 @@
 """Temporal accumulation (include/moptix.h "denoiser: temporal accumulation") without a GPU: the CPU mirror of the kernels
-(tests/temporalsim, the kernels' own per-pixel code from pt_temporal.h) against an independent float64 statement of the contract written
+(tests/hostsim/temporalsim.cpp, the kernels' own per-pixel code from pt_temporal.h) against an independent float64 statement of the contract written
 here from the header's text, the anchor to the spatial denoiser, the properties of reprojection, the history's life, the quality
 on path-traced sequences and the C ABI's host-only entry points."""
 import ctypes as C
@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from common import M, K, hostsim_render, rmse
+from common import M, K, MovedScene, hostsim_render, rmse
 from aov_helpers import aovsim_render
 from denoise_helpers import denoisesim, synthetic_aovs
-from temporal_helpers import (TEMPORAL_DEFAULTS, TemporalSim, MovedScene, cam_params, cam_of, centres_of, copy_spheres, moved_camera,
+from temporal_helpers import (TEMPORAL_DEFAULTS, TemporalSim, cam_params, cam_of, centres_of, copy_spheres, moved_camera,
                               sphere_array)
 
 F = np.float64

@@ -4,7 +4,7 @@ import os, sys, hashlib, random
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
-from common import M, tree_containment_errors, hostsim_render, hostsim_lib   # noqa: E402
+from common import M, tree_containment_errors, hostsim_render   # noqa: E402
 ctx = M.Context(0)
 rng = random.Random(int(os.environ.get("SEED", "1")))
 cases = int(os.environ.get("CASES", "24"))
@@ -77,11 +77,9 @@ for case in range(cases):
                 # walk) on the SAME 64-byte nodes gives the candidate's values at the differing pixels, on the 128-byte nodes the reference's,
                 # the tree is valid, and the damage is a pixel or two.
                 diff = (got != own).any(axis=-1)
-                hostsim_lib().hostsim_set_builder(int(opts.get("builder", 1)))
-                h64, _c = hostsim_render(hs, seeds, leaf_size=int(opts.get("leaf_size", 4)), node_format=64)
-                hostsim_lib().hostsim_set_builder(int(opts.get("builder", 1)))
-                h128, _c = hostsim_render(hs, seeds, leaf_size=int(opts.get("leaf_size", 4)), node_format=128)
-                hostsim_lib().hostsim_set_builder(1)
+                tree = dict(leaf_size=int(opts.get("leaf_size", 4)), builder=int(opts.get("builder", 1)))
+                h64, _c = hostsim_render(hs, seeds, node_format=64, **tree)
+                h128, _c = hostsim_render(hs, seeds, node_format=128, **tree)
                 nodes_, tris_, _p = ctx.debug_read_accel()
                 valid = tree_containment_errors(nodes_, tris_, 0 if len(nodes_) else -1, ctx.debug_read_nodes64()) == 0
                 same64 = float(np.abs(h64[diff] - got[diff]).max()) <= 1e-5 * spp
