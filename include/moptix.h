@@ -271,7 +271,10 @@ int moptix_unpack_tiles(moptix_context ctx, int32_t rank, int32_t nRanks, const 
  *                      is ordered like the first one of a context -- what a single-frame render sees
  *   "comm_blocking"    1 = moptix_comm_init makes a blocking communicator even where a non-blocking one is available (default 0)
  *   "query_blocks_per_cu"  ray queries: the grid's cap in workgroups of 256 rays per CU (default 32, 1..64); a longer batch is walked by
- *                      that grid in a loop, and the stack overflow area is sized by it.  Time and memory only: same results for any value
+ *                      that grid in a loop, and the stack overflow area is sized by it.  Time and memory only: same results for any value.
+ *                      The radiance queries' grid has the same cap
+ *   "radiance_buffer_mb"  radiance queries: the per-sample scratch a launch may use, in MB of 16-byte records (default 256, 1..16384); a
+ *                      call with more samples runs in passes.  Time and memory only: same results for any value
  *   "drain_below"      variant 4: a workgroup of the trace kernel that is down to this many paths (default 64, 0 = never) hands them
  *                      to the drain kernel (csrc/drainkernel.hip: a wave per up to 16 paths, all lanes on one frontier) at their next
  *                      packet boundary and leaves; same image bits, ray and hit counts either way -- the node / triangle-test counts
@@ -568,6 +571,45 @@ enum { MOPTIX_QUERY_CLOSEST = 0, MOPTIX_QUERY_ANY = 1 };
 int moptix_query_rays_device(moptix_context ctx, const float* dRays, int64_t n, int32_t mode, void* dOut);
 int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t mode, void* out);
 
+/* ---- radiance queries: path-traced radiance for the caller's own rays -------------------------------------------------------------
+ * How much light arrives along a ray, from the materials, lights, next-event estimation and shadow rule the frame uses: a probe, a
+ * lightmap texel, another sensor model.  The camera and the frame size play no part; "fast_shading" is not consulted.
+ * A ray is the ray queries' eight floats  ox oy oz dx dy dz tmin tmax, valid or not by their rule (a non-finite component, tmax <= tmin
+ * or a zero direction: invalid; a negative tmin is walked as 0).  THE DIRECTION MUST BE UNIT LENGTH: it is used as given, the shading
+ * code assumes |d| = 1 and nothing renormalises it.  The ray's own tmin and tmax hold for its first segment only; every later segment
+ * of the path is the renderer's (rayEpsilonT and so on).
+ * Each ray gets nSamples samples, one path each.  The RNG state a path starts from:
+ *   seeds    nSamples launch seeds (host memory, copied): sample s of ray i starts from tea16(uint32(indexBase + i), uint32(seeds[s])),
+ *            the camera's rule with the ray's index in the pixel's place; indexBase wraps mod 2^32.  A query cut into calls on ranges
+ *            of the rays, each with indexBase = its first ray's index, equals the one call.
+ *   states   n x nSamples words, ray-major: sample s of ray i starts from states[i * nSamples + s], taken as it is.
+ * Exactly one of the two is given.  The path then runs as a camera path does from depth 1, throughput (1,1,1): rayMaxDepth, bgColor,
+ * the lights and "shadow_rule" act as in a render.  A sample's value is its radiance, unclamped; with MOPTIX_RADIANCE_CLAMP each channel
+ * is clamped to [0, 1] as a frame's samples are (then a camera's rays and the states its lens and jitter draws leave behind reproduce
+ * the accumulation buffer of moptix_render bit for bit).
+ * Output: four floats  r g b t  per ray.
+ *   r g b  the binary32 sum of the ray's sample values in sample order, from +0, by plain adds -- not divided by nSamples.  The bits
+ *          depend neither on the scheduling nor on "query_blocks_per_cu", "radiance_buffer_mb" or the node format.
+ *   t      the first segment's hit distance, with the bits of moptix_hit.t of MOPTIX_QUERY_CLOSEST on the same ray (tmax on a miss): the
+ *          distance to what the radiance came from first, e.g. to place a probe's sample or to weight a texel, without a second query.
+ *   An invalid ray: r = g = b = 0, t = the given tmax; no path is traced for it.
+ * Nodes: the 64-byte form where the tree has one, else the 128-byte one; option "node_format" 64 / 128 forces either (same bits).
+ *   moptix_query_radiance_device  dRays, dOut: device memory, 16-byte aligned; dStates: device memory, 4-byte aligned; seeds: host
+ *                                 memory.  Asynchronous on the context's stream: moptix_sync, or the stream's own synchronisation,
+ *                                 waits for it.  The per-sample scratch ("radiance_buffer_mb") is allocated at first use and kept;
+ *                                 the stack overflow area lives in the context until moptix_clear_scene, moptix_build_accel or
+ *                                 moptix_destroy.  The scene tables are read as they are when the kernel runs.
+ *   moptix_query_radiance         host pointers, blocking: upload, query, read back (staging kept in the context)
+ * n may be any int64 >= 0; n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or misaligned pointers, n < 0, nSamples < 1, both or neither
+ * of seeds and states, unknown flag bits; state errors as moptix_query_rays ("faces dirty" before a refit included).  A radiance
+ * query changes nothing else in the context: not the accumulation buffer, the depth history, the node-format verdict,
+ * moptix_kernel_time, the AOV, denoiser, temporal or adaptive state, nor the ray queries' buffers. */
+enum { MOPTIX_RADIANCE_CLAMP = 1 };
+int moptix_query_radiance_device(moptix_context ctx, const float* dRays, int64_t n, const int32_t* seeds, const uint32_t* dStates,
+                                 int32_t nSamples, uint32_t indexBase, uint32_t flags, float* dOut);
+int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, const int32_t* seeds, const uint32_t* states,
+                          int32_t nSamples, uint32_t indexBase, uint32_t flags, float* out);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
@@ -584,7 +626,7 @@ int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t 
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class

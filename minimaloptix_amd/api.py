@@ -558,6 +558,69 @@ class Context:
         ints = out.view(torch.int32)
         return dict(records=out, t=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], ng=out[:, 5:8])
 
+    def query_radiance(self, rays, seeds=None, states=None, clamp=False, index_base=0):
+        """Path-traced radiance along the caller's rays, n x 8 floats o, d, tmin, tmax with UNIT directions; blocking.  Returns (n, 4)
+        float32 r, g, b, t: rgb the sum (not the mean) of the ray's samples in order, t the first hit's distance (tmax on a miss).
+        seeds: a list of launch seeds, one sample each -- sample s of ray i starts from tea16(index_base + i, seeds[s]); or
+        states: (n, nSamples) uint32 RNG states, taken as they are.  clamp: each sample clamped to [0, 1] as a frame's are.
+        A numpy array takes the host path.  A contiguous (n, 8) float32 torch tensor on this context's device is read where it is (states
+        then a contiguous uint32 or int32 tensor on that device) and the result is a tensor on that device."""
+        if (seeds is None) == (states is None):
+            raise ValueError("query_radiance: give either seeds or states")
+        flags = K.RADIANCE_CLAMP if clamp else 0
+        base = int(index_base) & 0xffffffff
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray((np.asarray(seeds).astype(np.int64).reshape(-1) & 0xffffffff).astype(np.uint32)).view(np.int32)
+            if len(sd) < 1:
+                raise ValueError("query_radiance: an empty seed list")
+        sp = None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_int32))
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):
+            rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
+            n = len(rays)
+            st = None
+            if states is not None:
+                if hasattr(states, "data_ptr"):
+                    raise ValueError("query_radiance: states follow the rays: a numpy array for numpy rays")
+                st = np.asarray(states)
+                if st.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or st.ndim != 2 or st.shape[0] != n or st.shape[1] < 1:
+                    raise ValueError("query_radiance: states must be (n, nSamples) uint32")
+                st = np.ascontiguousarray(st).view(np.uint32)
+            ns = len(sd) if sd is not None else st.shape[1]
+            out = np.zeros((n, 4), np.float32)
+            self._chk(self._L.moptix_query_radiance(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), n, sp,
+                                                    None if st is None else st.ctypes.data_as(C.POINTER(C.c_uint32)), ns, base, flags,
+                                                    out.ctypes.data_as(C.POINTER(C.c_float))))
+            return out
+        import torch
+        tensors = [("rays", rays, ("torch.float32",))]
+        if states is not None:
+            if not hasattr(states, "data_ptr"):
+                raise ValueError("query_radiance: states follow the rays: a tensor on the rays' device")
+            tensors.append(("states", states, ("torch.uint32", "torch.int32")))
+        for name, t, dtypes in tensors:
+            if not t.is_cuda:
+                raise ValueError("query_radiance: %s must live on the GPU (its data_ptr is handed to a kernel); pass numpy arrays for the host path" % name)
+            if str(t.dtype) not in dtypes:
+                raise ValueError("query_radiance: %s has dtype %s" % (name, t.dtype))
+            if t.device.index != self.device:
+                raise ValueError("query_radiance: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
+            if not t.is_contiguous() or t.dim() != 2:
+                raise ValueError("query_radiance: %s must be a contiguous 2-d tensor" % name)
+        if rays.shape[1] != 8:
+            raise ValueError("query_radiance: rays must be (n, 8)")
+        n = rays.shape[0]
+        if states is not None and (states.shape[0] != n or states.shape[1] < 1):
+            raise ValueError("query_radiance: states must be (n, nSamples)")
+        ns = len(sd) if sd is not None else states.shape[1]
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()      # the rays are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_radiance_device(self._h, C.c_void_p(rays.data_ptr()), n, sp,
+                                                       None if states is None else C.c_void_p(states.data_ptr()), ns, base, flags,
+                                                       C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
     # ---- mesh updates and refit (include/moptix.h "mesh updates and refit") ----
     def update_faces(self, first, positions, normals=None):
         """New positions (and normals) of the faces first .. first + n, numbered in upload order: (n, 3, 3) or (n, 9) float32, p0 p1 p2

@@ -65,6 +65,7 @@ struct Options {
   int auxDepth = 16;              // variant 4: depth from which a path's shadow rays get slots of their own (0 = off)
   int queryBlocksPerCU = 32;      // ray queries (querykernel.hip): the grid's cap in workgroups per CU; beyond it lanes loop over rays
   int temporalFaceMotion = 0;     // 1 = moptix_denoise_temporal reprojects moved triangles through their own motion (api_temporal.hip)
+  int radianceBufferMB = 256;     // radiance queries (radiancekernel.hip): the per-sample scratch a launch may use; a longer call runs in passes
 };
 
 }}  // namespace pt::api
@@ -222,6 +223,24 @@ struct moptix_context_t {
     void drop() { overflow.release(); }
     void release() { drop(); rays.release(); out.release(); }
   } query;
+
+  // ---- radiance queries (api_radiance.hip): the per-sample scratch, the work counter and the seeds' device copy, allocated at first use
+  // and kept; the stack overflow area of the radiance kernel, allocated at the first radiance query after a build and dropped with the tree
+  // it was sized for, where the ray queries' is; the staging of the host-pointer entry point ----
+  struct Radiance {
+    DevBuf<int> overflow;
+    DevBuf<float> scratch; DevBuf<int> work, seeds;
+    int* seedStaging = nullptr; size_t seedStagingN = 0;      // pinned: the seeds' upload is asynchronous
+    hipEvent_t seedsUploaded = nullptr;                       // recorded behind that upload: the staging is free again once it has passed
+    DevBuf<float> rays, out; DevBuf<uint32_t> states;
+    void drop() { overflow.release(); }
+    void release() {
+      drop(); scratch.release(); work.release(); seeds.release(); rays.release(); out.release(); states.release();
+      if (seedStaging) (void)hipHostFree(seedStaging);
+      if (seedsUploaded) (void)hipEventDestroy(seedsUploaded);
+      seedStaging = nullptr; seedStagingN = 0; seedsUploaded = nullptr;
+    }
+  } radiance;
 
   // ---- mesh updates and refit (api_refit.hip) ----
   // facesDirty: positions changed since the tree was built or refitted (check_ready refuses to trace); hostStale: the device copy of the

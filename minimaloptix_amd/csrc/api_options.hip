@@ -49,6 +49,7 @@ const Option kOptions[] = {
   { "comm_timeout_ms", &Options::commTimeoutMs, nullptr, 1, INT_MAX, ">= 1" },
   { "comm_blocking", &Options::commBlocking, nullptr, 0, 1, "in {0,1}" },
   { "query_blocks_per_cu", &Options::queryBlocksPerCU, nullptr, 1, 64, "in [1,64]" },
+  { "radiance_buffer_mb", &Options::radianceBufferMB, nullptr, 1, 16384, "in [1,16384]" },
   { "temporal_face_motion", &Options::temporalFaceMotion, nullptr, 0, 1, "in {0,1}", kFaceSnapshot },      // 0 drops the face snapshot
   { "forget_history", nullptr, nullptr, INT_MIN, INT_MAX, "", kTileHistory },      // the next launch orders its work like a context's first (measurement of a cold frame)
   { "comm_nonblocking_used", nullptr, [](moptix_context c) { return c->comm.nonBlocking ? 1 : 0; } },
