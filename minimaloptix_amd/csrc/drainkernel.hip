@@ -70,7 +70,7 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
   return v;
 }
 __device__ __forceinline__ float inv_dir(float d) {
-  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < 1e-30f ? __builtin_copysignf(1e-30f, d) : d);
+  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d);
 }
 __device__ __forceinline__ unsigned long long hit_key(float t, unsigned int prim) { return ((unsigned long long)(uint32_t)f2i(t) << 32) | prim; }
 

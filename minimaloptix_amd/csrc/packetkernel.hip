@@ -129,7 +129,7 @@ struct SlotStack {
 };
 
 __device__ __forceinline__ float node_inv(float d) {      // slab_inv (pt_path.h) with the hardware reciprocal
-  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < 1e-30f ? __builtin_copysignf(1e-30f, d) : d);
+  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d);
 }
 __device__ __forceinline__ int lane_rank(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));

@@ -76,8 +76,8 @@ PT_HD float pad_hi(float v, float padAbs) { return v + (padAbs + 1e-6f * __built
 // Node128 -> Node64.  Every plane moves outwards to the node's 256-step grid, and by a margin of a few ulps more: the
 // kernels fold the decode into the slab test (t = fma(q, step/d, (corner - o)/d), pt_path.h), whose rounding differs from
 // fma(plane, 1/d, -o/d) by about an ulp of the larger coordinate, so the margin keeps the compressed test at least as
-// accepting as the uncompressed one.  Returns false if a step beyond kNode64MaxStep would be needed (|1/d| is capped at
-// 1e30 by slab_inv; step/d has to stay finite): scenes wider than 1e10 units.
+// accepting as the uncompressed one.  Returns false if a step beyond kNode64MaxStep would be needed (chosen when slab_inv capped
+// |1/d| at 1e30, for step/d to stay finite; the cap is 1e19 now, pt_path.h kSlabMinDir): scenes wider than 1e10 units.
 constexpr float kNode64MaxStep = 6.0e7f;
 PT_HD float node64_plane(float corner, float step, int q) { return fma_((float)q, step, corner); }
 PT_HD bool compress_node(const Node128& n, Node64& out) {

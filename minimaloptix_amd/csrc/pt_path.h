@@ -115,10 +115,13 @@ PT_HD void shadow_candidate_tri(const SceneView& sc, int cls, int mat, float t, 
   att = (cls == SHADOW_GLASS) ? load_const(&at32(sc.mats, mat)->color) : mk3(0.f, 0.f, 0.f);
 }
 
-// 1/d for the slab planes.  A direction component below 1e-30 in magnitude is treated as +-1e-30 so that
-// plane*inv and o*inv stay finite (inf - inf would poison the planes); over any t the scene allows, that moves
-// the ray by less than 1e-29, far inside the padding of the boxes.
-PT_HD float slab_inv(float d) { return 1.0f / (__builtin_fabsf(d) < 1e-30f ? __builtin_copysignf(1e-30f, d) : d); }
+// 1/d for the slab planes.  A direction component below kSlabMinDir in magnitude is treated as +-kSlabMinDir so that
+// plane*inv and o*inv stay finite (inf - inf would poison the planes) for coordinates up to 3e19, beyond every scene whose box
+// areas are finite floats; over any t the scene allows, that moves the ray by 1e-19 of the scene's size, far inside the padding
+// of the boxes (1e-5 of it).  (It was 1e-30 until a scene reaching 1e9 units showed that coordinates above 3.4e8 overflowed:
+// DESIGN.md section 2.)
+constexpr float kSlabMinDir = 1e-19f;
+PT_HD float slab_inv(float d) { return 1.0f / (__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d); }
 PT_HD v3 neg_o_inv(v3 o, v3 inv) { return mk3(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z)); }
 
 // Brute-force lists ("NoAccel" groups and the light geometry) + set-up of the BVH walk.

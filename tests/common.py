@@ -64,6 +64,7 @@ def hostsim_lib():
         sig("hostsim_create", [C.POINTER(HostsimScene), C.c_int, C.c_int], vp)
         sig("hostsim_free", [vp], None)
         sig("hostsim_read_bvh", [vp, C.POINTER(HostsimBvhOut)])
+        sig("hostsim_read_sah_levels", [vp, i32p, i32p, C.c_int])
         sig("hostsim_debug_ray", [vp, f32p, f32p, C.c_float, C.c_int])
         sig("hostsim_render", [vp, C.c_int, C.c_int, i32p, C.c_int, f32p, u64p, C.POINTER(C.c_double)])
         sig("aovsim_render_aovs", [vp, C.c_int, i32p, C.c_int, C.POINTER(AovsimBuffers)])
@@ -195,6 +196,17 @@ def hostsim_bvh(hs, leaf_size=4, builder=1, want_nodes64=False):
     if want_nodes64:
         return nodes[:out.nNodes], tris[:sim.n_faces], prim[:sim.n_faces], out.rootRef, out.depth, n64[:out.nNodes]
     return nodes[:out.nNodes], tris[:sim.n_faces], prim[:sim.n_faces], out.rootRef, out.depth
+
+
+def hostsim_sah_levels(hs, leaf_size=4, builder=1):
+    """The level table of the mirror's SAH build: an int32 [levels, 2] array of (active nodes, the largest node's triangle count) per
+    level, top down; no rows for builder 0.  hs: a scene, or a built one."""
+    sim = hostsim_handle(hs, leaf_size, builder)
+    cap = 256
+    nodes = np.zeros(cap, np.int32); largest = np.zeros(cap, np.int32)
+    n = hostsim_lib().hostsim_read_sah_levels(sim._h, _ptr(nodes, C.c_int32), _ptr(largest, C.c_int32), cap)
+    assert 0 <= n <= cap
+    return np.stack([nodes[:n], largest[:n]], axis=1)
 
 
 class MovedScene:

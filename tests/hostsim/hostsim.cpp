@@ -39,7 +39,8 @@ static int subtree_depth(const std::vector<Node128>& nodes, int ref) {
 struct SahTask { int node, first, count; v3 cbLo, cbHi; };
 // forcedRootSplit: the device's SahTask::force of the root task
 static void build_sah_topology(const std::vector<v3>& lo, const std::vector<v3>& hi, std::vector<int>& order, v3 cbLo, v3 cbHi,
-                               int leafSize, int forcedRootSplit, std::vector<KarrasNode>& nodes, std::vector<int>& parentI, std::vector<int>& parentL) {
+                               int leafSize, int forcedRootSplit, std::vector<KarrasNode>& nodes, std::vector<int>& parentI, std::vector<int>& parentL,
+                               std::vector<int>& levelNodes, std::vector<int>& levelLargest) {
   const int n = (int)order.size();
   nodes.assign(n - 1, KarrasNode{ 0, 0, 0, 0 }); parentI.assign(n - 1, -1); parentL.assign(n, -1);
   std::vector<SahTask> tasks{ SahTask{ 0, 0, n, cbLo, cbHi } }, next;
@@ -49,6 +50,9 @@ static void build_sah_topology(const std::vector<v3>& lo, const std::vector<v3>&
     next.clear();
     if (getenv("HOSTSIM_DEBUG")) fprintf(stderr, "[hostsim] SAH level %d: %zu nodes\n", level, tasks.size());
     const int nextBase = idBase + (int)tasks.size();
+    int largest = 0;
+    for (const SahTask& t : tasks) largest = std::max(largest, t.count);
+    levelNodes.push_back((int)tasks.size()); levelLargest.push_back(largest);
     for (const SahTask& t : tasks) {
       SahSplit sp; sp.axis = -1; sp.bin = 0; sp.nLeft = (t.count + 1) / 2;
       // HOSTSIM_SWEEP=1 -- a YARDSTICK, not the device's builder: the exact surface-area heuristic, every one of the
@@ -182,6 +186,7 @@ static void esc_split(const v3 tri[3], v3 lo, v3 hi, double triArea2, double k, 
 
 void hostsim::build_lbvh(const hostsim_scene& s, int leafSize, int builder, HostBVH& out) {
   out.nodes.clear(); out.nodes64.clear(); out.tris.clear(); out.shade.clear(); out.rootRef = kEmptyRef; out.depth = 0;
+  out.levelNodes.clear(); out.levelLargest.clear();
   if (s.nFaces <= 0) return;
   // references: one per face, or (HOSTSIM_ESC) several clipped boxes of one face
   std::vector<int> refFace; std::vector<v3> lo, hi;
@@ -220,7 +225,7 @@ void hostsim::build_lbvh(const hostsim_scene& s, int leafSize, int builder, Host
     std::vector<int> order(n);
     for (int k = 0; k < n; k++) order[k] = key_face(keys[k], idxBits);
     // large triangles first (pt_lbvh.h kSmallKeyBit): the root's range is split between them and the others
-    build_sah_topology(lo, hi, order, clo, chi, leafSize, big_key_count(keys.data(), n), sahNodes, sahParentI, sahParentL);
+    build_sah_topology(lo, hi, order, clo, chi, leafSize, big_key_count(keys.data(), n), sahNodes, sahParentI, sahParentL, out.levelNodes, out.levelLargest);
     for (int k = 0; k < n; k++) keys[k] = (uint64_t)order[k];              // the device keeps the face index only, too
   }
 
@@ -385,6 +390,15 @@ int hostsim_read_bvh(void* h, hostsim_bvh_out* out) {
   if (out->tris && !b.tris.empty()) memcpy(out->tris, b.tris.data(), b.tris.size() * sizeof(Tri48));
   if (out->triPrim) for (size_t i = 0; i < b.tris.size(); i++) out->triPrim[i] = b.tris[i].prim;
   return 0;
+}
+
+// The level table of the mirror's SAH build (builder 1; none for builder 0): per level the number of active nodes and the largest node's
+// triangle count, up to `cap` levels.  Returns the number of levels.
+int hostsim_read_sah_levels(void* h, int32_t* nodes, int32_t* largest, int cap) {
+  const HostBVH& b = static_cast<HostSim*>(h)->hs.bvh;
+  const int n = (int)b.levelNodes.size();
+  for (int i = 0; i < n && i < cap; i++) { if (nodes) nodes[i] = b.levelNodes[i]; if (largest) largest[i] = b.levelLargest[i]; }
+  return n;
 }
 
 // Debugging aid: where does a ray lose a triangle?  Prints, for every node on the way from the root to the leaf that holds

@@ -37,6 +37,7 @@ using namespace pt;
 struct HostBVH {
   std::vector<Node128> nodes; std::vector<Node64> nodes64; std::vector<Tri48> tris; std::vector<TriShade> shade;
   int rootRef = kEmptyRef; int depth = 0;
+  std::vector<int> levelNodes, levelLargest;      // per SAH level of the build: active nodes, the largest node's triangle count (builder 1)
 };
 
 struct HostScene {
