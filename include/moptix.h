@@ -610,6 +610,60 @@ int moptix_query_radiance_device(moptix_context ctx, const float* dRays, int64_t
 int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, const int32_t* seeds, const uint32_t* states,
                           int32_t nSamples, uint32_t indexBase, uint32_t flags, float* out);
 
+/* ---- point queries: the nearest surface point for the caller's own points ------------------------------------------------------------
+ * What is the nearest point of the scene's surface to q, and how far is it: contact and collision, sampling a distance field,
+ * closest-point correspondences, proximity masks -- on the tree the rays walk, refitted with it.
+ * A query is four floats  x y z maxDist, read as one 16-byte load.  r2 = maxDist * maxDist, one binary32 multiply; maxDist = +inf is
+ * allowed and means "no limit".  Needs moptix_set_params and moptix_build_accel like a ray query; the camera and the frame size play no part.
+ * Per primitive there is a function d2(q, primitive): the squared distance from q to the nearest point c of the primitive, in binary32
+ * under the arithmetic contract of csrc/pt_math.h (AC1-AC5, no contraction, correctly rounded division and square root).  It depends on
+ * q and the primitive's device record alone; csrc/pt_point.h states every operation in order.  d2 = dot(q - c, q - c) throughout.
+ *   segment (a, ab)  den = dot(ab, ab); t = clamp(dot(q - a, ab) / den, 0, 1), t = 0 when den is 0; c = a + ab * t.  Here and for the
+ *              quad, clamp(x, 0, 1) is x > 0 ? (x < 1 ? x : 1) : 0 by comparisons: -0 and NaN give +0
+ *   triangle   the triangle of the device record, v0 = p0, v1 = p0 + e0, v2 = p0 - e1 (e0 = p1 - p0 and e1 = p0 - p2 as stored: the
+ *              triangle the ray test sees).  The minimum of up to four candidates, the first of equal ones: the segments (v0, e0),
+ *              (v0, -e1), (v1, v2 - v1), and the plane projection c = (v0 + bu * e0) + bv * (-e1) with bu, bv the barycentrics of step 2 of
+ *              moptix_denoise_temporal (e1 = e0, e2 = -e1 of the record, w = q - v0, unclamped) evaluated with the normal scaled by a
+ *              power of two so that its largest component lies in [1, 2) -- dot(n, n) itself leaves binary32 for edges beyond 4e9 or
+ *              below 1e-10 units.  The projection applies when the normal is non-zero and finite and
+ *              bu >= 0, bv >= 0, bu + bv <= 1.  A zero-area triangle is thereby well defined: collinear vertices count as the longest of
+ *              the three segments, coincident vertices as a point, and no NaN comes out of finite input.
+ *   sphere     the surface: c = centre + radius * normalize(q - centre), with the direction (1, 0, 0) when q is the centre
+ *   quad       the rectangle in the ray test's own parametrisation: a1 = clamp(dot(v1, q - anchor), 0, 1), a2 = clamp(dot(v2, q - anchor),
+ *              0, 1), c = (anchor + a1 * E1) + a2 * E2 with E1 = v1 / dot(v1, v1), E2 = v2 / dot(v2, v2), the edges moptix_quad_params holds
+ *              inverted
+ * MOPTIX_POINT_CLOSEST -> one moptix_point_hit (32 bytes) per query: the primitive least by (d2, prim) among those with d2 < r2; at
+ * exactly equal d2 the lower prim wins (rule D5).  The answer is a function of the per-primitive d2 alone -- what a loop over every
+ * primitive gives, bit for bit: tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part.  Every primitive
+ * counts, whatever its material.
+ *   dist  sqrt(d2) of the winner, one correctly rounded square root
+ *   prim  primitive id in the ray queries' numbering: spheres, then quads, then triangles by original face id; -1 = miss
+ *   mat   material id of the primitive; -1 on a miss
+ *   u, v  triangles: the weights of the face's second and third vertex, c = p0 + u (p1 - p0) + v (p2 - p0) up to rounding; quads: a1, a2;
+ *         spheres: 0
+ *   p     the nearest point c
+ *   miss  dist = the given maxDist, prim = mat = -1, every other field 0
+ * MOPTIX_POINT_ANY -> one int32 per query: 1 if and only if the closest mode on the same query reports prim >= 0, else 0; the walk stops
+ * at the first primitive it accepts.
+ * Invalid queries are misses, decided before any traversal: x, y or z non-finite, maxDist NaN, or maxDist <= 0.
+ * The distance is UNSIGNED.  A sign needs a watertight mesh and angle-weighted pseudonormals at edges and vertices; neither is assumed
+ * or built here: signed distance is out of scope.
+ * Nodes: the 64-byte form where the tree has one, else the 128-byte one; option "node_format" 64 / 128 forces either (same bits: the
+ * 64-byte boxes contain the 128-byte ones, so the walk enters more boxes and finds the same minimum).
+ *   moptix_query_points_device  dPoints, dOut: device memory, 16-byte aligned (dOut of MOPTIX_POINT_ANY: 4).  Asynchronous on the
+ *                               context's stream: moptix_sync, or the stream's own synchronisation, waits for it.  Allocates nothing
+ *                               after the first point query on a tree: the point queries keep a stack overflow area of their own,
+ *                               kept across refits, until moptix_clear_scene, moptix_build_accel or moptix_destroy.  The sphere and quad
+ *                               tables are read as they are when the kernel runs: a query after moptix_update_spheres sees the moved spheres.
+ *   moptix_query_points         host pointers, blocking: upload, query, read back (staging kept in the context)
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 points); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_rays ("faces dirty" before a refit included).  A point query
+ * changes nothing else in the context, and in particular not the ray queries' buffers; moptix_debug_buffer_addresses keeps its slots. */
+typedef struct { float dist; int32_t prim; int32_t mat; float u, v; float p[3]; } moptix_point_hit;
+enum { MOPTIX_POINT_CLOSEST = 0, MOPTIX_POINT_ANY = 1 };
+int moptix_query_points_device(moptix_context ctx, const float* dPoints, int64_t n, int32_t mode, void* dOut);
+int moptix_query_points(moptix_context ctx, const float* points, int64_t n, int32_t mode, void* out);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
@@ -626,7 +680,7 @@ int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, cons
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -641,7 +695,7 @@ int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, cons
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray queries' stack overflow area (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray and point queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

@@ -161,6 +161,14 @@ class Hit(C.Structure):
 
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+
+
+class PointHit(C.Structure):
+    """moptix_point_hit: the record of a closest-point query (32 bytes)."""
+    _fields_ = [("dist", C.c_float), ("prim", C.c_int32), ("mat", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("p", C.c_float * 3)]
+
+
+POINT_CLOSEST, POINT_ANY = 0, 1
 RADIANCE_CLAMP = 1
 
 
@@ -190,6 +198,7 @@ DEVICE_SYMBOLS = [
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
     "moptix_query_rays_device", "moptix_query_rays", "moptix_query_radiance_device", "moptix_query_radiance",
+    "moptix_query_points_device", "moptix_query_points",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -288,6 +297,8 @@ def device_lib():
         u32p = C.POINTER(C.c_uint32)
         L.moptix_query_radiance_device.argtypes = [vp, vp, C.c_int64, i32p, vp, i32, C.c_uint32, C.c_uint32, vp]
         L.moptix_query_radiance.argtypes = [vp, f32p, C.c_int64, i32p, u32p, i32, C.c_uint32, C.c_uint32, f32p]
+        L.moptix_query_points_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_points.argtypes = [vp, f32p, C.c_int64, i32, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]
         L.moptix_update_faces_device.argtypes = [vp, i32, i32, vp, vp]
         L.moptix_refit_accel.argtypes = [vp]

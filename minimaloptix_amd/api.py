@@ -11,6 +11,8 @@ from ._capi import MoptixError
 # moptix_hit as a numpy record (include/moptix.h "ray queries")
 HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("ng", np.float32, (3,))])
 assert HIT_DTYPE.itemsize == C.sizeof(K.Hit) == 32
+POINT_DTYPE = np.dtype([("dist", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("p", np.float32, (3,))])
+assert POINT_DTYPE.itemsize == C.sizeof(K.PointHit) == 32
 
 
 def scenes_dir():
@@ -620,6 +622,54 @@ class Context:
                                                        C.c_void_p(out.data_ptr())))
         self.sync()
         return out
+
+    # ---- point queries (include/moptix.h "point queries") ----
+    POINT_MODES = dict(closest=K.POINT_CLOSEST, any=K.POINT_ANY)
+
+    def query_points(self, points, mode="closest", max_dist=np.inf):
+        """The nearest surface point ("closest") or "is anything within max_dist" ("any") for the caller's points; blocking.
+        A numpy array takes the host path: (n, 3) positions with max_dist a scalar or an (n,) array, or (n, 4) rows x y z maxDist
+        (max_dist is then not consulted).  "closest" returns a POINT_DTYPE record array (dist, prim, mat, u, v, p), "any" an int32 array.
+        A contiguous (n, 4) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
+        "any" an int32 tensor; "closest" a dict of views dist, prim, mat, u, v, p into "records", the (n, 8) float32 tensor of the raw
+        moptix_point_hit records."""
+        if mode not in self.POINT_MODES:
+            raise ValueError("query_points: mode %r (closest or any)" % (mode,))
+        m = self.POINT_MODES[mode]
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            pts = np.asarray(points, np.float32)
+            if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+                raise ValueError("query_points: points must be (n, 3) or (n, 4), not %r" % (pts.shape,))
+            if pts.shape[1] == 3:
+                md = np.asarray(max_dist, np.float32)
+                if md.ndim > 1 or (md.ndim == 1 and len(md) != len(pts)):
+                    raise ValueError("query_points: max_dist must be a scalar or one value per point")
+                pts = np.concatenate([pts, np.broadcast_to(md.reshape(-1, 1) if md.ndim else md, (len(pts), 1))], axis=1)
+            pts = np.ascontiguousarray(pts, np.float32)
+            out = np.zeros(len(pts), POINT_DTYPE if m == K.POINT_CLOSEST else np.int32)
+            self._chk(self._L.moptix_query_points(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), m, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        if not points.is_cuda:
+            raise ValueError("query_points: the tensor must live on the GPU (its data_ptr is handed to a kernel); pass a numpy array for the host path")
+        if str(points.dtype) != "torch.float32":
+            raise ValueError("query_points: dtype %s" % points.dtype)
+        if points.device.index != self.device:
+            raise ValueError("query_points: the tensor is on %s, the context on GPU %d" % (points.device, self.device))
+        if not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 4:
+            raise ValueError("query_points: must be a contiguous (n, 4) tensor x y z maxDist")
+        n = points.shape[0]
+        if m == K.POINT_ANY:
+            out = torch.empty(n, dtype=torch.int32, device=points.device)
+        else:
+            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+        torch.cuda.current_stream(points.device).synchronize()      # the points are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_points_device(self._h, C.c_void_p(points.data_ptr()), n, m, C.c_void_p(out.data_ptr())))
+        self.sync()
+        if m == K.POINT_ANY:
+            return out
+        ints = out.view(torch.int32)
+        return dict(records=out, dist=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], p=out[:, 5:8])
 
     # ---- mesh updates and refit (include/moptix.h "mesh updates and refit") ----
     def update_faces(self, first, positions, normals=None):

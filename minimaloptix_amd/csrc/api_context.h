@@ -242,6 +242,16 @@ struct moptix_context_t {
     }
   } radiance;
 
+  // ---- point queries (api_point.hip): the stack overflow area of the point kernel, its own (eight bytes an entry: reference + box
+  // distance), allocated at the first point query after a build and dropped with the tree it was sized for, where the ray queries' is;
+  // the staging of the host-pointer entry point ----
+  struct Point {
+    DevBuf<unsigned long long> overflow;
+    DevBuf<float> points; DevBuf<uint8_t> out;
+    void drop() { overflow.release(); }
+    void release() { drop(); points.release(); out.release(); }
+  } point;
+
   // ---- mesh updates and refit (api_refit.hip) ----
   // facesDirty: positions changed since the tree was built or refitted (check_ready refuses to trace); hostStale: the device copy of the
   // faces is ahead of the host staging (moptix_update_faces_device; moptix_build_accel fetches it back first); facesOnDevice: how many

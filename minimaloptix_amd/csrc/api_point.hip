@@ -1,0 +1,74 @@
+// api_point.hip -- closest-point queries (pointkernel.hip, pt_point.h): the two moptix_query_points* entry points of include/moptix.h.
+#include <cstring>
+
+#include "api_context.h"
+#include "pt_point.h"
+#include "pointkernel.h"
+
+using namespace pt;
+using namespace pt::api;
+
+static_assert(sizeof(moptix_point_hit) == sizeof(PointHit), "moptix_point_hit is the kernel's record");
+static_assert(MOPTIX_POINT_CLOSEST == POINT_CLOSEST && MOPTIX_POINT_ANY == POINT_ANY, "point query modes");
+
+namespace {
+
+size_t out_bytes(int32_t mode) { return mode == MOPTIX_POINT_ANY ? sizeof(int32_t) : sizeof(moptix_point_hit); }
+
+int check_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out) {
+  const int rc = check_ready(c);
+  if (rc != MOPTIX_OK) return rc;
+  if (n < 0 || (mode != MOPTIX_POINT_CLOSEST && mode != MOPTIX_POINT_ANY)) return fail(c, MOPTIX_ERR_INVALID, "bad point count or query mode");
+  if (n > 0 && (!points || !out)) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  return MOPTIX_OK;
+}
+
+// Enqueues the query on the context's stream, in launches of at most kPointMaxLaunch points.  The stack overflow area is the point
+// queries' own: allocated at the first point query after a build, reused by every later one.
+int enqueue_points(moptix_context c, const float* dPoints, int64_t n, int32_t mode, void* dOut) {
+  PointArgs a;
+  memset(&a, 0, sizeof(a));
+  fill_view(c, a.scene);                                  // the node-format verdict of the render path is not consulted
+  const bool node64 = c->bvh.nodes64 != nullptr && c->opt.nodeFormat != 128 && a.scene.rootRef != kEmptyRef;
+  a.scene.nodes64 = node64 ? c->bvh.nodes64 : nullptr;
+  const int nBlocks = pointkernel_blocks(c->numCUs, c->opt.queryBlocksPerCU);
+  const size_t ovf = a.scene.rootRef != kEmptyRef ? pointkernel_overflow_entries(nBlocks, c->bvh.stackBound) : 0;
+  if (ovf > 0) {
+    HIPCHK(c, c->point.overflow.ensure(ovf), "alloc point query stack overflow area");
+    a.stackOverflow = c->point.overflow.p;
+  }
+  for (int64_t first = 0; first < n; first += kPointMaxLaunch) {
+    a.points = dPoints + 4 * first;
+    a.out = static_cast<char*>(dOut) + out_bytes(mode) * (size_t)first;
+    a.n = (int)(n - first < kPointMaxLaunch ? n - first : kPointMaxLaunch);
+    HIPCHK(c, launch_pointquery(c->stream, a, nBlocks, mode), "launch point query");
+  }
+  return MOPTIX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int moptix_query_points_device(moptix_context c, const float* dPoints, int64_t n, int32_t mode, void* dOut) {
+  int rc = check_points(c, dPoints, n, mode, dOut);
+  if (rc != MOPTIX_OK || n == 0) return rc;
+  if ((reinterpret_cast<uintptr_t>(dPoints) & 15u) != 0 || (reinterpret_cast<uintptr_t>(dOut) & (mode == MOPTIX_POINT_ANY ? 3u : 15u)) != 0)
+    return fail(c, MOPTIX_ERR_INVALID, "point queries read points and write records 16 bytes at a time: misaligned device pointer");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  return enqueue_points(c, dPoints, n, mode, dOut);
+}
+
+int moptix_query_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out) {
+  int rc = check_points(c, points, n, mode, out);
+  if (rc != MOPTIX_OK || n == 0) return rc;
+  if ((rc = begin_call(c, false)) != MOPTIX_OK) return rc;
+  const size_t bytes = out_bytes(mode) * (size_t)n;
+  HIPCHK(c, c->point.points.ensure(4 * (size_t)n), "alloc query points");
+  HIPCHK(c, c->point.out.ensure(bytes), "alloc point query results");
+  HIPCHK(c, hipMemcpyAsync(c->point.points.p, points, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream), "upload query points");
+  if ((rc = enqueue_points(c, c->point.points.p, n, mode, c->point.out.p)) != MOPTIX_OK) return rc;
+  return read_back(c, { { out, c->point.out.p, bytes } }, "read point query results");
+}
+
+}  // extern "C"

@@ -1,0 +1,23 @@
+// pointkernel.h -- launch interface of pointkernel.hip (closest-point queries, pt_point.h)
+#pragma once
+#include <hip/hip_runtime.h>
+#include "pt_types.h"
+
+namespace pt {
+
+struct PointArgs {
+  SceneView scene;                // nodes64 set = walk the 64-byte nodes
+  const float* points;            // n x 4 floats x y z maxDist, 16-byte aligned (device)
+  void* out;                      // closest: n x PointHit (16-byte aligned); any: n x int32 (device)
+  int n;                          // points of this launch (the host cuts longer batches: indices stay 32-bit)
+  unsigned long long* stackOverflow;   // per-thread spill area (reference + box distance per entry) for trees deeper than the LDS stack, or null
+};
+constexpr int kPointMaxLaunch = 1 << 30;      // points per launch
+
+int pointkernel_lds_stack_entries();
+int pointkernel_blocks(int nCUs, int blocksPerCU);
+size_t pointkernel_overflow_entries(int nBlocks, int stackBound);     // 8-byte entries; 0 = the tree fits the LDS stack
+// mode: POINT_CLOSEST / POINT_ANY (pt_point.h).  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
+hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode);
+
+}  // namespace pt

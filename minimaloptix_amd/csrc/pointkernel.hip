@@ -1,0 +1,96 @@
+// pointkernel.hip -- closest-point queries (pt_point.h) for gfx950: the nearest surface point, or "is anything within maxDist", for
+// caller-supplied points.
+//
+// Its own translation unit, as the ray-query kernel's: nothing of this pass is compiled into the trace kernels.
+//
+// Execution model: the ray queries' (querykernel.hip).  One point per lane, walked to its end with the if-if step (pt_point.h point_step).
+// The grid is ceil(n / 256) workgroups up to a cap of CUs x blocksPerCU; past the cap a lane goes on to the point one grid further
+// (grid-stride loop), so the stack overflow area is sized by the cap, not by n, and a result goes to its point's own index: nothing depends
+// on the scheduling.  A point is read as one 16-byte load, a record written as two 16-byte stores.
+// The traversal stack holds a child reference and the squared distance to its box side by side, eight bytes an entry: 16 entries per lane
+// in LDS ([entry][lane], 32 KB per workgroup as the ray queries' 32 four-byte ones) with a global overflow column per thread.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "pt_point.h"
+#include "pointkernel.h"
+
+namespace pt {
+
+namespace {
+
+constexpr int kBlockThreads = 256;
+constexpr int kWavesPerBlock = kBlockThreads / 64;
+constexpr int kLdsStack = 16;          // entries per lane kept in LDS (8 bytes each: 32 KB per workgroup)
+
+// LDS stack [entry][lane] with a global overflow column per thread: querykernel.hip's QueryStack (itself megakernel.hip's LaneStack, copied
+// for the reason given there: sharing it means editing files whose code objects this change leaves bit for bit alone), with the entry
+// widened to reference + box distance.
+struct PointStack {
+  unsigned long long* lds;
+  unsigned long long* ovf;       // this thread's overflow column (stride = ovfStride) or nullptr
+  int ovfStride;
+  __device__ __forceinline__ void store(int sp, int ref, float d2) {
+    const unsigned long long e = ((unsigned long long)(uint32_t)f2i(d2) << 32) | (uint32_t)ref;
+    if (sp < kLdsStack) lds[sp * 64] = e;
+    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = e;
+  }
+  __device__ __forceinline__ void load(int sp, int& ref, float& d2) const {
+    const unsigned long long e = sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
+    ref = (int32_t)(uint32_t)e; d2 = i2f((int32_t)(e >> 32));
+  }
+};
+
+template <bool ANY, bool N64>
+__global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a) {
+  __shared__ unsigned long long ldsStack[kWavesPerBlock * kLdsStack * 64];
+  const SceneView& sc = a.scene;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
+  PointStack st;
+  st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
+  st.ovfStride = stride;
+  st.ovf = a.stackOverflow ? a.stackOverflow + gthread : nullptr;
+  const uint4* __restrict__ points = reinterpret_cast<const uint4*>(a.points);
+  for (int i = gthread; i < a.n; i += stride) {           // n <= kPointMaxLaunch = 2^30 and stride <= 2^22: no overflow
+    const uint4 r = points[(size_t)i];
+    const float p[4] = { i2f((int32_t)r.x), i2f((int32_t)r.y), i2f((int32_t)r.z), i2f((int32_t)r.w) };
+    const v3 q = mk3(p[0], p[1], p[2]);
+    PointTrav tv;
+    point_begin<ANY>(sc, q, p[3] * p[3], point_valid(p), tv);
+    while (tv.node != kTravDone) point_step<ANY, N64>(sc, q, tv, st);
+    if constexpr (ANY) {
+      static_cast<int*>(a.out)[i] = tv.bestPrim >= 0 ? 1 : 0;
+    } else {
+      PointHit h;
+      point_hit(sc, q, p[3], tv, h);
+      uint4* o = static_cast<uint4*>(a.out) + 2 * (size_t)i;
+      o[0] = make_uint4((uint32_t)f2i(h.dist), (uint32_t)h.prim, (uint32_t)h.mat, (uint32_t)f2i(h.u));
+      o[1] = make_uint4((uint32_t)f2i(h.v), (uint32_t)f2i(h.p[0]), (uint32_t)f2i(h.p[1]), (uint32_t)f2i(h.p[2]));
+    }
+  }
+}
+
+}  // namespace
+
+int pointkernel_lds_stack_entries() { return kLdsStack; }
+int pointkernel_blocks(int nCUs, int blocksPerCU) { return (nCUs > 0 ? nCUs : 256) * blocksPerCU; }
+size_t pointkernel_overflow_entries(int nBlocks, int stackBound) {
+  return stackBound > kLdsStack ? (size_t)nBlocks * kBlockThreads * (size_t)(stackBound - kLdsStack + 1) : 0;
+}
+
+hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode) {
+  const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);
+  const bool n64 = a.scene.nodes64 != nullptr;
+  if (mode == POINT_ANY) {
+    if (n64) pt_pointquery<true, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery<true, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+  } else {
+    if (n64) pt_pointquery<false, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery<false, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace pt
