@@ -15,7 +15,6 @@ struct AovArgs {
   int* stackOverflow;               // per-thread spill area for trees deeper than the LDS stack (or null)
 };
 
-int aovkernel_lds_stack_entries();
 int aovkernel_threads(int nCUs);    // threads of a launch (the overflow area holds aovkernel_overflow_ints of them)
 size_t aovkernel_overflow_ints(int nCUs, int stackBound);
 // node64: walk scene.nodes64 (must be non-null) instead of scene.nodes.  tileCounter: one int of device memory, the waves' tile

@@ -15,6 +15,7 @@
 
 #include "aovkernel.h"
 #include "pt_aov.h"
+#include "pt_lanestack.h"
 
 namespace pt {
 
@@ -25,32 +26,13 @@ constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kLdsStack = 32;          // entries per lane kept in LDS (32 KB per workgroup)
 constexpr int kBlocksPerCU = 4;
 
-// LDS stack [entry][lane] with a global overflow column per thread (as megakernel.hip's LaneStack)
-struct AovStack {
-  int* lds;
-  int* ovf;       // this thread's overflow column (stride = ovfStride) or nullptr
-  int ovfStride;
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (sp < kLdsStack) lds[sp * 64] = v;
-    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    return sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kLdsStack; }
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp * 64] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
-
 // N64: walk the 64-byte nodes (sc.nodes64), else the 128-byte ones.  tileCounter: zeroed before the launch.
 template <bool N64>
 __global__ void __launch_bounds__(kBlockThreads) pt_aovkernel(const AovArgs a, int* tileCounter) {
   __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
   const SceneView& sc = a.scene;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  AovStack st;
+  LaneStack<kLdsStack> st;      // not st.init: this kernel adds the block's and the thread's offset to the pointer one after the other
   st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
   st.ovfStride = gridDim.x * kBlockThreads;
   st.ovf = a.stackOverflow ? a.stackOverflow + blockIdx.x * kBlockThreads + threadIdx.x : nullptr;
@@ -111,11 +93,8 @@ int aov_blocks(int nCUs) { return (nCUs > 0 ? nCUs : 256) * kBlocksPerCU; }
 
 }  // namespace
 
-int aovkernel_lds_stack_entries() { return kLdsStack; }
 int aovkernel_threads(int nCUs) { return aov_blocks(nCUs) * kBlockThreads; }
-size_t aovkernel_overflow_ints(int nCUs, int stackBound) {
-  return stackBound > kLdsStack ? (size_t)aovkernel_threads(nCUs) * (size_t)(stackBound - kLdsStack + 1) : 0;
-}
+size_t aovkernel_overflow_ints(int nCUs, int stackBound) { return lane_stack_overflow_entries(aovkernel_threads(nCUs), stackBound, kLdsStack); }
 
 hipError_t launch_aovkernel(hipStream_t stream, const AovArgs& a, int nCUs, int* tileCounter, bool node64) {
   const long long nTiles = (long long)((a.scene.width + 7) / 8) * ((a.scene.height + 7) / 8);

@@ -297,6 +297,9 @@ int begin_call(moptix_context c, bool withAccum);
 struct ReadBack { void* dst; const void* src; size_t bytes; };
 int read_back(moptix_context c, std::initializer_list<ReadBack> copies, const char* what);
 void fill_view(moptix_context c, SceneView& v);
+// The scene as a query sees it (api_query.hip, api_radiance.hip, api_point.hip): the 64-byte nodes wherever the tree has them and option
+// "node_format" does not say 128 -- the node-format verdict of the render path is not consulted.  Returns the launch's cap of workgroups.
+int fill_query_view(moptix_context c, SceneView& v);
 moptix_aov_buffers aov_ptrs(moptix_context c);       // api_aov.hip: bound or own, member by member
 void comm_release(moptix_context c);                 // api_comm.hip: destroys the communicator, frees the staging
 // api_denoise.hip, for moptix_denoise and moptix_denoise_temporal alike: the context is usable and has AOV samples, begin_call, the

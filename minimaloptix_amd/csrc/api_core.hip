@@ -6,7 +6,9 @@
 #include <cstring>
 
 #include "api_context.h"
+#include "pt_lanestack.h"
 #include "pt_upload.h"
+#include "querykernel.h"
 
 using namespace pt;
 using namespace pt::api;
@@ -71,6 +73,13 @@ void fill_view(moptix_context c, SceneView& v) {
   v.nodes = c->bvh.nodes; v.nodes64 = c->nodeFormatUsed == 64 ? c->bvh.nodes64 : nullptr; v.tris = c->bvh.tris; v.triShade = c->bvh.shade;
   v.triUV = (c->anyUV && c->bvh.nTris > 0) ? c->dFaceUV.p : nullptr;
   v.nTextures = (int)c->textures.size(); v.textures = c->dTextures.p;
+}
+
+int fill_query_view(moptix_context c, SceneView& v) {
+  fill_view(c, v);
+  const bool node64 = c->bvh.nodes64 != nullptr && c->opt.nodeFormat != 128 && v.rootRef != kEmptyRef;
+  v.nodes64 = node64 ? c->bvh.nodes64 : nullptr;
+  return querykernel_blocks(c->numCUs, c->opt.queryBlocksPerCU);
 }
 
 int check_ready(moptix_context c) {
@@ -491,10 +500,8 @@ int moptix_debug_trace(moptix_context c, const float* rays, int32_t n, float* ou
   hipError_t e = hipMalloc((void**)&dR, sizeof(float) * 8 * (size_t)n);
   if (e == hipSuccess) e = hipMalloc((void**)&dT, sizeof(float) * (size_t)n);
   if (e == hipSuccess) e = hipMalloc((void**)&dP, sizeof(int) * (size_t)n);
-  if (e == hipSuccess && c->bvh.stackBound > megakernel_lds_stack_entries()) {
-    const size_t threads = ((size_t)n + 255) / 256 * 256;
-    e = hipMalloc((void**)&dOvf, sizeof(int) * threads * (size_t)(c->bvh.stackBound - megakernel_lds_stack_entries() + 1));
-  }
+  const size_t ovf = lane_stack_overflow_entries(((size_t)n + 255) / 256 * 256, c->bvh.stackBound, megakernel_lds_stack_entries());
+  if (e == hipSuccess && ovf > 0) e = hipMalloc((void**)&dOvf, sizeof(int) * ovf);
   SceneView v; fill_view(c, v);
   if (e == hipSuccess) e = hipMemcpyAsync(dR, rays, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = launch_debug_trace(c->stream, v, dR, n, dT, dP, dOvf);

@@ -28,10 +28,7 @@ int check_query(moptix_context c, const float* rays, int64_t n, int32_t mode, vo
 int enqueue_query(moptix_context c, const float* dRays, int64_t n, int32_t mode, void* dOut) {
   QueryArgs a;
   memset(&a, 0, sizeof(a));
-  fill_view(c, a.scene);                                  // the node-format verdict of the render path is not consulted
-  const bool node64 = c->bvh.nodes64 != nullptr && c->opt.nodeFormat != 128 && a.scene.rootRef != kEmptyRef;
-  a.scene.nodes64 = node64 ? c->bvh.nodes64 : nullptr;
-  const int nBlocks = querykernel_blocks(c->numCUs, c->opt.queryBlocksPerCU);
+  const int nBlocks = fill_query_view(c, a.scene);
   const size_t ovf = a.scene.rootRef != kEmptyRef ? querykernel_overflow_ints(nBlocks, c->bvh.stackBound) : 0;
   if (ovf > 0) {
     HIPCHK(c, c->query.overflow.ensure(ovf), "alloc query stack overflow area");

@@ -4,7 +4,6 @@
 
 #include "api_context.h"
 #include "pt_radiance.h"
-#include "querykernel.h"
 #include "radiancekernel.h"
 
 using namespace pt;
@@ -53,10 +52,7 @@ int enqueue_radiance(moptix_context c, const float* dRays, int64_t n, const int3
   moptix_context_t::Radiance& r = c->radiance;
   RadianceArgs a;
   memset(&a, 0, sizeof(a));
-  fill_view(c, a.scene);                                  // the node-format verdict of the render path is not consulted
-  const bool node64 = c->bvh.nodes64 != nullptr && c->opt.nodeFormat != 128 && a.scene.rootRef != kEmptyRef;
-  a.scene.nodes64 = node64 ? c->bvh.nodes64 : nullptr;
-  const int nBlocks = querykernel_blocks(c->numCUs, c->opt.queryBlocksPerCU);
+  const int nBlocks = fill_query_view(c, a.scene);
   const size_t ovf = a.scene.rootRef != kEmptyRef ? radiancekernel_overflow_ints(nBlocks, c->bvh.stackBound) : 0;
   if (ovf > 0) {
     HIPCHK(c, r.overflow.ensure(ovf), "alloc radiance stack overflow area");

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "api_context.h"
+#include "pt_lanestack.h"
 
 using namespace pt;
 using namespace pt::api;
@@ -39,8 +40,8 @@ int choose_node_format(moptix_context c) {
   unsigned long long* dOut = nullptr; int* dOvf = nullptr;
   hipError_t e = hipMalloc((void**)&dOut, 4 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemsetAsync(dOut, 0, 4 * sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess && c->bvh.stackBound > megakernel_lds_stack_entries())
-    e = hipMalloc((void**)&dOvf, sizeof(int) * threads * (size_t)(c->bvh.stackBound - megakernel_lds_stack_entries() + 1));
+  const size_t ovf = lane_stack_overflow_entries(threads, c->bvh.stackBound, megakernel_lds_stack_entries());
+  if (e == hipSuccess && ovf > 0) e = hipMalloc((void**)&dOvf, sizeof(int) * ovf);
   if (e == hipSuccess) e = launch_probe_paths(c->stream, v, 0, false, dOut, dOvf);
   if (e == hipSuccess) e = launch_probe_paths(c->stream, v, 0, true, dOut + 2, dOvf);
   if (e == hipSuccess) e = hipMemcpyAsync(c->probeCounts, dOut, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
@@ -190,8 +191,8 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
     p.ovfDepth = hasTris ? std::max(0, c->bvh.stackBound - p.kernel->lds_stack_entries() + 1) : 0;
     p.overflowInts = p.ovfDepth > 0 ? p.kernel->overflow_ints(p.nBlocks, p.ovfDepth) : 0;
     p.poolBytes = p.kernel->cold_bytes(p.nBlocks);
-  } else if (c->bvh.stackBound > megakernel_lds_stack_entries()) {      // per thread, not per slot; LaunchArgs::ovfDepth stays 0
-    p.overflowInts = (size_t)(c->bvh.stackBound - megakernel_lds_stack_entries() + 1) * p.nBlocks * 256;
+  } else {      // per thread, not per slot; LaunchArgs::ovfDepth stays 0
+    p.overflowInts = lane_stack_overflow_entries((size_t)p.nBlocks * 256, c->bvh.stackBound, megakernel_lds_stack_entries());
   }
   // [0] work counter, [1] watchdog flag, then (variant 4) the drain list (megakernel.h kDrain*): counters, capacity, threshold, entries
   p.workInts = 2 + drain_list_ints(p.nBlocks, p.drainBelow);

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "megakernel.h"
+#include "pt_lanestack.h"
 #include "pt_path.h"
 #include "pt_packet.h"
 #include "pt_slot.h"
@@ -61,17 +62,6 @@ struct DrainLds {
   int rayList[kTop];                    // the ids of the rays in flight, compact
 };
 
-__device__ __forceinline__ int lane_prefix(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float inv_dir(float d) {
-  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d);
-}
 __device__ __forceinline__ unsigned long long hit_key(float t, unsigned int prim) { return ((unsigned long long)(uint32_t)f2i(t) << 32) | prim; }
 
 // the four child boxes of a node against one ray: which are entered (pt_path.h trav_node_step's planes, without its sort and stack)
@@ -241,7 +231,7 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
             tmax = tv.tbest; if (tv.bestPrim >= 0) prim0 = (unsigned int)tv.bestPrim;
           }
           const int rid = lane * 4 + j;
-          const v3 inv = mk3(inv_dir(d.x), inv_dir(d.y), inv_dir(d.z));
+          const v3 inv = mk3(node_inv(d.x), node_inv(d.y), node_inv(d.z));
           const v3 noi = neg_o_inv(ps.o, inv);
           S.d[rid][0] = d.x; S.d[rid][1] = d.y; S.d[rid][2] = d.z;
           S.inv[rid][0] = inv.x; S.inv[rid][1] = inv.y; S.inv[rid][2] = inv.z;
@@ -255,7 +245,7 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
     int sp = 0;
     if (sc.rootRef != kEmptyRef) {
       const unsigned long long m0 = __ballot(nR > 0), m1 = __ballot(nR > 1), m2 = __ballot(nR > 2), m3 = __ballot(nR > 3);
-      const int off = lane_prefix(m0) + lane_prefix(m1) + lane_prefix(m2) + lane_prefix(m3);
+      const int off = lane_rank(m0) + lane_rank(m1) + lane_rank(m2) + lane_rank(m3);
       const int nRays = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);
       const int nT = S.nTop;
       if (nT > 0 && nRays <= kTop) {         // few rays: each starts at the tree's second level (kTop above)
@@ -277,7 +267,7 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
             in = tn <= tf * 1.0000005f;
           }
           const unsigned long long m = __ballot(in);
-          if (in) { const int w = sp + lane_prefix(m); S.ref[w] = S.topRef[e]; S.tn[w] = i2f((f2i(tn) & ~kRidMask) | rid); }
+          if (in) { const int w = sp + lane_rank(m); S.ref[w] = S.topRef[e]; S.tn[w] = i2f((f2i(tn) & ~kRidMask) | rid); }
           sp += __popcll(m);
         }
       } else {                               // one frontier entry per ray, at the root
@@ -346,7 +336,7 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
       const bool isNode = live && ref >= 0;
       const int m = isNode ? (int)cin[0] + (int)cin[1] + (int)cin[2] + (int)cin[3] : 0;
       const unsigned long long b0 = __ballot((m & 1) != 0), b1 = __ballot((m & 2) != 0), b2 = __ballot((m & 4) != 0);
-      int w = sp + lane_prefix(b0) + 2 * lane_prefix(b1) + 4 * lane_prefix(b2);
+      int w = sp + lane_rank(b0) + 2 * lane_rank(b1) + 4 * lane_rank(b2);
       if (isNode) {
 #pragma unroll
         for (int c = 3; c >= 0; c--) {        // children 3 .. 0: the lower ones end up nearer the top
@@ -388,11 +378,10 @@ __global__ void __launch_bounds__(64) pt_drainkernel(const LaunchArgs a) {
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[kCntPerLane] = { wave_sum32(ct.samples), wave_sum32(ct.primaryRays), wave_sum32(ct.bounceRays), wave_sum32(ct.shadowRays),
-                            wave_sum32(ct.nodeFetches), wave_sum32(ct.triTests), wave_sum32(ct.closestHits), wave_sum32(ct.lightLoads),
-                            wave_sum32(ct.analyticTests) };
+    uint32_t v[kCntPerLane];
+    wave_sum_counters(ct, v);
     for (int i = 0; i < kCensusRegions; i++) {
-      const uint32_t cl = wave_sum32(ct.censusLanes[i]), cw = wave_sum32(ct.censusWaves[i]);
+      const uint32_t cl = wave_sum(ct.censusLanes[i]), cw = wave_sum(ct.censusWaves[i]);
       if (lane == 0 && cw != 0u) { atomicAdd(&c[kCntCensusLanes + i], (unsigned long long)cl); atomicAdd(&c[kCntCensusWaves + i], (unsigned long long)cw); }
     }
     if (lane == 0) {

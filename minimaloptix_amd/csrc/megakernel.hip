@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "megakernel.h"
+#include "pt_lanestack.h"
 #include "pt_path.h"
 
 namespace pt {
@@ -31,41 +32,7 @@ constexpr int kBlockThreads = 256;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kLdsStack = 32;          // entries per lane kept in LDS
 
-// LDS stack with global overflow.  lds points at this lane's column ([entry][lane] layout).
-struct LaneStack {
-  int* lds;
-  int* ovf;       // this lane's overflow column (stride = ovfStride) or nullptr
-  int ovfStride;
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (sp < kLdsStack) lds[sp * 64] = v;
-    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    return sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kLdsStack; }
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp * 64] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
-struct NoStack {
-  __device__ __forceinline__ void store(int, int) {}
-  __device__ __forceinline__ int load(int) const { return kTravDone; }
-  __device__ __forceinline__ bool roomy(int) const { return false; }
-  __device__ __forceinline__ void store_fast(int, int) {}
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
-
-__device__ __forceinline__ int popc64(unsigned long long m) { return __popcll(m); }
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+using Stack32 = LaneStack<kLdsStack>;
 
 template <bool CNT, bool HAS_TRIS>
 __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs a) {
@@ -73,9 +40,10 @@ __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs 
   const SceneView& sc = a.scene;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
-  using Stack = typename std::conditional<HAS_TRIS, LaneStack, NoStack>::type;
+  using Stack = typename std::conditional<HAS_TRIS, Stack32, NoStack>::type;
   Stack st;
   if constexpr (HAS_TRIS) {
+    // not st.init: it takes the thread's index ready, and this kernel's code has it computed behind the LDS column
     st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
     const int gthread = blockIdx.x * kBlockThreads + threadIdx.x;
     st.ovfStride = gridDim.x * kBlockThreads;
@@ -83,13 +51,8 @@ __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs 
   }
 
   PathState ps;
-  ps.mode = M_NEW_PIXEL; ps.pixel = 0; ps.item = 0; ps.accum = mk3(0, 0, 0);
-  ps.thr = mk3(0, 0, 0); ps.rad = mk3(0, 0, 0); ps.depth = 0; ps.seed = 0;
-  ps.o = mk3(0, 0, 0); ps.d = mk3(0, 0, 1); ps.tmin = 0; ps.tmax = 0; ps.kind = RK_RADIANCE;
-  ps.N = mk3(0, 0, 1); ps.V = mk3(0, 0, 1); ps.mat = 0; ps.light = 0; ps.pendW = mk3(0, 0, 0); ps.pendInv = 0;
   Trav tv;
-  tv.node = kTravDone; tv.sp = 0; tv.started = 0; tv.tbest = 0; tv.bestPrim = -1; tv.bestTri = -1;
-  tv.beta = 0; tv.gamma = 0; tv.att = mk3(1, 1, 1); tv.inv = mk3(0, 0, 0); tv.noi = mk3(0, 0, 0);
+  idle_path(ps, tv);
   Counters ct = {};
   uint32_t waveSteps = 0, activeLaneSteps = 0;
 
@@ -145,9 +108,8 @@ __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs 
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
-                            wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
-                            wave_sum(ct.analyticTests) };
+    uint32_t v[kCntPerLane];
+    wave_sum_counters(ct, v);
     if (lane == 0) {
       for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
       atomicAdd(&c[kCntTraversalSteps], (unsigned long long)waveSteps);
@@ -159,12 +121,9 @@ __global__ void __launch_bounds__(kBlockThreads) pt_megakernel(const LaunchArgs 
 // nearest-hit queries for explicit rays (moptix_debug_trace)
 __global__ void __launch_bounds__(kBlockThreads) k_debug_trace(SceneView sc, const float* rays, int n, float* outT, int* outPrim, int* stackOverflow) {
   __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  LaneStack st;
-  st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
-  st.ovfStride = gridDim.x * kBlockThreads;
-  st.ovf = stackOverflow ? stackOverflow + i : nullptr;
+  Stack32 st;
+  st.init(ldsStack, stackOverflow, i, gridDim.x * kBlockThreads);
   if (i >= n) return;
   PathState ps = {};
   ps.o = mk3(rays[8 * i], rays[8 * i + 1], rays[8 * i + 2]); ps.d = mk3(rays[8 * i + 3], rays[8 * i + 4], rays[8 * i + 5]);
@@ -184,12 +143,10 @@ constexpr int kProbeDepth = 6;
 template <bool N64>
 __global__ void __launch_bounds__(kBlockThreads) k_probe_paths(SceneView sc, int launchSeed, unsigned long long* out, int* stackOverflow) {
   __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  LaneStack st;
-  st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
-  st.ovfStride = gridDim.x * kBlockThreads;
-  st.ovf = stackOverflow ? stackOverflow + i : nullptr;
+  Stack32 st;
+  st.init(ldsStack, stackOverflow, i, gridDim.x * kBlockThreads);
   Counters ct = {};
   if (i < sc.width * sc.height) {
     PathState ps = {};

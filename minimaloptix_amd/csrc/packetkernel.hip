@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "megakernel.h"
+#include "pt_lanestack.h"
 #include "pt_path.h"
 #include "pt_packet.h"
 #include "pt_slot.h"
@@ -127,18 +128,6 @@ struct SlotStack {
   __device__ __forceinline__ bool fits_fast(int sp, int m) const { return sp + m <= kStackN && sp < kStackN; }
   __device__ __forceinline__ int peek_fast(int sp) const { return lds[min(sp, kStackN) - 1]; }
 };
-
-__device__ __forceinline__ float node_inv(float d) {      // slab_inv (pt_path.h) with the hardware reciprocal
-  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d);
-}
-__device__ __forceinline__ int lane_rank(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // The launch arguments again, read from the kernel-argument segment through a pointer the compiler cannot see through.
 // The kernel is one loop; whatever it reads from its arguments is loop-invariant, so the compiler loads ALL of it in front
@@ -864,9 +853,8 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
-                            wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
-                            wave_sum(ct.analyticTests) };
+    uint32_t v[kCntPerLane];
+    wave_sum_counters(ct, v);
     const uint32_t rw[4] = { wave_sum(rows[0]), wave_sum(rows[1]), wave_sum(rows[2]), wave_sum(rows[3]) };
     for (int i = 0; i < kCensusRegions; i++) {
       const uint32_t cl = wave_sum(ct.censusLanes[i]), cw = wave_sum(ct.censusWaves[i]);

@@ -14,8 +14,6 @@ struct PointArgs {
 };
 constexpr int kPointMaxLaunch = 1 << 30;      // points per launch
 
-int pointkernel_lds_stack_entries();
-int pointkernel_blocks(int nCUs, int blocksPerCU);
 size_t pointkernel_overflow_entries(int nBlocks, int stackBound);     // 8-byte entries; 0 = the tree fits the LDS stack
 // mode: POINT_CLOSEST / POINT_ANY (pt_point.h).  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
 hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode);

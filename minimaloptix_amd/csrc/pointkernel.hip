@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "pt_lanestack.h"
 #include "pt_point.h"
 #include "pointkernel.h"
 
@@ -24,20 +25,13 @@ constexpr int kBlockThreads = 256;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kLdsStack = 16;          // entries per lane kept in LDS (8 bytes each: 32 KB per workgroup)
 
-// LDS stack [entry][lane] with a global overflow column per thread: querykernel.hip's QueryStack (itself megakernel.hip's LaneStack, copied
-// for the reason given there: sharing it means editing files whose code objects this change leaves bit for bit alone), with the entry
-// widened to reference + box distance.
-struct PointStack {
-  unsigned long long* lds;
-  unsigned long long* ovf;       // this thread's overflow column (stride = ovfStride) or nullptr
-  int ovfStride;
+// LaneStack (pt_lanestack.h) over eight-byte entries: reference + box distance
+struct PointStack : LaneStack<kLdsStack, unsigned long long> {
   __device__ __forceinline__ void store(int sp, int ref, float d2) {
-    const unsigned long long e = ((unsigned long long)(uint32_t)f2i(d2) << 32) | (uint32_t)ref;
-    if (sp < kLdsStack) lds[sp * 64] = e;
-    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = e;
+    LaneStack::store(sp, ((unsigned long long)(uint32_t)f2i(d2) << 32) | (uint32_t)ref);
   }
   __device__ __forceinline__ void load(int sp, int& ref, float& d2) const {
-    const unsigned long long e = sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
+    const unsigned long long e = LaneStack::load(sp);
     ref = (int32_t)(uint32_t)e; d2 = i2f((int32_t)(e >> 32));
   }
 };
@@ -46,12 +40,9 @@ template <bool ANY, bool N64>
 __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a) {
   __shared__ unsigned long long ldsStack[kWavesPerBlock * kLdsStack * 64];
   const SceneView& sc = a.scene;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
   PointStack st;
-  st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
-  st.ovfStride = stride;
-  st.ovf = a.stackOverflow ? a.stackOverflow + gthread : nullptr;
+  st.init(ldsStack, a.stackOverflow, gthread, stride);
   const uint4* __restrict__ points = reinterpret_cast<const uint4*>(a.points);
   for (int i = gthread; i < a.n; i += stride) {           // n <= kPointMaxLaunch = 2^30 and stride <= 2^22: no overflow
     const uint4 r = points[(size_t)i];
@@ -74,11 +65,7 @@ __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a
 
 }  // namespace
 
-int pointkernel_lds_stack_entries() { return kLdsStack; }
-int pointkernel_blocks(int nCUs, int blocksPerCU) { return (nCUs > 0 ? nCUs : 256) * blocksPerCU; }
-size_t pointkernel_overflow_entries(int nBlocks, int stackBound) {
-  return stackBound > kLdsStack ? (size_t)nBlocks * kBlockThreads * (size_t)(stackBound - kLdsStack + 1) : 0;
-}
+size_t pointkernel_overflow_entries(int nBlocks, int stackBound) { return lane_stack_overflow_entries((size_t)nBlocks * kBlockThreads, stackBound, kLdsStack); }
 
 hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode) {
   const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);

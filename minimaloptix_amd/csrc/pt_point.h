@@ -33,7 +33,7 @@
 //                    E1 = v1 / dot(v1, v1), E2 = v2 / dot(v2, v2) (the edges setQuadParams inverted), c = (anchor + E1 * a1) + E2 * a2
 //
 // The traversal is ordered by the squared distance from q to a child's box and pruned by the best d2 so far (point_node_step); it is used
-// by the point kernel (pointkernel.hip) and by its CPU mirror (tests/pointsim); nothing of the render path includes it.
+// by the point kernel (pointkernel.hip) and by its CPU mirror (tests/hostsim/pointsim.cpp); nothing of the render path includes it.
 #pragma once
 #include "pt_path.h"
 #include "pt_lbvh.h"

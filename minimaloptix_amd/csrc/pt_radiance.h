@@ -15,7 +15,7 @@
 // Its fourth component is the first segment's hit distance with the bits of the closest query's moptix_hit.t on the same ray: tbest of
 // that segment, or the given tmax where it meets nothing or the ray is invalid.  An invalid ray's sample is (0, 0, 0, tmax) and no path
 // is traced for it.
-// Used by the radiance kernel (radiancekernel.hip) and by its CPU mirror (tests/radiancesim); nothing of the render path includes it.
+// Used by the radiance kernel (radiancekernel.hip) and by its CPU mirror (tests/hostsim/radiancesim.cpp); nothing of the render path includes it.
 #pragma once
 #include "pt_query.h"
 

@@ -14,8 +14,7 @@ struct QueryArgs {
 };
 constexpr int kQueryMaxLaunch = 1 << 30;      // rays per launch
 
-int querykernel_lds_stack_entries();
-int querykernel_blocks(int nCUs, int blocksPerCU);
+int querykernel_blocks(int nCUs, int blocksPerCU);      // the grid's cap, of the radiance and point queries too (api_core.hip fill_query_view)
 size_t querykernel_overflow_ints(int nBlocks, int stackBound);     // 0 = the tree fits the LDS stack
 // mode: QUERY_CLOSEST / QUERY_ANY (pt_query.h).  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
 hipError_t launch_rayquery(hipStream_t stream, const QueryArgs& a, int nBlocks, int mode);

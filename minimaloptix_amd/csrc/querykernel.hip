@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "pt_lanestack.h"
 #include "pt_query.h"
 #include "querykernel.h"
 
@@ -24,37 +25,13 @@ constexpr int kBlockThreads = 256;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kLdsStack = 32;          // entries per lane kept in LDS (32 KB per workgroup)
 
-// LDS stack [entry][lane] with a global overflow column per thread: megakernel.hip's LaneStack, copied as aovkernel.hip copies it.  LaneStack
-// lives in megakernel.hip's anonymous namespace beside its kLdsStack; sharing it means editing that file and the AOV kernel's, whose code
-// objects this change leaves bit for bit alone (tools/isa_diff.py).
-struct QueryStack {
-  int* lds;
-  int* ovf;       // this thread's overflow column (stride = ovfStride) or nullptr
-  int ovfStride;
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (sp < kLdsStack) lds[sp * 64] = v;
-    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    return sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kLdsStack; }
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp * 64] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
-
 template <bool ANY, bool N64>
 __global__ void __launch_bounds__(kBlockThreads) pt_rayquery(const QueryArgs a) {
   __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
   const SceneView& sc = a.scene;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
-  QueryStack st;
-  st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
-  st.ovfStride = stride;
-  st.ovf = a.stackOverflow ? a.stackOverflow + gthread : nullptr;
+  LaneStack<kLdsStack> st;
+  st.init(ldsStack, a.stackOverflow, gthread, stride);
   const uint4* __restrict__ rays = reinterpret_cast<const uint4*>(a.rays);
   Counters ct;                      // not counted: never written
   for (int i = gthread; i < a.n; i += stride) {           // n <= kQueryMaxLaunch = 2^30 and stride <= 2^22: no overflow
@@ -80,11 +57,8 @@ __global__ void __launch_bounds__(kBlockThreads) pt_rayquery(const QueryArgs a) 
 
 }  // namespace
 
-int querykernel_lds_stack_entries() { return kLdsStack; }
 int querykernel_blocks(int nCUs, int blocksPerCU) { return (nCUs > 0 ? nCUs : 256) * blocksPerCU; }
-size_t querykernel_overflow_ints(int nBlocks, int stackBound) {
-  return stackBound > kLdsStack ? (size_t)nBlocks * kBlockThreads * (size_t)(stackBound - kLdsStack + 1) : 0;
-}
+size_t querykernel_overflow_ints(int nBlocks, int stackBound) { return lane_stack_overflow_entries((size_t)nBlocks * kBlockThreads, stackBound, kLdsStack); }
 
 hipError_t launch_rayquery(hipStream_t stream, const QueryArgs& a, int nBlocks, int mode) {
   const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);

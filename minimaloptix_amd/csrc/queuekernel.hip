@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "megakernel.h"
+#include "pt_lanestack.h"
 #include "pt_path.h"
 
 namespace pt {
@@ -151,18 +152,6 @@ struct SlotStack {
   __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
   __device__ __forceinline__ int peek_fast(int) const { return 0; }
 };
-
-__device__ __forceinline__ float node_inv(float d) {      // slab_inv (pt_path.h) with the hardware reciprocal
-  return __builtin_amdgcn_rcpf(__builtin_fabsf(d) < kSlabMinDir ? __builtin_copysignf(kSlabMinDir, d) : d);
-}
-__device__ __forceinline__ int lane_rank(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // destination queue of a slot after a traversal step / a ray set-up
 __device__ __forceinline__ int route(int node, int kind, int bestPrim) {
@@ -621,9 +610,8 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
 
   if constexpr (CNT) {
     unsigned long long* c = a.counters;
-    const uint32_t v[kCntPerLane] = { wave_sum(ct.samples), wave_sum(ct.primaryRays), wave_sum(ct.bounceRays), wave_sum(ct.shadowRays),
-                            wave_sum(ct.nodeFetches), wave_sum(ct.triTests), wave_sum(ct.closestHits), wave_sum(ct.lightLoads),
-                            wave_sum(ct.analyticTests) };
+    uint32_t v[kCntPerLane];
+    wave_sum_counters(ct, v);
     if (lane == 0) {
       for (int i = 0; i < kCntPerLane; i++) atomicAdd(&c[i], (unsigned long long)v[i]);
       atomicAdd(&c[kCntTraversalSteps], (unsigned long long)nodeSteps + leafPasses);

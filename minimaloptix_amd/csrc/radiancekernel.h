@@ -24,7 +24,6 @@ struct RadianceArgs {
 };
 constexpr long long kRadianceMaxWork = 1ll << 30;     // work items per launch: the counter and the record index stay 32-bit
 
-int radiancekernel_lds_stack_entries();
 size_t radiancekernel_overflow_ints(int nBlocks, int stackBound);      // 0 = the tree fits the LDS stack
 // Launches min(nBlocks, ceil(n * nSamples / 256)) workgroups of the trace kernel on `stream`, then the ordered reduction of the records.
 hipError_t launch_radiance(hipStream_t stream, const RadianceArgs& a, int nBlocks);

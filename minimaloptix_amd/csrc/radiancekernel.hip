@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "pt_lanestack.h"
 #include "pt_radiance.h"
 #include "radiancekernel.h"
 
@@ -27,34 +28,12 @@ constexpr int kBlockThreads = 256;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 constexpr int kLdsStack = 32;          // entries per lane kept in LDS (32 KB per workgroup)
 
-// LDS stack [entry][lane] with a global overflow column per thread: megakernel.hip's LaneStack, copied as querykernel.hip copies it (it
-// lives in that file's anonymous namespace; sharing it means editing files whose code objects this change leaves bit for bit alone).
-struct RadianceStack {
-  int* lds;
-  int* ovf;       // this thread's overflow column (stride = ovfStride) or nullptr
-  int ovfStride;
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (sp < kLdsStack) lds[sp * 64] = v;
-    else ovf[(size_t)(sp - kLdsStack) * ovfStride] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    return sp < kLdsStack ? lds[sp * 64] : ovf[(size_t)(sp - kLdsStack) * ovfStride];
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kLdsStack; }
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp * 64] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
-
-__device__ __forceinline__ int popc64(unsigned long long m) { return __popcll(m); }
-
 template <bool N64>
 __global__ void __launch_bounds__(kBlockThreads) pt_radiancekernel(const RadianceArgs a) {
   __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
   const SceneView& sc = a.scene;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  RadianceStack st;
+  LaneStack<kLdsStack> st;      // not st.init: it takes the thread's index ready, and this kernel's code has it computed behind the LDS column
   st.lds = ldsStack + wave * (kLdsStack * 64) + lane;
   st.ovfStride = gridDim.x * kBlockThreads;
   st.ovf = a.stackOverflow ? a.stackOverflow + (blockIdx.x * kBlockThreads + threadIdx.x) : nullptr;
@@ -62,14 +41,9 @@ __global__ void __launch_bounds__(kBlockThreads) pt_radiancekernel(const Radianc
   const int nWork = a.n * a.nSamples;                 // <= kRadianceMaxWork
 
   PathState ps;
-  ps.mode = M_NEW_PIXEL; ps.pixel = 0; ps.item = 0; ps.accum = mk3(0, 0, 0);
-  ps.thr = mk3(0, 0, 0); ps.rad = mk3(0, 0, 0); ps.depth = 0; ps.seed = 0;
-  ps.o = mk3(0, 0, 0); ps.d = mk3(0, 0, 1); ps.tmin = 0; ps.tmax = 0; ps.kind = RK_RADIANCE;
-  ps.N = mk3(0, 0, 1); ps.V = mk3(0, 0, 1); ps.mat = 0; ps.light = 0; ps.pendW = mk3(0, 0, 0); ps.pendInv = 0;
-  ps.cdlin = mk3(0, 0, 0);
   Trav tv;
-  tv.node = kTravDone; tv.sp = 0; tv.started = 0; tv.tbest = 0; tv.bestPrim = -1; tv.bestTri = -1; tv.bestCls = 0;
-  tv.beta = 0; tv.gamma = 0; tv.att = mk3(1, 1, 1); tv.inv = mk3(0, 0, 0); tv.noi = mk3(0, 0, 0);
+  idle_path(ps, tv);
+  ps.cdlin = mk3(0, 0, 0); tv.bestCls = 0;
   Counters ct;                      // not counted: never written
   float tFirst = 0.f;
 
@@ -141,10 +115,7 @@ __global__ void __launch_bounds__(kBlockThreads) k_radiance_sum(const RadianceAr
 
 }  // namespace
 
-int radiancekernel_lds_stack_entries() { return kLdsStack; }
-size_t radiancekernel_overflow_ints(int nBlocks, int stackBound) {
-  return stackBound > kLdsStack ? (size_t)nBlocks * kBlockThreads * (size_t)(stackBound - kLdsStack + 1) : 0;
-}
+size_t radiancekernel_overflow_ints(int nBlocks, int stackBound) { return lane_stack_overflow_entries((size_t)nBlocks * kBlockThreads, stackBound, kLdsStack); }
 
 hipError_t launch_radiance(hipStream_t stream, const RadianceArgs& a, int nBlocks) {
   const long long nWork = (long long)a.n * a.nSamples;

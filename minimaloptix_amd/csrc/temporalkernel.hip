@@ -24,6 +24,7 @@ namespace {
 
 constexpr int kBlockThreads = kImageBlockThreads;
 
+// not pt_lanestack.h's wave_sum: that one leaves the sum in every lane (__shfl_xor), other instructions than these
 __device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
   for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
   return v;                                                     // lane 0 holds the sum

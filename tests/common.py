@@ -60,7 +60,7 @@ def hostsim_lib():
         def sig(name, argtypes, restype=C.c_int):
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype
-        # the built scene: a handle, and what traces on it (hostsim.cpp, aovsim.cpp, querysim.cpp, refitsim.cpp)
+        # the built scene: a handle, and what traces on it (hostsim.cpp, aovsim.cpp, querysim.cpp, radiancesim.cpp, pointsim.cpp, refitsim.cpp)
         sig("hostsim_create", [C.POINTER(HostsimScene), C.c_int, C.c_int], vp)
         sig("hostsim_free", [vp], None)
         sig("hostsim_read_bvh", [vp, C.POINTER(HostsimBvhOut)])
@@ -70,6 +70,12 @@ def hostsim_lib():
         sig("aovsim_render_aovs", [vp, C.c_int, i32p, C.c_int, C.POINTER(AovsimBuffers)])
         sig("aovsim_camera_rays", [C.POINTER(HostsimScene), C.c_int32, f32p])
         sig("querysim_query", [vp, C.c_int, f32p, C.c_int64, C.c_int, vp])
+        sig("radiancesim_query", [vp, C.c_int, f32p, C.c_int64, i32p, u32p, C.c_int32, C.c_uint32, C.c_uint32, f32p])
+        sig("radiancesim_camera", [C.POINTER(HostsimScene), C.c_int32, f32p, u32p])
+        sig("radiancesim_shadow_rule", [vp, C.c_int])
+        sig("pointsim_query", [vp, C.c_int, f32p, C.c_int64, C.c_int, vp])
+        sig("pointsim_brute", [vp, f32p, C.c_int64, C.c_int, vp])
+        sig("pointsim_stack_depth", [vp, C.c_int, f32p, C.c_int64])
         sig("refitsim_update", [vp, C.c_int32, C.c_int32, f32p, f32p])
         sig("refitsim_refit", [vp])
         sig("refitsim_read", [vp, C.POINTER(RefitsimOut)])

@@ -73,6 +73,12 @@ struct LocalStack {
   inline bool fits_fast(int, int) const { return false; }
   inline int peek_fast(int) const { return 0; }
 };
+// the point queries' entry: a reference and the squared distance to its box (pt_point.h)
+struct LocalPointStack {
+  int ref[256]; float d2[256];
+  inline void store(int sp, int r, float d) { ref[sp] = r; d2[sp] = d; }
+  inline void load(int sp, int& r, float& d) const { r = ref[sp]; d = d2[sp]; }
+};
 
 // nodeFormat 64 walks the 64-byte nodes where the tree has them (as the packet kernel does by default), 128 the 128-byte ones
 inline bool walks_node64(const SceneView& sc, int nodeFormat) { return nodeFormat == 64 && sc.nodes64 != nullptr; }

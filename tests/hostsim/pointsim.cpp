@@ -1,21 +1,14 @@
 // pointsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the point-query kernel (minimaloptix_amd/csrc/pointkernel.hip): the same
 // per-point code (pt_point.h), compiled for the host and run one point at a time, on the scene and tree of a hostsim_create handle
-// (../hostsim/hostsim.h: HostSim is header-defined and the per-element code is all inline, so this library needs nothing of
-// libhostsim.so's but the handle); and the loop over every primitive that the traversal must equal.  The GPU tests compare the kernel's
-// output with this bit for bit.  It is not part of the product: nothing under minimaloptix_amd/ builds or loads it.
+// (hostsim.h); and the loop over every primitive that the traversal must equal.  The GPU tests compare the kernel's output with this bit
+// for bit.  It is not part of the product: nothing under minimaloptix_amd/ builds or loads it.
 #include <cstring>
-#include "../hostsim/hostsim.h"
+#include "hostsim.h"
 #include "../../minimaloptix_amd/csrc/pt_point.h"
 
 using namespace hostsim;
 
 namespace {
-
-struct LocalPointStack {
-  int ref[256]; float d2[256];
-  inline void store(int sp, int r, float d) { ref[sp] = r; d2[sp] = d; }
-  inline void load(int sp, int& r, float& d) const { r = ref[sp]; d = d2[sp]; }
-};
 
 void write_out(const SceneView& sc, int mode, const float* p, const PointTrav& tv, void* out, size_t i) {
   if (mode == POINT_ANY) static_cast<int32_t*>(out)[i] = tv.bestPrim >= 0 ? 1 : 0;

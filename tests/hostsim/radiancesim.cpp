@@ -1,10 +1,9 @@
 // radiancesim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the radiance-query kernel (minimaloptix_amd/csrc/radiancekernel.hip): the same
 // per-sample code (pt_radiance.h over pt_path.h's state machine and traversal), compiled for the host and run one sample at a time, on the
-// scene and tree of a hostsim_create handle (../hostsim/hostsim.h: HostSim is header-defined and the per-element code is all inline, so
-// this library needs nothing of libhostsim.so's but the handle).  The GPU tests compare the kernel's output with this bit for bit.  It is
-// not part of the product: nothing under minimaloptix_amd/ builds or loads it.
+// scene and tree of a hostsim_create handle (hostsim.h).  The GPU tests compare the kernel's output with this bit for bit.  It is not part
+// of the product: nothing under minimaloptix_amd/ builds or loads it.
 #include <cstring>
-#include "../hostsim/hostsim.h"
+#include "hostsim.h"
 #include "../../minimaloptix_amd/csrc/pt_radiance.h"
 
 using namespace hostsim;

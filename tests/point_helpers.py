@@ -1,36 +1,12 @@
-"""The point queries of the CPU mirror (tests/pointsim/pointsim.cpp, a library of its own on libhostsim.so's scene handle): built on demand,
-loaded here, with the point sets of the point-query tests and a binary64 distance that shares no code with the mirror."""
-import ctypes as C
-import os
-import subprocess
-
+"""The point queries of the CPU mirror (tests/hostsim/pointsim.cpp, in libhostsim.so), with the point sets of the point-query tests and a
+binary64 distance that shares no code with the mirror."""
 import numpy as np
 
-from common import M, REPO, _f32, _ptr, hostsim_handle
+from common import M, _f32, _ptr, hostsim_handle, hostsim_lib
 from query_helpers import same_bits, scene_box      # noqa: F401  (same_bits: for the tests)
 
 POINT_DTYPE = M.POINT_DTYPE
-_DIR = os.path.join(REPO, "tests", "pointsim")
-_lib = None
 INF = np.float32(np.inf)
-
-
-def pointsim_lib():
-    global _lib
-    if _lib is None:
-        path = os.path.join(_DIR, "libpointsim.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _DIR, "-s"])
-        L = C.CDLL(path)
-        f32p = C.POINTER(C.c_float)
-        L.pointsim_query.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int64, C.c_int, C.c_void_p]
-        L.pointsim_query.restype = C.c_int
-        L.pointsim_brute.argtypes = [C.c_void_p, f32p, C.c_int64, C.c_int, C.c_void_p]
-        L.pointsim_brute.restype = C.c_int
-        L.pointsim_stack_depth.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int64]
-        L.pointsim_stack_depth.restype = C.c_int
-        _lib = L
-    return _lib
 
 
 def _mode(mode):
@@ -47,7 +23,7 @@ def pointsim(hs, points, mode="closest", node_format=64, leaf_size=4):
     sim = hostsim_handle(hs, leaf_size)
     pts = _points(points)
     out = np.zeros(len(pts), POINT_DTYPE if mode == "closest" else np.int32)
-    assert pointsim_lib().pointsim_query(sim._h, int(node_format), _ptr(pts), len(pts), _mode(mode), out.ctypes.data) == 0
+    assert hostsim_lib().pointsim_query(sim._h, int(node_format), _ptr(pts), len(pts), _mode(mode), out.ctypes.data) == 0
     return out
 
 
@@ -56,7 +32,7 @@ def pointbrute(hs, points, mode="closest", leaf_size=4):
     sim = hostsim_handle(hs, leaf_size)
     pts = _points(points)
     out = np.zeros(len(pts), POINT_DTYPE if mode == "closest" else np.int32)
-    assert pointsim_lib().pointsim_brute(sim._h, _ptr(pts), len(pts), _mode(mode), out.ctypes.data) == 0
+    assert hostsim_lib().pointsim_brute(sim._h, _ptr(pts), len(pts), _mode(mode), out.ctypes.data) == 0
     return out
 
 
@@ -64,7 +40,7 @@ def stack_depth(hs, points, node_format=64, leaf_size=4):
     """Most stack entries the closest walk of any of the points holds."""
     sim = hostsim_handle(hs, leaf_size)
     pts = _points(points)
-    d = pointsim_lib().pointsim_stack_depth(sim._h, int(node_format), _ptr(pts), len(pts))
+    d = hostsim_lib().pointsim_stack_depth(sim._h, int(node_format), _ptr(pts), len(pts))
     assert d >= 0
     return d
 

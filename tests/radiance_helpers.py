@@ -1,35 +1,12 @@
-"""The radiance queries of the CPU mirror (tests/radiancesim/radiancesim.cpp, a library of its own on libhostsim.so's scene handle):
-built on demand, loaded here, and the camera's rays and RNG states the radiance tests start from."""
+"""The radiance queries of the CPU mirror (tests/hostsim/radiancesim.cpp, in libhostsim.so), and the camera's rays and RNG states the
+radiance tests start from."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from common import REPO, HostsimScene, K, _f32, _hostsim_scene, _ptr, hostsim_handle
-
-_DIR = os.path.join(REPO, "tests", "radiancesim")
-_lib = None
+from common import K, _f32, _hostsim_scene, _ptr, hostsim_handle, hostsim_lib
 
 CLAMP = K.RADIANCE_CLAMP
-
-
-def radiancesim_lib():
-    global _lib
-    if _lib is None:
-        path = os.path.join(_DIR, "libradiancesim.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _DIR, "-s"])
-        L = C.CDLL(path)
-        f32p, i32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
-        L.radiancesim_query.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int64, i32p, u32p, C.c_int32, C.c_uint32, C.c_uint32, f32p]
-        L.radiancesim_query.restype = C.c_int
-        L.radiancesim_camera.argtypes = [C.POINTER(HostsimScene), C.c_int32, f32p, u32p]
-        L.radiancesim_camera.restype = C.c_int
-        L.radiancesim_shadow_rule.argtypes = [C.c_void_p, C.c_int]
-        L.radiancesim_shadow_rule.restype = C.c_int
-        _lib = L
-    return _lib
 
 
 def as_seeds(seeds):
@@ -46,16 +23,16 @@ def radiancesim(hs, rays, seeds=None, states=None, clamp=False, index_base=0, no
     sd = None if seeds is None else as_seeds(seeds)
     st = None if states is None else np.ascontiguousarray(np.asarray(states).view(np.uint32).reshape(n, -1))
     ns = len(sd) if sd is not None else st.shape[1]
-    rc = radiancesim_lib().radiancesim_query(sim._h, int(node_format), _ptr(rays), n, None if sd is None else _ptr(sd, C.c_int32),
-                                             None if st is None else _ptr(st, C.c_uint32), ns, int(index_base) & 0xffffffff,
-                                             CLAMP if clamp else 0, _ptr(out))
+    rc = hostsim_lib().radiancesim_query(sim._h, int(node_format), _ptr(rays), n, None if sd is None else _ptr(sd, C.c_int32),
+                                         None if st is None else _ptr(st, C.c_uint32), ns, int(index_base) & 0xffffffff,
+                                         CLAMP if clamp else 0, _ptr(out))
     assert rc == 0
     return out
 
 
 def shadow_rule(sim, rule):
     """moptix option "shadow_rule" on a built scene of the mirror (a HostsimHandle)."""
-    assert radiancesim_lib().radiancesim_shadow_rule(sim._h, int(rule)) == 0
+    assert hostsim_lib().radiancesim_shadow_rule(sim._h, int(rule)) == 0
 
 
 def tea16(v0, v1):
@@ -84,7 +61,7 @@ def camera_rays_states(hs, seed):
     s, keep = _hostsim_scene(hs)
     rays = np.zeros((hs.height * hs.width, 8), np.float32)
     states = np.zeros((hs.height * hs.width, 1), np.uint32)
-    rc = radiancesim_lib().radiancesim_camera(C.byref(s), int(as_seeds([seed])[0]), _ptr(rays), _ptr(states, C.c_uint32))
+    rc = hostsim_lib().radiancesim_camera(C.byref(s), int(as_seeds([seed])[0]), _ptr(rays), _ptr(states, C.c_uint32))
     assert rc == 0
     return rays, states
 

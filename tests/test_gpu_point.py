@@ -1,4 +1,4 @@
-"""Point queries on the MI355X (pointkernel.hip): bit for bit the CPU mirror of the kernel's code (tests/pointsim), whatever the grid, the
+"""Point queries on the MI355X (pointkernel.hip): bit for bit the CPU mirror of the kernel's code (tests/hostsim/pointsim.cpp), whatever the grid, the
 node format and the path the points take; moving geometry; and nothing else in the context touched."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-"""Radiance queries on the MI355X (radiancekernel.hip): bit for bit the CPU mirror of the kernel's per-sample code (tests/radiancesim), the
+"""Radiance queries on the MI355X (radiancekernel.hip): bit for bit the CPU mirror of the kernel's per-sample code (tests/hostsim/radiancesim.cpp), the
 frame of moptix_render from the camera's own rays and states, and the contract of the entry: sizes, scheduling, stream, state, and a
 context that is otherwise untouched."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Point queries on the CPU (csrc/pt_point.h through tests/pointsim): the traversal gives the bytes of a loop over every primitive, the
+"""Point queries on the CPU (csrc/pt_point.h through tests/hostsim/pointsim.cpp): the traversal gives the bytes of a loop over every primitive, the
 distances agree with an independent binary64 computation, degenerate triangles are well defined, and the details of the contract hold."""
 import numpy as np
 import pytest

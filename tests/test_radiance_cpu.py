@@ -1,4 +1,4 @@
-"""Radiance queries on the CPU: the mirror of the kernel's per-sample code (tests/radiancesim) against the render's mirror -- a camera's own
+"""Radiance queries on the CPU: the mirror of the kernel's per-sample code (tests/hostsim/radiancesim.cpp) against the render's mirror -- a camera's own
 rays and RNG states give the frame, bit for bit -- and against the recursive oracle's orc_trace_one, which nothing else uses; then the
 contract of the entry: seeds and states, chunking, sample lists, the t channel, invalid rays, the depth cap, bad arguments."""
 import ctypes as C

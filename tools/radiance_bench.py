@@ -3,7 +3,7 @@
     python3 tools/radiance_bench.py [--spp 16] [--reps 5] [--probe-rays 4096] [--probe-samples 1024]
 
 Scene file:coffee at 1920x1080, tree built once.
-  camera  the camera's own rays and the RNG states its lens and jitter draws leave behind (tests/radiancesim radiancesim_camera), for --spp
+  camera  the camera's own rays and the RNG states its lens and jitter draws leave behind (tests/hostsim radiancesim_camera), for --spp
           launch seeds, as one device-resident batch of spp x 1920 x 1080 rays with one sample each and the clamp flag: the samples of
           moptix_render(seeds).  The render runs the per-lane megakernel the query's loops are copied from ("kernel_variant" 0); its time is
           moptix_kernel_time + moptix_reduce_time (trace kernel + ordered reduction), the query's is HIP events round the call on the
