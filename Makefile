@@ -22,7 +22,7 @@ BUILD    ?= build
 HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -fno-slp-vectorize -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -include cstring
 CXXFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -fno-math-errno -mavx2 -mfma -Wall -Wno-unused-function -Wno-unknown-pragmas
 
-DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_radiance.hip $(CSRC)/api_point.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/facemotionkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/radiancekernel.hip $(CSRC)/pointkernel.hip $(CSRC)/refitkernel.hip
+DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_radiance.hip $(CSRC)/api_point.hip $(CSRC)/api_sign.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/facemotionkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/radiancekernel.hip $(CSRC)/pointkernel.hip $(CSRC)/signkernel.hip $(CSRC)/refitkernel.hip
 DEV_OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(DEV_SRCS))
 DEV_HDRS := $(wildcard $(CSRC)/*.h) include/moptix.h
 HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(HOST)/standin_scenes.cpp $(HOST)/image_read.cpp $(HOST)/jpeg_read.cpp \

@@ -646,8 +646,50 @@ int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, cons
  * MOPTIX_POINT_ANY -> one int32 per query: 1 if and only if the closest mode on the same query reports prim >= 0, else 0; the walk stops
  * at the first primitive it accepts.
  * Invalid queries are misses, decided before any traversal: x, y or z non-finite, maxDist NaN, or maxDist <= 0.
- * The distance is UNSIGNED.  A sign needs a watertight mesh and angle-weighted pseudonormals at edges and vertices; neither is assumed
- * or built here: signed distance is out of scope.
+ * MOPTIX_POINT_SIGNED -> one moptix_point_hit per query: every field has the bits of MOPTIX_POINT_CLOSEST on the same query, except that
+ * dist is negated when q is inside.  A miss and an invalid query are exactly as in the closest mode (dist = +maxDist); maxDist limits the
+ * unsigned distance.  The sign is decided from the winner's own record and its row of the sign table (csrc/pt_sign.h states every
+ * operation in order), so the signed answer too is what a loop over every primitive gives, bit for bit.  With c the reported nearest
+ * point:  s = dot(q - c, N),  dist = s < 0 ? -sqrt(d2) : +sqrt(d2): s == 0 (q == c included) and NaN give +.
+ *   triangle   N = the angle-weighted pseudonormal (Baerentzen and Aanaes) of the feature c lies on.  The feature is DEFINED by which of
+ *              the four candidates above won (the first of equal ones) and by the segment's clamped parameter t:
+ *                1  segment(v0, e0)       t == 0 vertex 0, t == 1 vertex 1, else edge 01
+ *                2  segment(v0, -e1)      t == 0 vertex 0, t == 1 vertex 2, else edge 02
+ *                3  segment(v1, v2 - v1)  t == 0 vertex 1, t == 1 vertex 2, else edge 12
+ *                4  the projection        the face
+ *              not by the reported (u, v): (1 - t) + t is not always 1.
+ *   sphere     inside if and only if dot(w, w) < radius * radius, w = q - centre
+ *   quad       always +: a quad is an open surface
+ * Topology.  Taken once per set of uploaded faces, at the first signed query or the first moptix_get_sign_info after the faces were
+ * added, on the host, from the face positions of the staging (pending device-side updates are fetched back first, as moptix_build_accel
+ * does).  Kept across moptix_update_faces*, moptix_refit_accel and moptix_build_accel; dropped by moptix_clear_scene, moptix_add_mesh and
+ * moptix_destroy.  Corners are welded when their three position words are equal, -0 taken as +0; welded ids run in order of first
+ * appearance by (face, corner); an edge is an unordered pair of welded ids.  A face with two corners welded together, or whose normal is
+ * zero or non-finite, is DEGENERATE: it contributes to no sum and no count, and its record is zero (a query it wins is +).
+ * Pseudonormals (not normalised: only the sign of s is used), in binary32, every operation in csrc/pt_sign.h:
+ *   face    un = the unit normal of cross(p1 - p0, p2 - p0), the cross product scaled by a power of two first (as the projection above)
+ *   edge    the sum of un over the edge's faces in ascending face id, from +0 by plain adds
+ *   vertex  the sum over its corners in ascending (face id, corner) of un * angle, from +0 by plain adds; angle = atan2_ac(length(cross(a,
+ *           b)), dot(a, b)) of the corner's two edge vectors, atan2_ac one specified binary32 algorithm (absolute error <= 1e-6)
+ * Ordered sums, no float atomics: the words depend on positions and topology alone.  The stated range is edges whose cross products stay
+ * finite and normal in binary32 (lengths between about 1e-9 and 1e9 units).  The table holds 96 bytes per original face id (six
+ * pseudonormals v0 v1 v2 e01 e02 e12, the unit face normal, padding) and is computed on the device from the faces' current positions.  It
+ * is stale after moptix_update_faces*, moptix_refit_accel and moptix_build_accel; the next signed query enqueues its build in front of the
+ * query kernel on the context's stream, without a host synchronisation and without an allocation after the first.
+ *   moptix_get_sign_info   works from the moment faces are uploaded and needs no built tree (zeros without faces):
+ *     weldedVerts, edges   of the topology (degenerate faces add vertices, not edges)
+ *     boundaryEdges        edges with one face
+ *     nonManifoldEdges     edges with more than two faces
+ *     flippedEdges         edges whose two faces run along them in the same direction
+ *     degenerateFaces      as defined above, on the positions the topology was taken from
+ *     closed               1 if and only if the previous four are 0 and there is at least one face
+ *     signedVolume         sum of dot(p0, cross(p1, p2)) / 6 in binary64 over those positions; NEGATIVE means the mesh is wound inwards
+ *                          and every sign comes out flipped
+ *     tableBuilds          how many times the device table has been computed on this topology
+ *   On a mesh that is not closed the sign is still the formula's, and is meaningless near the holes: the library reports and does not
+ *   refuse.  Meshes uploaded by separate moptix_add_mesh calls weld like one.  Interpenetrating solids are not united.
+ *   moptix_debug_read_sign_table   a test aid, not an interface to build on: the table (computed first if stale, which counts as a build)
+ *                          copied to the host, 96 bytes per face; state errors as a query.
  * Nodes: the 64-byte form where the tree has one, else the 128-byte one; option "node_format" 64 / 128 forces either (same bits: the
  * 64-byte boxes contain the 128-byte ones, so the walk enters more boxes and finds the same minimum).
  *   moptix_query_points_device  dPoints, dOut: device memory, 16-byte aligned (dOut of MOPTIX_POINT_ANY: 4).  Asynchronous on the
@@ -658,11 +700,22 @@ int moptix_query_radiance(moptix_context ctx, const float* rays, int64_t n, cons
  *   moptix_query_points         host pointers, blocking: upload, query, read back (staging kept in the context)
  * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 points); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
  * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_rays ("faces dirty" before a refit included).  A point query
- * changes nothing else in the context, and in particular not the ray queries' buffers; moptix_debug_buffer_addresses keeps its slots. */
+ * changes nothing else in the context, and in particular not the ray queries' buffers; moptix_debug_buffer_addresses keeps its slots.
+ * A signed query shares the point queries' stack overflow area and keeps its topology and table beside it.
+ *   moptix_query_points_signed  the host-pointer, blocking form of MOPTIX_POINT_SIGNED (staging as moptix_query_points').  The mode is taken
+ *                               by moptix_query_points_device; moptix_query_points itself keeps the two modes it had, and 2 stays
+ *                               MOPTIX_ERR_INVALID there: nothing a caller of it relied on has changed. */
 typedef struct { float dist; int32_t prim; int32_t mat; float u, v; float p[3]; } moptix_point_hit;
-enum { MOPTIX_POINT_CLOSEST = 0, MOPTIX_POINT_ANY = 1 };
+enum { MOPTIX_POINT_CLOSEST = 0, MOPTIX_POINT_ANY = 1, MOPTIX_POINT_SIGNED = 2 };
+typedef struct {
+  uint32_t weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed, tableBuilds;
+  double signedVolume;
+} moptix_sign_info;
 int moptix_query_points_device(moptix_context ctx, const float* dPoints, int64_t n, int32_t mode, void* dOut);
 int moptix_query_points(moptix_context ctx, const float* points, int64_t n, int32_t mode, void* out);
+int moptix_query_points_signed(moptix_context ctx, const float* points, int64_t n, moptix_point_hit* out);
+int moptix_get_sign_info(moptix_context ctx, moptix_sign_info* out);
+int moptix_debug_read_sign_table(moptix_context ctx, void* table);
 
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.

@@ -168,7 +168,7 @@ class PointHit(C.Structure):
     _fields_ = [("dist", C.c_float), ("prim", C.c_int32), ("mat", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("p", C.c_float * 3)]
 
 
-POINT_CLOSEST, POINT_ANY = 0, 1
+POINT_CLOSEST, POINT_ANY, POINT_SIGNED = 0, 1, 2
 RADIANCE_CLAMP = 1
 
 
@@ -178,6 +178,17 @@ class RefitInfo(C.Structure):
 
     def as_dict(self):
         return dict(refitMs=float(self.refitMs), sahCost=float(self.sahCost), sahCostBuilt=float(self.sahCostBuilt), has64=int(self.has64))
+
+
+class SignInfo(C.Structure):
+    """moptix_sign_info: what moptix_get_sign_info reports of the faces' topology and the sign table."""
+    _fields_ = [(n, C.c_uint32) for n in ("weldedVerts", "edges", "boundaryEdges", "nonManifoldEdges", "flippedEdges", "degenerateFaces",
+                                          "closed", "tableBuilds")] + [("signedVolume", C.c_double)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_[:-1]}
+        d["signedVolume"] = float(self.signedVolume)
+        return d
 
 
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
@@ -198,7 +209,7 @@ DEVICE_SYMBOLS = [
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
     "moptix_query_rays_device", "moptix_query_rays", "moptix_query_radiance_device", "moptix_query_radiance",
-    "moptix_query_points_device", "moptix_query_points",
+    "moptix_query_points_device", "moptix_query_points", "moptix_query_points_signed", "moptix_get_sign_info", "moptix_debug_read_sign_table",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -299,6 +310,9 @@ def device_lib():
         L.moptix_query_radiance.argtypes = [vp, f32p, C.c_int64, i32p, u32p, i32, C.c_uint32, C.c_uint32, f32p]
         L.moptix_query_points_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_points.argtypes = [vp, f32p, C.c_int64, i32, vp]
+        L.moptix_query_points_signed.argtypes = [vp, f32p, C.c_int64, vp]
+        L.moptix_get_sign_info.argtypes = [vp, C.POINTER(SignInfo)]
+        L.moptix_debug_read_sign_table.argtypes = [vp, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]
         L.moptix_update_faces_device.argtypes = [vp, i32, i32, vp, vp]
         L.moptix_refit_accel.argtypes = [vp]

@@ -528,7 +528,7 @@ class Context:
         """Closest hit ("closest") or occlusion ("any") of the caller's rays, n x 8 floats o, d, tmin, tmax; blocking.
         A numpy array takes the host path: "closest" returns a HIT_DTYPE record array (t, prim, mat, u, v, ng), "any" an int32 array.
         A contiguous (n, 8) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
-        "any" an int32 tensor; "closest" a dict of views t, prim, mat, u, v, ng into "records", the (n, 8) float32 tensor of the
+        "any" an int32 tensor; "closest" and "signed" a dict of views t, prim, mat, u, v, ng into "records", the (n, 8) float32 tensor of the
         raw moptix_hit records."""
         if mode not in self.QUERY_MODES:
             raise ValueError("query_rays: mode %r (closest or any)" % (mode,))
@@ -624,17 +624,18 @@ class Context:
         return out
 
     # ---- point queries (include/moptix.h "point queries") ----
-    POINT_MODES = dict(closest=K.POINT_CLOSEST, any=K.POINT_ANY)
+    POINT_MODES = dict(closest=K.POINT_CLOSEST, any=K.POINT_ANY, signed=K.POINT_SIGNED)
 
     def query_points(self, points, mode="closest", max_dist=np.inf):
-        """The nearest surface point ("closest") or "is anything within max_dist" ("any") for the caller's points; blocking.
+        """The nearest surface point ("closest"), the same with dist negative inside a closed mesh or a sphere ("signed": sign_info() says
+        whether the mesh is closed), or "is anything within max_dist" ("any") for the caller's points; blocking.
         A numpy array takes the host path: (n, 3) positions with max_dist a scalar or an (n,) array, or (n, 4) rows x y z maxDist
-        (max_dist is then not consulted).  "closest" returns a POINT_DTYPE record array (dist, prim, mat, u, v, p), "any" an int32 array.
+        (max_dist is then not consulted).  "closest" and "signed" return a POINT_DTYPE record array (dist, prim, mat, u, v, p), "any" an int32 array.
         A contiguous (n, 4) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
-        "any" an int32 tensor; "closest" a dict of views dist, prim, mat, u, v, p into "records", the (n, 8) float32 tensor of the raw
+        "any" an int32 tensor; "closest" and "signed" a dict of views dist, prim, mat, u, v, p into "records", the (n, 8) float32 tensor of the raw
         moptix_point_hit records."""
         if mode not in self.POINT_MODES:
-            raise ValueError("query_points: mode %r (closest or any)" % (mode,))
+            raise ValueError("query_points: mode %r (closest, signed or any)" % (mode,))
         m = self.POINT_MODES[mode]
         if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
             pts = np.asarray(points, np.float32)
@@ -646,8 +647,12 @@ class Context:
                     raise ValueError("query_points: max_dist must be a scalar or one value per point")
                 pts = np.concatenate([pts, np.broadcast_to(md.reshape(-1, 1) if md.ndim else md, (len(pts), 1))], axis=1)
             pts = np.ascontiguousarray(pts, np.float32)
-            out = np.zeros(len(pts), POINT_DTYPE if m == K.POINT_CLOSEST else np.int32)
-            self._chk(self._L.moptix_query_points(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), m, C.c_void_p(out.ctypes.data)))
+            out = np.zeros(len(pts), np.int32 if m == K.POINT_ANY else POINT_DTYPE)
+            pp = pts.ctypes.data_as(C.POINTER(C.c_float))
+            if m == K.POINT_SIGNED:
+                self._chk(self._L.moptix_query_points_signed(self._h, pp, len(pts), C.c_void_p(out.ctypes.data)))
+            else:
+                self._chk(self._L.moptix_query_points(self._h, pp, len(pts), m, C.c_void_p(out.ctypes.data)))
             return out
         import torch
         if not points.is_cuda:
@@ -670,6 +675,20 @@ class Context:
             return out
         ints = out.view(torch.int32)
         return dict(records=out, dist=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], p=out[:, 5:8])
+
+    def sign_info(self):
+        """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed
+        (1: the faces form a closed, consistently wound surface), signedVolume (negative: wound inwards, every sign flipped), tableBuilds.
+        Works from the moment faces are uploaded."""
+        r = K.SignInfo()
+        self._chk(self._L.moptix_get_sign_info(self._h, C.byref(r)))
+        return r.as_dict()
+
+    def sign_table_read(self):
+        """A test aid: the device's table of pseudonormals, (nFaces, 24) float32 -- v0 v1 v2 e01 e02 e12, the unit face normal, padding."""
+        out = np.zeros((max(1, self.accel_info().nTriangles), 24), np.float32)
+        self._chk(self._L.moptix_debug_read_sign_table(self._h, C.c_void_p(out.ctypes.data)))
+        return out[:self.accel_info().nTriangles]
 
     # ---- mesh updates and refit (include/moptix.h "mesh updates and refit") ----
     def update_faces(self, first, positions, normals=None):

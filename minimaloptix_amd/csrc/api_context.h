@@ -10,6 +10,7 @@
 #include "lbvh.h"
 #include "megakernel.h"
 #include "refitkernel.h"
+#include "pt_signtopo.h"
 
 struct ncclComm;      // RCCL's communicator (api_comm.hip is the only file that sees RCCL's declarations)
 
@@ -252,6 +253,24 @@ struct moptix_context_t {
     void release() { drop(); points.release(); out.release(); }
   } point;
 
+  // ---- signed point queries (api_sign.hip) ----
+  // The topology belongs to one set of uploaded faces: taken on the host at the first signed query or moptix_get_sign_info, kept across
+  // moptix_update_faces*, moptix_refit_accel and moptix_build_accel, dropped by moptix_clear_scene, moptix_add_mesh and destroy.  Its
+  // device copy and the table are allocated at the first signed query and kept with it.  stale: the faces may have moved since the table
+  // was computed (set by the three calls that keep the topology); the next signed query enqueues the table build in front of its kernel.
+  struct Sign {
+    bool have = false, uploaded = false, stale = true;
+    pt::SignTopology topo;
+    uint32_t tableBuilds = 0;
+    DevBuf<int> faceIds, vertexStart, vertexCorner, edgeStart, edgeFace;
+    DevBuf<pt::SignFace> faces; DevBuf<pt::v4> vertexN, edgeN; DevBuf<pt::SignRecord> table;
+    void release() {
+      faceIds.release(); vertexStart.release(); vertexCorner.release(); edgeStart.release(); edgeFace.release();
+      faces.release(); vertexN.release(); edgeN.release(); table.release();
+      topo = pt::SignTopology(); have = false; uploaded = false; stale = true; tableBuilds = 0;
+    }
+  } sign;
+
   // ---- mesh updates and refit (api_refit.hip) ----
   // facesDirty: positions changed since the tree was built or refitted (check_ready refuses to trace); hostStale: the device copy of the
   // faces is ahead of the host staging (moptix_update_faces_device; moptix_build_accel fetches it back first); facesOnDevice: how many
@@ -288,6 +307,10 @@ int hipFail(moptix_context c, hipError_t e, const char* what);
 
 int check_ready(moptix_context c);                   // params set, tree built and fitted to the faces, stream alive
 int fetch_faces(moptix_context c);                   // api_refit.hip: the host staging catches up with device-side face updates
+// api_sign.hip, for api_point.hip: the signed mode of a point query, enqueued on the context's stream (the topology and the table first,
+// where they are missing or stale); the caller has filled a.p but for the sign table
+int enqueue_points_signed(moptix_context c, const float* dPoints, int64_t n, void* dOut);
+void sign_release(moptix_context c);                 // the topology goes (a query in flight finishes first)
 float* accum_ptr(moptix_context c);
 int ensure_accum(moptix_context c);
 // What a call that uses the device starts with: hipSetDevice, the batch in flight finishes (moptix_sync: timed, watchdog flag read) and,

@@ -134,6 +134,7 @@ int moptix_destroy(moptix_context c) {
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
   c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->radiance.release(); c->point.release(); c->refit.drop();
+  c->sign.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -187,6 +188,7 @@ int moptix_clear_scene(moptix_context c) {
     c->tp.faces.release();                                     // the face snapshot too
   }
   c->refit.drop(); c->refit.facesDirty = false; c->refit.hostStale = false; c->refit.facesOnDevice = 0;      // the faces are gone, and the plan with their tree
+  sign_release(c);                                             // and the signed queries' topology of them
   return MOPTIX_OK;
 }
 
@@ -272,6 +274,7 @@ int moptix_add_mesh(moptix_context c, const float* positions, int32_t nVerts, co
     c->faceUV.push_back(uv);
   }
   c->sceneDirty = true; c->accelBuilt = false;
+  if (nFaces > 0) sign_release(c);                             // the signed queries' topology describes the faces there were
   return MOPTIX_OK;
 }
 
@@ -366,6 +369,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
   c->formatDecided = false;            // choose_node_format at the next render: it needs the camera
   c->sceneDirty = false; c->accelBuilt = true; c->refit.facesDirty = false;
   c->tp.faces.changed = true;   // the device copy of the faces was uploaded afresh (the snapshot stays: the faces keep their upload order)
+  c->sign.stale = true;         // the signed queries' topology stays, their table is computed again from what was uploaded
   c->tiles.forget();            // new scene: forget which tiles had deep paths
   return MOPTIX_OK;
 }

@@ -1,4 +1,5 @@
-// api_point.hip -- closest-point queries (pointkernel.hip, pt_point.h): the two moptix_query_points* entry points of include/moptix.h.
+// api_point.hip -- closest-point queries (pointkernel.hip, pt_point.h): the moptix_query_points* entry points of include/moptix.h.
+// The signed mode is api_sign.hip's (enqueue_points_signed); its arguments are checked and its results staged here like the others'.
 #include <cstring>
 
 #include "api_context.h"
@@ -15,10 +16,12 @@ namespace {
 
 size_t out_bytes(int32_t mode) { return mode == MOPTIX_POINT_ANY ? sizeof(int32_t) : sizeof(moptix_point_hit); }
 
-int check_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out) {
+// withSigned: the entry takes MOPTIX_POINT_SIGNED.  moptix_query_points does not: its modes are the two it had (2 stays
+// MOPTIX_ERR_INVALID there, as callers and tests of it have it); the host-pointer form of the signed mode is moptix_query_points_signed.
+int check_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out, bool withSigned) {
   const int rc = check_ready(c);
   if (rc != MOPTIX_OK) return rc;
-  if (n < 0 || (mode != MOPTIX_POINT_CLOSEST && mode != MOPTIX_POINT_ANY)) return fail(c, MOPTIX_ERR_INVALID, "bad point count or query mode");
+  if (n < 0 || (mode != MOPTIX_POINT_CLOSEST && mode != MOPTIX_POINT_ANY && !(withSigned && mode == MOPTIX_POINT_SIGNED))) return fail(c, MOPTIX_ERR_INVALID, "bad point count or query mode");
   if (n > 0 && (!points || !out)) return fail(c, MOPTIX_ERR_INVALID, "null argument");
   return MOPTIX_OK;
 }
@@ -26,6 +29,7 @@ int check_points(moptix_context c, const float* points, int64_t n, int32_t mode,
 // Enqueues the query on the context's stream, in launches of at most kPointMaxLaunch points.  The stack overflow area is the point
 // queries' own: allocated at the first point query after a build, reused by every later one.
 int enqueue_points(moptix_context c, const float* dPoints, int64_t n, int32_t mode, void* dOut) {
+  if (mode == MOPTIX_POINT_SIGNED) return enqueue_points_signed(c, dPoints, n, dOut);
   PointArgs a;
   memset(&a, 0, sizeof(a));
   const int nBlocks = fill_query_view(c, a.scene);
@@ -48,7 +52,7 @@ int enqueue_points(moptix_context c, const float* dPoints, int64_t n, int32_t mo
 extern "C" {
 
 int moptix_query_points_device(moptix_context c, const float* dPoints, int64_t n, int32_t mode, void* dOut) {
-  int rc = check_points(c, dPoints, n, mode, dOut);
+  int rc = check_points(c, dPoints, n, mode, dOut, true);
   if (rc != MOPTIX_OK || n == 0) return rc;
   if ((reinterpret_cast<uintptr_t>(dPoints) & 15u) != 0 || (reinterpret_cast<uintptr_t>(dOut) & (mode == MOPTIX_POINT_ANY ? 3u : 15u)) != 0)
     return fail(c, MOPTIX_ERR_INVALID, "point queries read points and write records 16 bytes at a time: misaligned device pointer");
@@ -56,8 +60,8 @@ int moptix_query_points_device(moptix_context c, const float* dPoints, int64_t n
   return enqueue_points(c, dPoints, n, mode, dOut);
 }
 
-int moptix_query_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out) {
-  int rc = check_points(c, points, n, mode, out);
+static int query_points_host(moptix_context c, const float* points, int64_t n, int32_t mode, void* out, bool withSigned) {
+  int rc = check_points(c, points, n, mode, out, withSigned);
   if (rc != MOPTIX_OK || n == 0) return rc;
   if ((rc = begin_call(c, false)) != MOPTIX_OK) return rc;
   const size_t bytes = out_bytes(mode) * (size_t)n;
@@ -66,6 +70,14 @@ int moptix_query_points(moptix_context c, const float* points, int64_t n, int32_
   HIPCHK(c, hipMemcpyAsync(c->point.points.p, points, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream), "upload query points");
   if ((rc = enqueue_points(c, c->point.points.p, n, mode, c->point.out.p)) != MOPTIX_OK) return rc;
   return read_back(c, { { out, c->point.out.p, bytes } }, "read point query results");
+}
+
+int moptix_query_points(moptix_context c, const float* points, int64_t n, int32_t mode, void* out) {
+  return query_points_host(c, points, n, mode, out, false);
+}
+
+int moptix_query_points_signed(moptix_context c, const float* points, int64_t n, moptix_point_hit* out) {
+  return query_points_host(c, points, n, MOPTIX_POINT_SIGNED, out, true);
 }
 
 }  // extern "C"

@@ -7,13 +7,12 @@
 // The grid is ceil(n / 256) workgroups up to a cap of CUs x blocksPerCU; past the cap a lane goes on to the point one grid further
 // (grid-stride loop), so the stack overflow area is sized by the cap, not by n, and a result goes to its point's own index: nothing depends
 // on the scheduling.  A point is read as one 16-byte load, a record written as two 16-byte stores.
-// The traversal stack holds a child reference and the squared distance to its box side by side, eight bytes an entry: 16 entries per lane
-// in LDS ([entry][lane], 32 KB per workgroup as the ray queries' 32 four-byte ones) with a global overflow column per thread.
+// The traversal stack (pt_pointstack.h) holds a child reference and the squared distance to its box side by side, eight bytes an entry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "pt_lanestack.h"
+#include "pt_pointstack.h"
 #include "pt_point.h"
 #include "pointkernel.h"
 
@@ -21,20 +20,7 @@ namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = 256;
-constexpr int kWavesPerBlock = kBlockThreads / 64;
-constexpr int kLdsStack = 16;          // entries per lane kept in LDS (8 bytes each: 32 KB per workgroup)
-
-// LaneStack (pt_lanestack.h) over eight-byte entries: reference + box distance
-struct PointStack : LaneStack<kLdsStack, unsigned long long> {
-  __device__ __forceinline__ void store(int sp, int ref, float d2) {
-    LaneStack::store(sp, ((unsigned long long)(uint32_t)f2i(d2) << 32) | (uint32_t)ref);
-  }
-  __device__ __forceinline__ void load(int sp, int& ref, float& d2) const {
-    const unsigned long long e = LaneStack::load(sp);
-    ref = (int32_t)(uint32_t)e; d2 = i2f((int32_t)(e >> 32));
-  }
-};
+constexpr int kBlockThreads = kPointBlockThreads, kWavesPerBlock = kPointWavesPerBlock, kLdsStack = kPointLdsStack;      // pt_pointstack.h
 
 template <bool ANY, bool N64>
 __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a) {

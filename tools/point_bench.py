@@ -1,6 +1,6 @@
 """Point-query throughput on coffee (csrc/pointkernel.hip), with the ray queries' closest-hit time for the same count beside it for scale.
 
-    python3 tools/point_bench.py [--log2 20] [--reps 12] [--sweep]
+    python3 tools/point_bench.py [--log2 20] [--reps 12] [--sweep] [--signed]
 
 Scene file:coffee, tree built once.  Two device-resident point sets of 2^log2 points each:
   uniform   uniform in the scene box, maxDist = inf: every walk has to find the surface from wherever it starts
@@ -8,7 +8,10 @@ Scene file:coffee, tree built once.  Two device-resident point sets of 2^log2 po
 Timed with HIP events on the context's stream (a torch stream handed to moptix_set_stream), after a warm-up: median, minimum and maximum
 of --reps runs of moptix_query_points_device in closest and in any mode ("any" with maxDist = 1 % of the diagonal: with no limit it ends at
 the first primitive of the first leaf).  Then moptix_query_rays_device, closest, on as many incoherent rays (tools/query_bench.py's set).
---sweep adds the grid's cap ("query_blocks_per_cu") and the 128-byte nodes.  Prints the table that profiles/r16_point.txt keeps."""
+--sweep adds the grid's cap ("query_blocks_per_cu") and the 128-byte nodes.  Prints the table that profiles/r16_point.txt keeps.
+--signed adds the signed mode (csrc/signkernel.hip) on the same two point sets beside the closest mode, with their ratio, and the rebuild of
+the sign table after a refit: a signed query of 256 points with the table stale (moptix_update_faces + moptix_refit_accel before each run)
+against the same query with the table current, beside the refit's own refitMs (profiles/r17_sign.txt)."""
 import argparse
 import ctypes as C
 import os
@@ -54,6 +57,7 @@ def main():
     ap.add_argument("--log2", type=int, default=20)
     ap.add_argument("--reps", type=int, default=12)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--signed", action="store_true")
     a = ap.parse_args()
     n = 1 << a.log2
 
@@ -108,6 +112,36 @@ def main():
             ctx.set_option("node_format", 128)
             line("  node_format=128 closest, %s" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_CLOSEST, recs))
             ctx.set_option("node_format", 0)
+    if a.signed:
+        print("# sign_info: %s" % ctx.sign_info())
+        for name in ("uniform", "near"):
+            closest = line("pt_pointquery closest, %s, no limit" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_CLOSEST, recs))
+            signed = line("pt_pointsigned, %s, no limit" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_SIGNED, recs))
+            print("#   signed / closest %.3f; inside: %d of %d" % (signed / closest, int((recs[:, 0] < 0).sum()), n))
+        fp = hs.face_arrays()[0]
+        ext = float((hs.aabb_max - hs.aabb_min).max())
+        p3 = fp.reshape(-1, 3)
+        rows = (p3 + np.float32(0.01 * ext) * np.sin(7.0 * p3[:, [1, 2, 0]].astype(np.float64) + 0.3).astype(np.float32)).astype(np.float32).reshape(-1, 9)
+        small = sets["uniform"][:256].contiguous()
+        stale, current, refit = [], [], []
+        for i in range(a.reps + 2):
+            ctx.update_faces(0, rows if i % 2 == 0 else fp)
+            refit.append(ctx.refit_accel()["refitMs"])
+            for ms in (stale, current):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                rc = L.moptix_query_points_device(ctx._h, C.c_void_p(small.data_ptr()), 256, K.POINT_SIGNED, C.c_void_p(recs.data_ptr()))
+                assert rc == K.MOPTIX_OK, ctx.last_error()
+                e1.record(stream)
+                stream.synchronize()
+                if i >= 2:
+                    ms.append(e0.elapsed_time(e1))
+        refit = sorted(refit[2:])
+        t_stale = line("signed query of 256 points, table stale (rebuilt first)", 256, stale)
+        t_cur = line("signed query of 256 points, table current", 256, current)
+        print("#   table rebuild %.3f ms beside refitMs %.3f ms (median): %.3f of the refit; tableBuilds %d" % (
+            t_stale - t_cur, refit[len(refit) // 2], (t_stale - t_cur) / refit[len(refit) // 2], ctx.sign_info()["tableBuilds"]))
+        ctx.update_faces(0, fp); ctx.refit_accel()
     rays = torch.from_numpy(ray_set(hs, "incoherent", n)).to(dev)
     torch.cuda.synchronize()
     line("for scale: pt_rayquery closest, incoherent rays", n, timed(L.moptix_query_rays_device, rays, K.QUERY_CLOSEST, recs), "Mrays/s")
