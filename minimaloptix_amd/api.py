@@ -35,6 +35,33 @@ def launch_seeds(n, base_seed=0, first=0):
     return np.array([_tea16(first + i, base_seed) for i in range(n)], dtype=np.uint32).view(np.int32)
 
 
+def _check_tensor(who, name, t, dtypes, shape, expect, device=None, on_gpu=True):
+    """ValueError unless `t`, the argument `name` of the method `who`, is a torch tensor whose data_ptr a kernel can take: on the GPU
+    (on_gpu) and there on GPU `device` (an index, or None for any), contiguous, of `shape` -- an element count or a predicate, worded for
+    the message by `expect` -- and of one of `dtypes`."""
+    if on_gpu and (not hasattr(t, "data_ptr") or not t.is_cuda):
+        raise ValueError("%s: %s must live on the GPU (its data_ptr is handed to a kernel); numpy arrays take the host path" % (who, name))
+    if not t.is_contiguous() or not (shape(t) if callable(shape) else t.numel() == shape):
+        raise ValueError("%s: %s must be a contiguous tensor of %s" % (who, name, expect))
+    if str(t.dtype) not in dtypes:
+        raise ValueError("%s: %s has dtype %s" % (who, name, t.dtype))
+    if device is not None and t.device.index != device:
+        raise ValueError("%s: %s is on %s, the context on GPU %d" % (who, name, t.device, device))
+
+
+def _rows(k):
+    """_check_tensor's shape predicate for an (n, k) tensor."""
+    return lambda t: t.dim() == 2 and t.shape[1] == k
+
+
+def _record_views(out, first, last):
+    """The (n, 8) float32 tensor of moptix_hit / moptix_point_hit records as a dict of views: "records" itself, word 0 under the name
+    `first`, prim, mat, u, v, and words 5 .. 7 under the name `last`."""
+    import torch
+    ints = out.view(torch.int32)
+    return {"records": out, first: out[:, 0], "prim": ints[:, 1], "mat": ints[:, 2], "u": out[:, 3], "v": out[:, 4], last: out[:, 5:8]}
+
+
 def _f3(v):
     return [float(v.x), float(v.y), float(v.z)]
 
@@ -230,6 +257,11 @@ class Context:
         self._chk(self._L.moptix_get_accel_info(self._h, C.byref(a)))
         return a
 
+    def _frame(self, k=3, dtype=np.float32):
+        """An (H, W, k) output array, (H, W) for k = 0, and its pointer as the C ABI takes it."""
+        out = np.empty((self.height, self.width, k) if k else (self.height, self.width), dtype)
+        return out, out.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype)))
+
     @staticmethod
     def _seeds(seeds):
         s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32))
@@ -256,8 +288,8 @@ class Context:
         return st
 
     def accum_read(self):
-        out = np.empty((self.height, self.width, 3), np.float32)
-        self._chk(self._L.moptix_accum_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        out, p = self._frame()
+        self._chk(self._L.moptix_accum_read(self._h, p))
         return out
 
     def accum_clear(self):
@@ -275,9 +307,8 @@ class Context:
         self._chk(self._L.moptix_set_stream(self._h, C.c_void_p(hip_stream)))
 
     def resolve_rgb8(self, n_accumulation, clear=False):
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        self._chk(self._L.moptix_resolve_rgb8(self._h, float(n_accumulation), 1 if clear else 0,
-                                              out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        out, p = self._frame(3, np.uint8)
+        self._chk(self._L.moptix_resolve_rgb8(self._h, float(n_accumulation), 1 if clear else 0, p))
         return out
 
     def kernel_time(self, reset=False):
@@ -346,8 +377,7 @@ class Context:
     def aov_read(self):
         """{name: (H, W, k) array} in the accumulation buffer's row order (row 0 = bottom): albedo, normal (k = 3), depth, hits
         (float32, k = 1), primId, matId (int32, k = 1)."""
-        out = {n: np.empty((self.height, self.width, self.AOV_CHANNELS[n]), np.int32 if n in ("primId", "matId") else np.float32)
-               for n in self.AOV_NAMES}
+        out = {n: self._frame(self.AOV_CHANNELS[n], np.int32 if n in ("primId", "matId") else np.float32)[0] for n in self.AOV_NAMES}
         b = K.AovBuffers(*[out[n].ctypes.data for n in self.AOV_NAMES])
         self._chk(self._L.moptix_aov_read(self._h, C.byref(b)))
         return out
@@ -364,10 +394,9 @@ class Context:
             if t is None:
                 ptrs.append(None)
                 continue
-            if not t.is_contiguous() or t.numel() != self.height * self.width * self.AOV_CHANNELS[n]:
-                raise ValueError("aov_bind: %s must be a contiguous tensor of %d x %d x %d elements" % (n, self.height, self.width, self.AOV_CHANNELS[n]))
-            if str(t.dtype) != ("torch.int32" if n in ("primId", "matId") else "torch.float32"):
-                raise ValueError("aov_bind: %s has dtype %s" % (n, t.dtype))
+            k = self.AOV_CHANNELS[n]
+            _check_tensor("aov_bind", n, t, ("torch.int32" if n in ("primId", "matId") else "torch.float32",), self.height * self.width * k,
+                          "%d x %d x %d elements" % (self.height, self.width, k), on_gpu=False)
             ptrs.append(t.data_ptr())
         b = K.AovBuffers(*ptrs)
         self._chk(self._L.moptix_aov_bind(self._h, C.byref(b)))
@@ -394,8 +423,8 @@ class Context:
         blocking.  Returns an (H, W, 3) float32 array in accum_read's row order (row 0 = bottom)."""
         p = K.DenoiseParams(int(iterations), int(normal_power), 1 if demodulate else 0, float(sigma_luminance), float(sigma_depth))
         self._chk(self._L.moptix_denoise(self._h, C.byref(p), float(n_accumulation)))
-        out = np.empty((self.height, self.width, 3), np.float32)
-        self._chk(self._L.moptix_denoise_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        out, op = self._frame()
+        self._chk(self._L.moptix_denoise_read(self._h, op))
         return out
 
     def denoise_bind(self, tensor):
@@ -404,10 +433,8 @@ class Context:
         if tensor is None:
             self._chk(self._L.moptix_denoise_bind(self._h, None))
             return
-        if not tensor.is_contiguous() or tensor.numel() != self.height * self.width * 3:
-            raise ValueError("denoise_bind: must be a contiguous tensor of %d x %d x 3 elements" % (self.height, self.width))
-        if str(tensor.dtype) != "torch.float32":
-            raise ValueError("denoise_bind: dtype %s" % tensor.dtype)
+        _check_tensor("denoise_bind", "the tensor", tensor, ("torch.float32",), self.height * self.width * 3,
+                      "%d x %d x 3 elements" % (self.height, self.width), on_gpu=False)
         self._chk(self._L.moptix_denoise_bind(self._h, C.c_void_p(tensor.data_ptr())))
 
     # ---- temporal accumulation (include/moptix.h "denoiser: temporal accumulation") ----
@@ -433,8 +460,8 @@ class Context:
                               int(t["max_history"]), int(t["variance_frames"]))
         p = K.DenoiseParams(int(iterations), int(normal_power), 1 if demodulate else 0, float(sigma_luminance), float(sigma_depth))
         self._chk(self._L.moptix_denoise_temporal(self._h, C.byref(p), C.byref(tp), float(n_accumulation)))
-        out = np.empty((self.height, self.width, 3), np.float32)
-        self._chk(self._L.moptix_denoise_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        out, op = self._frame()
+        self._chk(self._L.moptix_denoise_read(self._h, op))
         return out
 
     def temporal_reset(self):
@@ -457,8 +484,7 @@ class Context:
 
     def temporal_read(self):
         """Of the last denoise_temporal call: dict(motion=(H, W, 2) float32 pixel motion vectors, history=(H, W) float32 lengths)."""
-        motion = np.empty((self.height, self.width, 2), np.float32)
-        history = np.empty((self.height, self.width), np.float32)
+        motion, history = self._frame(2)[0], self._frame(0)[0]
         b = K.TemporalBuffers(motion.ctypes.data, history.ctypes.data)
         self._chk(self._L.moptix_temporal_read(self._h, C.byref(b)))
         return dict(motion=motion, history=history)
@@ -493,32 +519,27 @@ class Context:
     def adaptive_read(self):
         """dict(count=(H, W) uint32, moments=(H, W, 2) float32, error=(H, W) float32, converged=(H, W) uint8) in accum_read's row
         order (row 0 = bottom)."""
-        out = dict(count=np.empty((self.height, self.width), np.uint32), moments=np.empty((self.height, self.width, 2), np.float32),
-                   error=np.empty((self.height, self.width), np.float32), converged=np.empty((self.height, self.width), np.uint8))
+        out = dict(count=self._frame(0, np.uint32)[0], moments=self._frame(2)[0], error=self._frame(0)[0], converged=self._frame(0, np.uint8)[0])
         b = K.AdaptiveBuffers(*[out[n].ctypes.data for n in ("count", "moments", "error", "converged")])
         self._chk(self._L.moptix_adaptive_read(self._h, C.byref(b)))
         return out
 
     def adaptive_mean(self):
         """accum / count per pixel (0 where count is 0): an (H, W, 3) float32 array in accum_read's row order."""
-        out = np.empty((self.height, self.width, 3), np.float32)
-        self._chk(self._L.moptix_adaptive_mean(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        out, p = self._frame()
+        self._chk(self._L.moptix_adaptive_mean(self._h, p))
         return out
 
     def adaptive_mean_into(self, tensor):
         """The same into a torch float32 tensor on this context's device, contiguous, H*W*3 elements."""
-        if not tensor.is_contiguous() or tensor.numel() != self.height * self.width * 3:
-            raise ValueError("adaptive_mean_into: must be a contiguous tensor of %d x %d x 3 elements" % (self.height, self.width))
-        if str(tensor.dtype) != "torch.float32":
-            raise ValueError("adaptive_mean_into: dtype %s" % tensor.dtype)
-        if not tensor.is_cuda:
-            raise ValueError("adaptive_mean_into: the tensor must live on the GPU (its data_ptr is handed to a kernel)")
+        _check_tensor("adaptive_mean_into", "the tensor", tensor, ("torch.float32",), self.height * self.width * 3,
+                      "%d x %d x 3 elements" % (self.height, self.width))      # any GPU, as before: device is left None
         self._chk(self._L.moptix_adaptive_mean_device(self._h, C.c_void_p(tensor.data_ptr())))
 
     def adaptive_resolve_rgb8(self):
         """resolve_rgb8 with each pixel's own count as the divisor: (H, W, 3) uint8, row 0 = top."""
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        self._chk(self._L.moptix_adaptive_resolve_rgb8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        out, p = self._frame(3, np.uint8)
+        self._chk(self._L.moptix_adaptive_resolve_rgb8(self._h, p))
         return out
 
     # ---- ray queries (include/moptix.h "ray queries") ----
@@ -528,8 +549,8 @@ class Context:
         """Closest hit ("closest") or occlusion ("any") of the caller's rays, n x 8 floats o, d, tmin, tmax; blocking.
         A numpy array takes the host path: "closest" returns a HIT_DTYPE record array (t, prim, mat, u, v, ng), "any" an int32 array.
         A contiguous (n, 8) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
-        "any" an int32 tensor; "closest" and "signed" a dict of views t, prim, mat, u, v, ng into "records", the (n, 8) float32 tensor of the
-        raw moptix_hit records."""
+        "any" an int32 tensor; "closest" a dict of views t, prim, mat, u, v, ng into "records", the (n, 8) float32 tensor of the raw
+        moptix_hit records."""
         if mode not in self.QUERY_MODES:
             raise ValueError("query_rays: mode %r (closest or any)" % (mode,))
         m = self.QUERY_MODES[mode]
@@ -539,14 +560,7 @@ class Context:
             self._chk(self._L.moptix_query_rays(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), m, C.c_void_p(out.ctypes.data)))
             return out
         import torch
-        if not rays.is_cuda:
-            raise ValueError("query_rays: the tensor must live on the GPU (its data_ptr is handed to a kernel); pass a numpy array for the host path")
-        if str(rays.dtype) != "torch.float32":
-            raise ValueError("query_rays: dtype %s" % rays.dtype)
-        if rays.device.index != self.device:
-            raise ValueError("query_rays: the tensor is on %s, the context on GPU %d" % (rays.device, self.device))
-        if not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("query_rays: must be a contiguous (n, 8) tensor")
+        _check_tensor("query_rays", "rays", rays, ("torch.float32",), _rows(8), "shape (n, 8)", self.device)
         n = rays.shape[0]
         if m == K.QUERY_ANY:
             out = torch.empty(n, dtype=torch.int32, device=rays.device)
@@ -557,8 +571,7 @@ class Context:
         self.sync()
         if m == K.QUERY_ANY:
             return out
-        ints = out.view(torch.int32)
-        return dict(records=out, t=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], ng=out[:, 5:8])
+        return _record_views(out, "t", "ng")
 
     def query_radiance(self, rays, seeds=None, states=None, clamp=False, index_base=0):
         """Path-traced radiance along the caller's rays, n x 8 floats o, d, tmin, tmax with UNIT directions; blocking.  Returns (n, 4)
@@ -595,25 +608,13 @@ class Context:
                                                     out.ctypes.data_as(C.POINTER(C.c_float))))
             return out
         import torch
-        tensors = [("rays", rays, ("torch.float32",))]
+        _check_tensor("query_radiance", "rays", rays, ("torch.float32",), _rows(8), "shape (n, 8)", self.device)
+        n = rays.shape[0]
         if states is not None:
             if not hasattr(states, "data_ptr"):
                 raise ValueError("query_radiance: states follow the rays: a tensor on the rays' device")
-            tensors.append(("states", states, ("torch.uint32", "torch.int32")))
-        for name, t, dtypes in tensors:
-            if not t.is_cuda:
-                raise ValueError("query_radiance: %s must live on the GPU (its data_ptr is handed to a kernel); pass numpy arrays for the host path" % name)
-            if str(t.dtype) not in dtypes:
-                raise ValueError("query_radiance: %s has dtype %s" % (name, t.dtype))
-            if t.device.index != self.device:
-                raise ValueError("query_radiance: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
-            if not t.is_contiguous() or t.dim() != 2:
-                raise ValueError("query_radiance: %s must be a contiguous 2-d tensor" % name)
-        if rays.shape[1] != 8:
-            raise ValueError("query_radiance: rays must be (n, 8)")
-        n = rays.shape[0]
-        if states is not None and (states.shape[0] != n or states.shape[1] < 1):
-            raise ValueError("query_radiance: states must be (n, nSamples)")
+            _check_tensor("query_radiance", "states", states, ("torch.uint32", "torch.int32"),
+                          lambda t: t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1, "shape (n, nSamples)", self.device)
         ns = len(sd) if sd is not None else states.shape[1]
         out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
         torch.cuda.current_stream(rays.device).synchronize()      # the rays are ready before the context's stream reads them
@@ -655,14 +656,7 @@ class Context:
                 self._chk(self._L.moptix_query_points(self._h, pp, len(pts), m, C.c_void_p(out.ctypes.data)))
             return out
         import torch
-        if not points.is_cuda:
-            raise ValueError("query_points: the tensor must live on the GPU (its data_ptr is handed to a kernel); pass a numpy array for the host path")
-        if str(points.dtype) != "torch.float32":
-            raise ValueError("query_points: dtype %s" % points.dtype)
-        if points.device.index != self.device:
-            raise ValueError("query_points: the tensor is on %s, the context on GPU %d" % (points.device, self.device))
-        if not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 4:
-            raise ValueError("query_points: must be a contiguous (n, 4) tensor x y z maxDist")
+        _check_tensor("query_points", "points", points, ("torch.float32",), _rows(4), "shape (n, 4), x y z maxDist", self.device)
         n = points.shape[0]
         if m == K.POINT_ANY:
             out = torch.empty(n, dtype=torch.int32, device=points.device)
@@ -673,8 +667,7 @@ class Context:
         self.sync()
         if m == K.POINT_ANY:
             return out
-        ints = out.view(torch.int32)
-        return dict(records=out, dist=out[:, 0], prim=ints[:, 1], mat=ints[:, 2], u=out[:, 3], v=out[:, 4], p=out[:, 5:8])
+        return _record_views(out, "dist", "p")
 
     def sign_info(self):
         """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed
@@ -708,14 +701,8 @@ class Context:
         for name, t in (("positions", positions), ("normals", normals)):
             if t is None:
                 continue
-            if not hasattr(t, "data_ptr") or not t.is_cuda:
-                raise ValueError("update_faces: %s must live on the GPU like the positions (pass numpy arrays for the host path)" % name)
-            if str(t.dtype) != "torch.float32":
-                raise ValueError("update_faces: %s has dtype %s" % (name, t.dtype))
-            if t.device.index != self.device:
-                raise ValueError("update_faces: %s is on %s, the context on GPU %d" % (name, t.device, self.device))
-            if not t.is_contiguous() or t.numel() % 9 != 0 or t.numel() != positions.numel():
-                raise ValueError("update_faces: %s must be a contiguous tensor of 9 floats per face" % name)
+            _check_tensor("update_faces", name, t, ("torch.float32",), lambda t: t.numel() % 9 == 0 and t.numel() == positions.numel(),
+                          "9 floats per face, as many faces as the positions", self.device)
         n = positions.numel() // 9
         torch.cuda.current_stream(positions.device).synchronize()      # the values are ready before the context's stream copies them
         self._chk(self._L.moptix_update_faces_device(self._h, int(first), n, C.c_void_p(positions.data_ptr() if n else None),

@@ -307,9 +307,9 @@ int hipFail(moptix_context c, hipError_t e, const char* what);
 
 int check_ready(moptix_context c);                   // params set, tree built and fitted to the faces, stream alive
 int fetch_faces(moptix_context c);                   // api_refit.hip: the host staging catches up with device-side face updates
-// api_sign.hip, for api_point.hip: the signed mode of a point query, enqueued on the context's stream (the topology and the table first,
-// where they are missing or stale); the caller has filled a.p but for the sign table
-int enqueue_points_signed(moptix_context c, const float* dPoints, int64_t n, void* dOut);
+// api_sign.hip, for api_point.hip: the sign table as the faces are now, for a kernel enqueued after this call (the topology, its upload and
+// the table build are enqueued on the context's stream where they are missing or stale); null in a scene without triangles
+int sign_table_for_query(moptix_context c, const SignRecord*& table);
 void sign_release(moptix_context c);                 // the topology goes (a query in flight finishes first)
 float* accum_ptr(moptix_context c);
 int ensure_accum(moptix_context c);

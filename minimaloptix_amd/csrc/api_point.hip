@@ -1,16 +1,15 @@
 // api_point.hip -- closest-point queries (pointkernel.hip, pt_point.h): the moptix_query_points* entry points of include/moptix.h.
-// The signed mode is api_sign.hip's (enqueue_points_signed); its arguments are checked and its results staged here like the others'.
+// The signed mode's table is api_sign.hip's (sign_table_for_query); everything else of the three modes is here.
 #include <cstring>
 
 #include "api_context.h"
-#include "pt_point.h"
 #include "pointkernel.h"
 
 using namespace pt;
 using namespace pt::api;
 
 static_assert(sizeof(moptix_point_hit) == sizeof(PointHit), "moptix_point_hit is the kernel's record");
-static_assert(MOPTIX_POINT_CLOSEST == POINT_CLOSEST && MOPTIX_POINT_ANY == POINT_ANY, "point query modes");
+static_assert(MOPTIX_POINT_CLOSEST == POINT_CLOSEST && MOPTIX_POINT_ANY == POINT_ANY && MOPTIX_POINT_SIGNED == POINT_SIGNED, "point query modes");
 
 namespace {
 
@@ -27,9 +26,14 @@ int check_points(moptix_context c, const float* points, int64_t n, int32_t mode,
 }
 
 // Enqueues the query on the context's stream, in launches of at most kPointMaxLaunch points.  The stack overflow area is the point
-// queries' own: allocated at the first point query after a build, reused by every later one.
+// queries' own: allocated at the first point query after a build, reused by every later one.  The signed mode's table goes first: the
+// topology, its upload and the table build are in front of the query kernel on the stream.
 int enqueue_points(moptix_context c, const float* dPoints, int64_t n, int32_t mode, void* dOut) {
-  if (mode == MOPTIX_POINT_SIGNED) return enqueue_points_signed(c, dPoints, n, dOut);
+  const SignRecord* table = nullptr;
+  if (mode == MOPTIX_POINT_SIGNED) {
+    const int rc = sign_table_for_query(c, table);
+    if (rc != MOPTIX_OK) return rc;
+  }
   PointArgs a;
   memset(&a, 0, sizeof(a));
   const int nBlocks = fill_query_view(c, a.scene);
@@ -42,7 +46,7 @@ int enqueue_points(moptix_context c, const float* dPoints, int64_t n, int32_t mo
     a.points = dPoints + 4 * first;
     a.out = static_cast<char*>(dOut) + out_bytes(mode) * (size_t)first;
     a.n = (int)(n - first < kPointMaxLaunch ? n - first : kPointMaxLaunch);
-    HIPCHK(c, launch_pointquery(c->stream, a, nBlocks, mode), "launch point query");
+    HIPCHK(c, launch_pointquery(c->stream, a, table, nBlocks, mode), mode == MOPTIX_POINT_SIGNED ? "launch signed point query" : "launch point query");
   }
   return MOPTIX_OK;
 }

@@ -1,5 +1,5 @@
 // api_sign.hip -- signed point queries (signkernel.hip, pt_sign.h, pt_signtopo.h): the topology of the uploaded faces, the table of
-// pseudonormals on the device, the signed mode of moptix_query_points* (entered from api_point.hip), moptix_get_sign_info and the test
+// pseudonormals on the device (what the signed mode of moptix_query_points* asks for, api_point.hip), moptix_get_sign_info and the test
 // aid moptix_debug_read_sign_table of include/moptix.h.
 #include <cstring>
 
@@ -9,7 +9,6 @@
 using namespace pt;
 using namespace pt::api;
 
-static_assert(MOPTIX_POINT_SIGNED == POINT_SIGNED, "point query modes");
 static_assert(sizeof(SignRecord) == 96, "moptix_debug_read_sign_table: 96 bytes per face");
 
 namespace {
@@ -77,25 +76,10 @@ void sign_release(moptix_context c) {
   s.release();
 }
 
-int enqueue_points_signed(moptix_context c, const float* dPoints, int64_t n, void* dOut) {
-  int rc = ensure_table(c);
-  if (rc != MOPTIX_OK) return rc;
-  PointSignedArgs a;
-  memset(&a, 0, sizeof(a));
-  const int nBlocks = fill_query_view(c, a.p.scene);
-  const size_t ovf = a.p.scene.rootRef != kEmptyRef ? pointkernel_overflow_entries(nBlocks, c->bvh.stackBound) : 0;
-  if (ovf > 0) {
-    HIPCHK(c, c->point.overflow.ensure(ovf), "alloc point query stack overflow area");
-    a.p.stackOverflow = c->point.overflow.p;
-  }
-  a.table = c->sign.table.p;
-  for (int64_t first = 0; first < n; first += kPointMaxLaunch) {
-    a.p.points = dPoints + 4 * first;
-    a.p.out = static_cast<char*>(dOut) + sizeof(moptix_point_hit) * (size_t)first;
-    a.p.n = (int)(n - first < kPointMaxLaunch ? n - first : kPointMaxLaunch);
-    HIPCHK(c, launch_pointsigned(c->stream, a, nBlocks), "launch signed point query");
-  }
-  return MOPTIX_OK;
+int sign_table_for_query(moptix_context c, const SignRecord*& table) {
+  const int rc = ensure_table(c);
+  if (rc == MOPTIX_OK) table = c->sign.table.p;
+  return rc;
 }
 
 }}  // namespace pt::api

@@ -1,7 +1,7 @@
-// pointkernel.h -- launch interface of pointkernel.hip (closest-point queries, pt_point.h)
+// pointkernel.h -- launch interface of pointkernel.hip (closest-point queries, pt_point.h, and their signed mode, pt_sign.h)
 #pragma once
 #include <hip/hip_runtime.h>
-#include "pt_types.h"
+#include "pt_sign.h"
 
 namespace pt {
 
@@ -12,10 +12,15 @@ struct PointArgs {
   int n;                          // points of this launch (the host cuts longer batches: indices stay 32-bit)
   unsigned long long* stackOverflow;   // per-thread spill area (reference + box distance per entry) for trees deeper than the LDS stack, or null
 };
+struct PointSignedArgs {          // what the signed mode's kernel takes
+  PointArgs p;                    // out: n x PointHit
+  const SignRecord* table;        // one record per original face id; may be null in a scene without triangles
+};
 constexpr int kPointMaxLaunch = 1 << 30;      // points per launch
 
 size_t pointkernel_overflow_entries(int nBlocks, int stackBound);     // 8-byte entries; 0 = the tree fits the LDS stack
-// mode: POINT_CLOSEST / POINT_ANY (pt_point.h).  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
-hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode);
+// mode: POINT_CLOSEST / POINT_ANY (pt_point.h) / POINT_SIGNED (pt_sign.h).  table: the signed mode's; null for the other two and for a
+// scene without triangles.  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
+hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, const SignRecord* table, int nBlocks, int mode);
 
 }  // namespace pt

@@ -7,24 +7,46 @@
 // The grid is ceil(n / 256) workgroups up to a cap of CUs x blocksPerCU; past the cap a lane goes on to the point one grid further
 // (grid-stride loop), so the stack overflow area is sized by the cap, not by n, and a result goes to its point's own index: nothing depends
 // on the scheduling.  A point is read as one 16-byte load, a record written as two 16-byte stores.
-// The traversal stack (pt_pointstack.h) holds a child reference and the squared distance to its box side by side, eight bytes an entry.
+// The traversal stack holds a child reference and the squared distance to its box side by side, eight bytes an entry: 16 entries per lane
+// in LDS ([entry][lane], 32 KB per workgroup as the ray queries' 32 four-byte ones) with a global overflow column per thread.
+// The signed mode is the closest walk followed by point_hit_signed (pt_sign.h): the feature of the winner, one v3 of its sign record, the
+// sign.  Its argument record carries the table behind the others' (PointSignedArgs), so the kernel is a template over the record too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "pt_pointstack.h"
-#include "pt_point.h"
+#include "pt_lanestack.h"
+#include "pt_sign.h"
 #include "pointkernel.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = kPointBlockThreads, kWavesPerBlock = kPointWavesPerBlock, kLdsStack = kPointLdsStack;      // pt_pointstack.h
+constexpr int kBlockThreads = 256;
+constexpr int kWavesPerBlock = kBlockThreads / 64;
+constexpr int kLdsStack = 16;          // entries per lane kept in LDS (8 bytes each: 32 KB per workgroup)
 
-template <bool ANY, bool N64>
-__global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a) {
+// LaneStack (pt_lanestack.h) over eight-byte entries: reference + box distance
+struct PointStack : LaneStack<kLdsStack, unsigned long long> {
+  __device__ __forceinline__ void store(int sp, int ref, float d2) {
+    LaneStack::store(sp, ((unsigned long long)(uint32_t)f2i(d2) << 32) | (uint32_t)ref);
+  }
+  __device__ __forceinline__ void load(int sp, int& ref, float& d2) const {
+    const unsigned long long e = LaneStack::load(sp);
+    ref = (int32_t)(uint32_t)e; d2 = i2f((int32_t)(e >> 32));
+  }
+};
+
+__device__ __forceinline__ const PointArgs& point_args(const PointArgs& s) { return s; }
+__device__ __forceinline__ const PointArgs& point_args(const PointSignedArgs& s) { return s.p; }
+
+// MODE: POINT_CLOSEST / POINT_ANY over PointArgs, POINT_SIGNED over PointSignedArgs
+template <int MODE, bool N64, class Args>
+__global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const Args s) {
+  constexpr bool ANY = MODE == POINT_ANY;
   __shared__ unsigned long long ldsStack[kWavesPerBlock * kLdsStack * 64];
+  const PointArgs& a = point_args(s);
   const SceneView& sc = a.scene;
   const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
   PointStack st;
@@ -41,7 +63,8 @@ __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a
       static_cast<int*>(a.out)[i] = tv.bestPrim >= 0 ? 1 : 0;
     } else {
       PointHit h;
-      point_hit(sc, q, p[3], tv, h);
+      if constexpr (MODE == POINT_SIGNED) point_hit_signed(sc, s.table, q, p[3], tv, h);
+      else point_hit(sc, q, p[3], tv, h);
       uint4* o = static_cast<uint4*>(a.out) + 2 * (size_t)i;
       o[0] = make_uint4((uint32_t)f2i(h.dist), (uint32_t)h.prim, (uint32_t)h.mat, (uint32_t)f2i(h.u));
       o[1] = make_uint4((uint32_t)f2i(h.v), (uint32_t)f2i(h.p[0]), (uint32_t)f2i(h.p[1]), (uint32_t)f2i(h.p[2]));
@@ -53,15 +76,19 @@ __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const PointArgs a
 
 size_t pointkernel_overflow_entries(int nBlocks, int stackBound) { return lane_stack_overflow_entries((size_t)nBlocks * kBlockThreads, stackBound, kLdsStack); }
 
-hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, int nBlocks, int mode) {
+hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, const SignRecord* table, int nBlocks, int mode) {
   const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);
   const bool n64 = a.scene.nodes64 != nullptr;
-  if (mode == POINT_ANY) {
-    if (n64) pt_pointquery<true, true><<<blocks, kBlockThreads, 0, stream>>>(a);
-    else     pt_pointquery<true, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+  if (mode == POINT_SIGNED) {
+    const PointSignedArgs s = { a, table };
+    if (n64) pt_pointquery<POINT_SIGNED, true><<<blocks, kBlockThreads, 0, stream>>>(s);
+    else     pt_pointquery<POINT_SIGNED, false><<<blocks, kBlockThreads, 0, stream>>>(s);
+  } else if (mode == POINT_ANY) {
+    if (n64) pt_pointquery<POINT_ANY, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery<POINT_ANY, false><<<blocks, kBlockThreads, 0, stream>>>(a);
   } else {
-    if (n64) pt_pointquery<false, true><<<blocks, kBlockThreads, 0, stream>>>(a);
-    else     pt_pointquery<false, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+    if (n64) pt_pointquery<POINT_CLOSEST, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery<POINT_CLOSEST, false><<<blocks, kBlockThreads, 0, stream>>>(a);
   }
   return hipGetLastError();
 }

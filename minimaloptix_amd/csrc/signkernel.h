@@ -1,7 +1,6 @@
-// signkernel.h -- launch interface of signkernel.hip (signed point queries and their table of pseudonormals, pt_sign.h)
+// signkernel.h -- launch interface of signkernel.hip (the signed point queries' table of pseudonormals, pt_sign.h)
 #pragma once
 #include <hip/hip_runtime.h>
-#include "pointkernel.h"
 #include "pt_sign.h"
 
 namespace pt {
@@ -20,12 +19,5 @@ struct SignBuildArgs {
 };
 // Three passes on `stream`: per face (unit normal, corner angles), per welded vertex and per edge (the ordered sums), per face (the record).
 hipError_t launch_sign_table(hipStream_t stream, const SignBuildArgs& a);
-
-struct PointSignedArgs {
-  PointArgs p;                    // out: n x PointHit
-  const SignRecord* table;        // one record per original face id; may be null in a scene without triangles
-};
-// The point kernel's launch (launch_pointquery) with the signed epilogue; the stack overflow area is the point queries' own.
-hipError_t launch_pointsigned(hipStream_t stream, const PointSignedArgs& a, int nBlocks);
 
 }  // namespace pt

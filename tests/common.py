@@ -46,6 +46,11 @@ class RefitsimOut(C.Structure):
                 ("nNodes", C.c_int32), ("rootRef", C.c_int32), ("has64", C.c_int32), ("sahCost", C.c_double), ("sahCostBuilt", C.c_double)]
 
 
+class SignsimInfo(C.Structure):      # signsim.cpp signsim_info: moptix_sign_info
+    _fields_ = [(n, C.c_uint32) for n in ("weldedVerts", "edges", "boundaryEdges", "nonManifoldEdges", "flippedEdges", "degenerateFaces", "closed",
+                                          "tableBuilds")] + [("signedVolume", C.c_double)]
+
+
 def hostsim_lib():
     """tests/hostsim/libhostsim.so, every CPU mirror in one library: the only loader, and every signature in one place."""
     global _hostsim
@@ -60,7 +65,8 @@ def hostsim_lib():
         def sig(name, argtypes, restype=C.c_int):
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype
-        # the built scene: a handle, and what traces on it (hostsim.cpp, aovsim.cpp, querysim.cpp, radiancesim.cpp, pointsim.cpp, refitsim.cpp)
+        # the built scene: a handle, and what traces on it (hostsim.cpp, aovsim.cpp, querysim.cpp, radiancesim.cpp, pointsim.cpp, signsim.cpp,
+        # refitsim.cpp)
         sig("hostsim_create", [C.POINTER(HostsimScene), C.c_int, C.c_int], vp)
         sig("hostsim_free", [vp], None)
         sig("hostsim_read_bvh", [vp, C.POINTER(HostsimBvhOut)])
@@ -76,6 +82,13 @@ def hostsim_lib():
         sig("pointsim_query", [vp, C.c_int, f32p, C.c_int64, C.c_int, vp])
         sig("pointsim_brute", [vp, f32p, C.c_int64, C.c_int, vp])
         sig("pointsim_stack_depth", [vp, C.c_int, f32p, C.c_int64])
+        sig("signsim_create", [vp], vp)      # the sign state of a handle; the other signsim entries take it, not the handle
+        sig("signsim_free", [vp], None)
+        sig("signsim_info_read", [vp, C.POINTER(SignsimInfo)])
+        sig("signsim_table", [vp, vp, vp])
+        sig("signsim_query", [vp, C.c_int, f32p, C.c_int64, vp])
+        sig("signsim_brute", [vp, f32p, C.c_int64, vp])
+        sig("signsim_atan2", [f32p, f32p, f32p, C.c_int], None)
         sig("refitsim_update", [vp, C.c_int32, C.c_int32, f32p, f32p])
         sig("refitsim_refit", [vp])
         sig("refitsim_read", [vp, C.POINTER(RefitsimOut)])

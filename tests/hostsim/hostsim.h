@@ -8,6 +8,7 @@
 #include "../../minimaloptix_amd/csrc/pt_lbvh.h"
 #include "../../minimaloptix_amd/csrc/pt_refit.h"
 #include "../../minimaloptix_amd/csrc/pt_upload.h"
+#include "../../minimaloptix_amd/csrc/pt_sign.h"
 
 extern "C" {
 
@@ -79,6 +80,11 @@ struct LocalPointStack {
   inline void store(int sp, int r, float d) { ref[sp] = r; d2[sp] = d; }
   inline void load(int sp, int& r, float& d) const { r = ref[sp]; d = d2[sp]; }
 };
+
+// pointsim.cpp, for signsim.cpp too: point i of a query by the traversal, and by the loop over every primitive record.  mode: POINT_CLOSEST,
+// POINT_ANY (out: int32 per point) or POINT_SIGNED with the sign table (null otherwise; out: a PointHit per point)
+void point_query_one(const SceneView& sc, int mode, bool n64, const SignRecord* table, const float* p, void* out, size_t i);
+void point_brute_one(const SceneView& sc, int mode, const SignRecord* table, const float* p, void* out, size_t i);
 
 // nodeFormat 64 walks the 64-byte nodes where the tree has them (as the packet kernel does by default), 128 the 128-byte ones
 inline bool walks_node64(const SceneView& sc, int nodeFormat) { return nodeFormat == 64 && sc.nodes64 != nullptr; }

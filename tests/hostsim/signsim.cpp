@@ -1,7 +1,8 @@
 // signsim.cpp -- TEST INFRASTRUCTURE.  The CPU mirror of the signed point queries (minimaloptix_amd/csrc/signkernel.hip, api_sign.hip): the
 // topology of the handle's faces (pt_signtopo.h, the function the library runs), the table of pseudonormals computed by the same per-face,
-// per-vertex and per-edge code (pt_sign.h) one element at a time, the signed traversal and the signed loop over every primitive, on the
-// scene and tree of a hostsim_create handle (hostsim.h), through a sign state made on that handle (signsim_create).  The GPU tests compare the device's table and output with these bit for bit.
+// per-vertex and per-edge code (pt_sign.h) one element at a time, and with that table the signed mode of pointsim.cpp's traversal and of
+// its loop over every primitive, on the scene and tree of a hostsim_create handle (hostsim.h), through a sign state made on that handle
+// (signsim_create).  The GPU tests compare the device's table and output with these bit for bit.
 // It is not part of the product: nothing under minimaloptix_amd/ builds or loads it.
 #include <cstring>
 #include "hostsim.h"
@@ -34,41 +35,6 @@ SignSim& refreshed(void* h) {
   s.table.resize((size_t)t.nFaces);
   for (int f = 0; f < t.nFaces; f++) s.table[f] = sign_record(&t.faceIds[6 * (size_t)f], faces[f], vertexN.data(), edgeN.data());
   return s;
-}
-
-template <bool N64>
-void query_one(const SceneView& sc, const SignRecord* table, const float* p, PointHit& out) {
-  LocalPointStack st;
-  PointTrav tv;
-  const v3 q = mk3(p[0], p[1], p[2]);
-  point_begin<false>(sc, q, p[3] * p[3], point_valid(p), tv);
-  while (tv.node != kTravDone) point_step<false, N64>(sc, q, tv, st);
-  point_hit_signed(sc, table, q, p[3], tv, out);
-}
-
-// No tree: every record through the per-primitive functions and the (d2, prim) rule (pointsim.cpp brute_one), then the signed record.
-void brute_one(const SceneView& sc, const SignRecord* table, const float* p, PointHit& out) {
-  PointTrav tv;
-  tv.bestD2 = p[3] * p[3]; tv.bestPrim = -1; tv.bestTri = -1; tv.sp = 0; tv.node = kTravDone;
-  const v3 q = mk3(p[0], p[1], p[2]);
-  if (point_valid(p)) {
-    PointCand k;
-    for (int s = 0; s < sc.nSpheres; s++) {
-      point_sphere(q, sc.spheres[s].center, sc.spheres[s].radius, k);
-      if (point_accept(k.d2, s, tv.bestD2, tv.bestPrim)) { tv.bestPrim = s; tv.bestD2 = k.d2; }
-    }
-    for (int g = 0; g < sc.nQuads; g++) {
-      point_quad(q, sc.quads[g].v1, sc.quads[g].v2, sc.quads[g].anchor, k);
-      if (point_accept(k.d2, sc.nSpheres + g, tv.bestD2, tv.bestPrim)) { tv.bestPrim = sc.nSpheres + g; tv.bestD2 = k.d2; }
-    }
-    for (int t = 0; t < sc.nTris; t++) {
-      const Tri48& r = sc.tris[t];
-      point_tri(q, r.p0, r.e0, r.e1, k);
-      const int prim = sc.nSpheres + sc.nQuads + r.prim;
-      if (point_accept(k.d2, prim, tv.bestD2, tv.bestPrim)) { tv.bestPrim = prim; tv.bestTri = t; tv.bestD2 = k.d2; }
-    }
-  }
-  point_hit_signed(sc, table, q, p[3], tv, out);
 }
 
 }  // namespace
@@ -119,10 +85,7 @@ int signsim_query(void* h, int nodeFormat, const float* points, int64_t n, void*
   const SceneView& sc = s.sim->hs.view;
   const bool n64 = walks_node64(sc, nodeFormat);
 #pragma omp parallel for schedule(dynamic, 64)
-  for (int64_t i = 0; i < n; i++) {
-    PointHit& o = static_cast<PointHit*>(out)[i];
-    if (n64) query_one<true>(sc, table, points + 4 * (size_t)i, o); else query_one<false>(sc, table, points + 4 * (size_t)i, o);
-  }
+  for (int64_t i = 0; i < n; i++) point_query_one(sc, POINT_SIGNED, n64, table, points + 4 * (size_t)i, out, (size_t)i);
   return 0;
 }
 
@@ -133,7 +96,7 @@ int signsim_brute(void* h, const float* points, int64_t n, void* out) {
   const SignRecord* table = s.table.data();
   const SceneView& sc = s.sim->hs.view;
 #pragma omp parallel for schedule(dynamic, 16)
-  for (int64_t i = 0; i < n; i++) brute_one(sc, table, points + 4 * (size_t)i, static_cast<PointHit*>(out)[i]);
+  for (int64_t i = 0; i < n; i++) point_brute_one(sc, POINT_SIGNED, table, points + 4 * (size_t)i, out, (size_t)i);
   return 0;
 }
 

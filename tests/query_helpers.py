@@ -3,7 +3,7 @@ import numpy as np
 
 from common import M, _f32, _ptr, hostsim_handle, hostsim_lib
 
-HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("ng", np.float32, (3,))])
+HIT_DTYPE = M.HIT_DTYPE
 
 
 def querysim(hs, rays, mode="closest", node_format=64, leaf_size=4):

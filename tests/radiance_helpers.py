@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from common import K, _f32, _hostsim_scene, _ptr, hostsim_handle, hostsim_lib
+from query_helpers import same_bits      # noqa: F401  (for the tests)
 
 CLAMP = K.RADIANCE_CLAMP
 
@@ -74,8 +75,3 @@ def camera_sum(query, hs, seeds):
         rays, states = camera_rays_states(hs, seed)
         acc = (acc + np.asarray(query(rays, states))[:, :3]).astype(np.float32)
     return acc.reshape(hs.height, hs.width, 3)
-
-
-def same_bits(a, b):
-    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()

@@ -4,47 +4,23 @@ import ctypes as C
 
 import numpy as np
 
-from common import M, HostsimHandle, MovedScene, _f32, _ptr, hostsim_lib
+from common import M, HostsimHandle, MovedScene, SignsimInfo, _f32, _ptr, hostsim_lib
 from point_helpers import INF, POINT_DTYPE, with_max      # noqa: F401  (for the tests)
 from query_helpers import same_bits                        # noqa: F401
 
-INFO_FIELDS = ("weldedVerts", "edges", "boundaryEdges", "nonManifoldEdges", "flippedEdges", "degenerateFaces", "closed", "tableBuilds")
-
-
-class SignsimInfo(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in INFO_FIELDS] + [("signedVolume", C.c_double)]
-
-
-_bound = False
-
-
-def _lib():
-    """common.hostsim_lib() with the signatures of signsim.cpp set on it."""
-    global _bound
-    L = hostsim_lib()
-    if not _bound:
-        vp, f32p = C.c_void_p, C.POINTER(C.c_float)
-        L.signsim_create.argtypes, L.signsim_create.restype = [vp], vp
-        L.signsim_free.argtypes, L.signsim_free.restype = [vp], None
-        L.signsim_info_read.argtypes, L.signsim_info_read.restype = [vp, C.POINTER(SignsimInfo)], C.c_int
-        L.signsim_table.argtypes, L.signsim_table.restype = [vp, vp, vp], C.c_int
-        L.signsim_query.argtypes, L.signsim_query.restype = [vp, C.c_int, f32p, C.c_int64, vp], C.c_int
-        L.signsim_brute.argtypes, L.signsim_brute.restype = [vp, f32p, C.c_int64, vp], C.c_int
-        L.signsim_atan2.argtypes, L.signsim_atan2.restype = [f32p, f32p, f32p, C.c_int], None
-        _bound = True
-    return L
+INFO_FIELDS = tuple(n for n, _ in SignsimInfo._fields_[:-1])      # the counters; signedVolume is the last field
 
 
 class _SignState:
     """signsim_create on a built scene: the topology of its faces as they are at this moment."""
 
     def __init__(self, sim):
-        self._s = C.c_void_p(_lib().signsim_create(sim._h))
+        self._s = C.c_void_p(hostsim_lib().signsim_create(sim._h))
         assert self._s
 
     def __del__(self):
         if getattr(self, "_s", None):
-            _lib().signsim_free(self._s)
+            hostsim_lib().signsim_free(self._s)
             self._s = None
 
 
@@ -59,14 +35,14 @@ def _state(sim):
 def atan2_ac(y, x):
     y, x = _f32(y), _f32(x)
     out = np.zeros(len(y), np.float32)
-    _lib().signsim_atan2(_ptr(y), _ptr(x), _ptr(out), len(y))
+    hostsim_lib().signsim_atan2(_ptr(y), _ptr(x), _ptr(out), len(y))
     return out
 
 
 def sign_info(sim):
     """moptix_get_sign_info of the mirror: a dict."""
     r = SignsimInfo()
-    assert _lib().signsim_info_read(_state(sim), C.byref(r)) == 0
+    assert hostsim_lib().signsim_info_read(_state(sim), C.byref(r)) == 0
     d = {n: int(getattr(r, n)) for n in INFO_FIELDS}
     d["signedVolume"] = float(r.signedVolume)
     return d
@@ -75,7 +51,7 @@ def sign_info(sim):
 def sign_table(sim):
     """The mirror's table for the handle's faces as they are now: (nFaces, 24) float32."""
     out = np.zeros((max(1, sim.n_faces), 24), np.float32)
-    assert _lib().signsim_table(_state(sim), out.ctypes.data, None) == 0
+    assert hostsim_lib().signsim_table(_state(sim), out.ctypes.data, None) == 0
     return out[:sim.n_faces]
 
 
@@ -86,14 +62,14 @@ def _points(points):
 def signsim(sim, points, node_format=64):
     pts = _points(points)
     out = np.zeros(len(pts), POINT_DTYPE)
-    assert _lib().signsim_query(_state(sim), int(node_format), _ptr(pts), len(pts), out.ctypes.data) == 0
+    assert hostsim_lib().signsim_query(_state(sim), int(node_format), _ptr(pts), len(pts), out.ctypes.data) == 0
     return out
 
 
 def signbrute(sim, points):
     pts = _points(points)
     out = np.zeros(len(pts), POINT_DTYPE)
-    assert _lib().signsim_brute(_state(sim), _ptr(pts), len(pts), out.ctypes.data) == 0
+    assert hostsim_lib().signsim_brute(_state(sim), _ptr(pts), len(pts), out.ctypes.data) == 0
     return out
 
 

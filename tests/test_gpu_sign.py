@@ -1,4 +1,4 @@
-"""Signed point queries on the MI355X (signkernel.hip): the device's table of pseudonormals and the signed records are bit for bit the
+"""Signed point queries on the MI355X (signkernel.hip, pointkernel.hip): the device's table of pseudonormals and the signed records are bit for bit the
 CPU mirror's (tests/hostsim/signsim.cpp), whatever the node format, the entry point and the grid; the table follows a refit; and the
 closest and any modes are not disturbed."""
 import ctypes as C

@@ -5,9 +5,11 @@ import numpy as np
 import pytest
 
 from common import M, oracle_scene
-from query_helpers import HIT_DTYPE, SCENES, coffee_rays, invalid_rays, querysim, same_bits, scene_and_rays, shortened
+from query_helpers import SCENES, coffee_rays, invalid_rays, querysim, same_bits, scene_and_rays, shortened
 
 K = M._capi
+# moptix_hit spelled out here, apart from the package's definition, which the helpers and the other tests use
+HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("ng", np.float32, (3,))])
 
 
 @pytest.fixture(scope="module", params=SCENES, ids=[s[0].replace("file:", "") for s in SCENES])

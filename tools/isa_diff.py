@@ -1,6 +1,6 @@
 """Are the gfx950 kernels of two device libraries the same, instruction for instruction?
 
-    python3 tools/isa_diff.py OLD.so NEW.so
+    python3 tools/isa_diff.py OLD.so NEW.so [--rename OLDSYMBOL=NEWSYMBOL]...
 
 For a change that must not touch the device code (a host-side refactor, a rename): build the library before and after with the same
 `make device` and compare.  Every gfx950 code object of each library (tools/kernel_resources.py code_objects) is disassembled with
@@ -10,6 +10,8 @@ the pc-relative literal behind an s_getpc_b64 (the address of a function or tabl
 points at, and the padding behind a kernel is ignored.  Beside the text,
 each kernel's entry in the AMDGPU metadata note is compared whole (registers, spills, LDS, scratch, kernel arguments, workgroup size).
 A symbol that several code objects carry (a template two files instantiate) is compared as the sorted list of its copies.
+--rename (repeatable): the kernel OLDSYMBOL of OLD.so is compared with NEWSYMBOL of NEW.so, without the `.name:` and `.symbol:` lines
+of the metadata, which hold the symbol itself.
 
 Prints the symbols that only one library has and the ones whose text or metadata differs, then one summary line; exit status 1 if
 there was any difference."""
@@ -63,8 +65,12 @@ def kernels(lib_path):
     return {s: sorted(v) for s, v in out.items()}
 
 
-def main(old_path, new_path):
+def main(old_path, new_path, renames=()):
     old, new = kernels(old_path), kernels(new_path)
+    for o, n in renames:
+        if o in old and n in new and n not in old:
+            nameless = lambda v, s: sorted((t, re.sub(r"^\s*\.(name|symbol):\s+%s(\.kd)?\n" % re.escape(s), "", m, flags=re.M)) for t, m in v)
+            old[n], new[n] = nameless(old.pop(o), o), nameless(new[n], n)
     bad = 0
     for s in sorted(set(old) - set(new)):
         print("only in %s: %s" % (old_path, s)); bad += 1
@@ -86,6 +92,12 @@ def main(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    renames = []
+    while "--rename" in args[:-1]:
+        i = args.index("--rename")
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    if len(args) != 2 or any(len(r) != 2 for r in renames):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], renames))

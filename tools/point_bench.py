@@ -9,7 +9,7 @@ Timed with HIP events on the context's stream (a torch stream handed to moptix_s
 of --reps runs of moptix_query_points_device in closest and in any mode ("any" with maxDist = 1 % of the diagonal: with no limit it ends at
 the first primitive of the first leaf).  Then moptix_query_rays_device, closest, on as many incoherent rays (tools/query_bench.py's set).
 --sweep adds the grid's cap ("query_blocks_per_cu") and the 128-byte nodes.  Prints the table that profiles/r16_point.txt keeps.
---signed adds the signed mode (csrc/signkernel.hip) on the same two point sets beside the closest mode, with their ratio, and the rebuild of
+--signed adds the signed mode (its table: csrc/signkernel.hip) on the same two point sets beside the closest mode, with their ratio, and the rebuild of
 the sign table after a refit: a signed query of 256 points with the table stale (moptix_update_faces + moptix_refit_accel before each run)
 against the same query with the table current, beside the refit's own refitMs (profiles/r17_sign.txt)."""
 import argparse
@@ -116,7 +116,7 @@ def main():
         print("# sign_info: %s" % ctx.sign_info())
         for name in ("uniform", "near"):
             closest = line("pt_pointquery closest, %s, no limit" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_CLOSEST, recs))
-            signed = line("pt_pointsigned, %s, no limit" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_SIGNED, recs))
+            signed = line("pt_pointquery signed, %s, no limit" % name, n, timed(L.moptix_query_points_device, sets[name], K.POINT_SIGNED, recs))
             print("#   signed / closest %.3f; inside: %d of %d" % (signed / closest, int((recs[:, 0] < 0).sum()), n))
         fp = hs.face_arrays()[0]
         ext = float((hs.aabb_max - hs.aabb_min).max())
