@@ -571,6 +571,43 @@ enum { MOPTIX_QUERY_CLOSEST = 0, MOPTIX_QUERY_ANY = 1 };
 int moptix_query_rays_device(moptix_context ctx, const float* dRays, int64_t n, int32_t mode, void* dOut);
 int moptix_query_rays(moptix_context ctx, const float* rays, int64_t n, int32_t mode, void* out);
 
+/* ---- multi-hit ray queries: the first maxHits hits along each ray, in order ---------------------------------------------------------
+ * Everything a ray passes through: the thickness of a wall, the entry / exit intervals of a solid, the layers behind a surface, a crossing
+ * count as an inside test for meshes that are not closed -- in one walk, and right at exactly equal t, where re-launching closest
+ * queries with an advanced tmin skips the second of two coincident surfaces.
+ * A ray is the ray queries' eight floats, valid or invalid by their rule; a negative tmin is walked as 0.
+ * The hit set H of a valid ray is the set of pairs (t, prim) over every primitive record whose own test accepts it with tmin < t < tmax:
+ * a triangle or a quad gives at most one pair; a sphere one per root inside the interval, so a sphere entered and left gives two pairs
+ * with the same prim and a tangent ray (both roots equal) one.  Every primitive counts, whatever its material.  An invalid ray has
+ * H = {}.  H is a function of the ray and the device records alone.
+ *   hits    n x maxHits moptix_hit records, ray-major.  For ray i the first c = min(maxHits, |H|) records are the c least elements of H by
+ *           (t, prim) ascending (rule D5's order), each filled exactly as MOPTIX_QUERY_CLOSEST fills a closest hit at that (t, prim):
+ *           mat, u, v and ng before any face-forward flip -- a sphere's exit hit has the outward normal, which points along the ray.
+ *           Records c .. maxHits - 1 are miss records (t = the given tmax, prim = mat = -1, the rest 0).  Every byte is defined.  Record
+ *           0 has the bits of MOPTIX_QUERY_CLOSEST on the same ray.
+ *   counts  n x int32: c.  With MOPTIX_MULTI_COUNT_ALL: |H|, the number of crossings -- the walk then cannot prune and visits every box
+ *           the ray meets inside (tmin, tmax), which costs well above a closest query.  counts[i] > 0 if and only if MOPTIX_QUERY_ANY
+ *           gives 1 on the same ray.
+ *   maxHits 1..64.  With MOPTIX_MULTI_COUNT_ALL also 0, and hits may then be NULL: the pure crossing count.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part, with the one exception the closest query
+ * has: a grazing hit that the triangle test accepts outside the triangle's own padded box is not seen by a walk that never enters that
+ * box.  Here that holds for every triangle along the ray, not only for the nearest.
+ *   moptix_query_rays_multi_device  dRays, dHits: device memory, 16-byte aligned; dCounts: device memory, 4-byte aligned.  Asynchronous on
+ *                                   the context's stream.  While a ray is walked its slice of dHits holds the candidates; nothing else
+ *                                   is allocated or written.  It uses the ray queries' stack overflow area (same grid cap, allocated at
+ *                                   the first ray query of either kind on a tree): moptix_debug_buffer_addresses out[0] keeps its value
+ *                                   across a multi-hit query.
+ *   moptix_query_rays_multi         host pointers, blocking: upload, query, read back (the ray queries' staging)
+ * n may be any int64 >= 0: longer batches are cut into launches of floor(2^30 / max(maxHits, 1)) rays, so that a launch writes at most
+ * 2^30 records and a record's index within it fits an int as a ray's does; n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or misaligned
+ * pointers, n < 0, maxHits out of range, unknown flag bits; state errors as moptix_query_rays ("faces dirty" before a refit included).
+ * A multi-hit query changes nothing else in the context. */
+enum { MOPTIX_MULTI_COUNT_ALL = 1 };
+int moptix_query_rays_multi_device(moptix_context ctx, const float* dRays, int64_t n, int32_t maxHits, uint32_t flags,
+                                   void* dHits, int32_t* dCounts);
+int moptix_query_rays_multi(moptix_context ctx, const float* rays, int64_t n, int32_t maxHits, uint32_t flags,
+                            moptix_hit* hits, int32_t* counts);
+
 /* ---- radiance queries: path-traced radiance for the caller's own rays -------------------------------------------------------------
  * How much light arrives along a ray, from the materials, lights, next-event estimation and shadow rule the frame uses: a probe, a
  * lightmap texel, another sensor model.  The camera and the frame size play no part; "fast_shading" is not consulted.

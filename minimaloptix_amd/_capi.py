@@ -161,6 +161,8 @@ class Hit(C.Structure):
 
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+MULTI_COUNT_ALL = 1
+MULTI_MAX_HITS = 64
 
 
 class PointHit(C.Structure):
@@ -208,7 +210,8 @@ DEVICE_SYMBOLS = [
     "moptix_temporal_face_info",
     "moptix_adaptive_defaults", "moptix_render_adaptive", "moptix_adaptive_clear", "moptix_adaptive_read", "moptix_adaptive_mean",
     "moptix_adaptive_mean_device", "moptix_adaptive_resolve_rgb8",
-    "moptix_query_rays_device", "moptix_query_rays", "moptix_query_radiance_device", "moptix_query_radiance",
+    "moptix_query_rays_device", "moptix_query_rays", "moptix_query_rays_multi_device", "moptix_query_rays_multi",
+    "moptix_query_radiance_device", "moptix_query_radiance",
     "moptix_query_points_device", "moptix_query_points", "moptix_query_points_signed", "moptix_get_sign_info", "moptix_debug_read_sign_table",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
@@ -305,6 +308,8 @@ def device_lib():
         L.moptix_adaptive_resolve_rgb8.argtypes = [vp, u8p]
         L.moptix_query_rays_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_rays.argtypes = [vp, f32p, C.c_int64, i32, vp]
+        L.moptix_query_rays_multi_device.argtypes = [vp, vp, C.c_int64, i32, C.c_uint32, vp, vp]
+        L.moptix_query_rays_multi.argtypes = [vp, f32p, C.c_int64, i32, C.c_uint32, vp, i32p]
         u32p = C.POINTER(C.c_uint32)
         L.moptix_query_radiance_device.argtypes = [vp, vp, C.c_int64, i32p, vp, i32, C.c_uint32, C.c_uint32, vp]
         L.moptix_query_radiance.argtypes = [vp, f32p, C.c_int64, i32p, u32p, i32, C.c_uint32, C.c_uint32, f32p]

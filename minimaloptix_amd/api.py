@@ -55,11 +55,11 @@ def _rows(k):
 
 
 def _record_views(out, first, last):
-    """The (n, 8) float32 tensor of moptix_hit / moptix_point_hit records as a dict of views: "records" itself, word 0 under the name
-    `first`, prim, mat, u, v, and words 5 .. 7 under the name `last`."""
+    """The (n, 8) -- or, for a multi-hit query, (n, k, 8) -- float32 tensor of moptix_hit / moptix_point_hit records as a dict of views:
+    "records" itself, word 0 under the name `first`, prim, mat, u, v, and words 5 .. 7 under the name `last`."""
     import torch
     ints = out.view(torch.int32)
-    return {"records": out, first: out[:, 0], "prim": ints[:, 1], "mat": ints[:, 2], "u": out[:, 3], "v": out[:, 4], last: out[:, 5:8]}
+    return {"records": out, first: out[..., 0], "prim": ints[..., 1], "mat": ints[..., 2], "u": out[..., 3], "v": out[..., 4], last: out[..., 5:8]}
 
 
 def _f3(v):
@@ -572,6 +572,37 @@ class Context:
         if m == K.QUERY_ANY:
             return out
         return _record_views(out, "t", "ng")
+
+    def query_rays_multi(self, rays, max_hits=4, count_all=False):
+        """The first max_hits hits along each of the caller's rays, n x 8 floats o, d, tmin, tmax, in order of (t, prim); blocking.  Returns
+        (hits, counts): per ray max_hits records, the hits first and miss records behind them, and how many are hits -- with count_all
+        the number of all hits along the ray instead, however many were kept (the walk then cannot prune); max_hits 1..64, with
+        count_all also 0: the pure crossing count.
+        A numpy array takes the host path: hits is an (n, max_hits) HIT_DTYPE array, counts an int32 array.
+        A contiguous (n, 8) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
+        hits the dict of views t, prim, mat, u, v, ng of query_rays into "records", here the (n, max_hits, 8) float32 tensor of the raw
+        moptix_hit records, and counts an int32 tensor."""
+        k = int(max_hits)
+        flags = K.MULTI_COUNT_ALL if count_all else 0
+        if k < (0 if count_all else 1) or k > K.MULTI_MAX_HITS:
+            raise ValueError("query_rays_multi: max_hits %r (1..%d; 0 only with count_all)" % (max_hits, K.MULTI_MAX_HITS))
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):
+            rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 8))
+            hits = np.zeros((len(rays), k), HIT_DTYPE)
+            counts = np.zeros(len(rays), np.int32)
+            self._chk(self._L.moptix_query_rays_multi(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), k, flags,
+                                                      C.c_void_p(hits.ctypes.data) if k else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
+            return hits, counts
+        import torch
+        _check_tensor("query_rays_multi", "rays", rays, ("torch.float32",), _rows(8), "shape (n, 8)", self.device)
+        n = rays.shape[0]
+        out = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
+        counts = torch.empty(n, dtype=torch.int32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()      # the rays are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_rays_multi_device(self._h, C.c_void_p(rays.data_ptr()), n, k, flags,
+                                                         C.c_void_p(out.data_ptr()) if k else None, C.c_void_p(counts.data_ptr())))
+        self.sync()
+        return _record_views(out, "t", "ng"), counts
 
     def query_radiance(self, rays, seeds=None, states=None, clamp=False, index_base=0):
         """Path-traced radiance along the caller's rays, n x 8 floats o, d, tmin, tmax with UNIT directions; blocking.  Returns (n, 4)

@@ -217,7 +217,8 @@ struct moptix_context_t {
   } ad;
 
   // ---- ray queries (api_query.hip): the stack overflow area of the query kernel, allocated at the first query after a build and
-  // dropped with the tree it was sized for (moptix_clear_scene, moptix_build_accel); the staging of the host-pointer entry point ----
+  // dropped with the tree it was sized for (moptix_clear_scene, moptix_build_accel); the staging of the host-pointer entry point.  The
+  // multi-hit queries use all three as they are (out: the records, the counts behind them) ----
   struct Query {
     DevBuf<int> overflow;
     DevBuf<float> rays; DevBuf<uint8_t> out;

@@ -1,7 +1,9 @@
-// api_query.hip -- batched ray queries (querykernel.hip, pt_query.h): the two moptix_query_rays* entry points of include/moptix.h.
+// api_query.hip -- batched ray queries (querykernel.hip, pt_query.h, pt_multihit.h): the moptix_query_rays* and moptix_query_rays_multi*
+// entry points of include/moptix.h.
 #include <cstring>
 
 #include "api_context.h"
+#include "pt_multihit.h"
 #include "pt_query.h"
 #include "querykernel.h"
 
@@ -10,6 +12,7 @@ using namespace pt::api;
 
 static_assert(sizeof(moptix_hit) == sizeof(QueryHit), "moptix_hit is the kernel's record");
 static_assert(MOPTIX_QUERY_CLOSEST == QUERY_CLOSEST && MOPTIX_QUERY_ANY == QUERY_ANY, "query modes");
+static_assert(MOPTIX_MULTI_COUNT_ALL == MULTI_COUNT_ALL, "multi-hit flags");
 
 namespace {
 
@@ -43,6 +46,39 @@ int enqueue_query(moptix_context c, const float* dRays, int64_t n, int32_t mode,
   return MOPTIX_OK;
 }
 
+int check_multi(moptix_context c, const float* rays, int64_t n, int32_t maxHits, uint32_t flags, const void* hits, const int32_t* counts) {
+  const int rc = check_ready(c);
+  if (rc != MOPTIX_OK) return rc;
+  if (n < 0 || (flags & ~(uint32_t)MOPTIX_MULTI_COUNT_ALL) != 0) return fail(c, MOPTIX_ERR_INVALID, "bad ray count or unknown multi-hit flag");
+  const int lowest = (flags & MOPTIX_MULTI_COUNT_ALL) ? 0 : 1;
+  if (maxHits < lowest || maxHits > kMultiMaxHits) return fail(c, MOPTIX_ERR_INVALID, "maxHits out of range (1..64; 0 only with MOPTIX_MULTI_COUNT_ALL)");
+  if (n > 0 && (!rays || !counts || (maxHits > 0 && !hits))) return fail(c, MOPTIX_ERR_INVALID, "null argument");
+  return MOPTIX_OK;
+}
+
+// As enqueue_query, with the ray queries' overflow area.  A launch takes at most kQueryMaxLaunch / max(maxHits, 1) rays, so that the
+// index of a record within a launch fits 32 bits as the index of a ray does.
+int enqueue_multi(moptix_context c, const float* dRays, int64_t n, int32_t maxHits, uint32_t flags, void* dHits, int32_t* dCounts) {
+  MultiArgs a;
+  memset(&a, 0, sizeof(a));
+  const int nBlocks = fill_query_view(c, a.scene);
+  const size_t ovf = a.scene.rootRef != kEmptyRef ? querykernel_overflow_ints(nBlocks, c->bvh.stackBound) : 0;
+  if (ovf > 0) {
+    HIPCHK(c, c->query.overflow.ensure(ovf), "alloc query stack overflow area");
+    a.stackOverflow = c->query.overflow.p;
+  }
+  a.maxHits = maxHits;
+  const int64_t perLaunch = kQueryMaxLaunch / (maxHits > 0 ? maxHits : 1);
+  for (int64_t first = 0; first < n; first += perLaunch) {
+    a.rays = dRays + 8 * first;
+    a.hits = maxHits > 0 ? static_cast<char*>(dHits) + sizeof(moptix_hit) * (size_t)maxHits * (size_t)first : nullptr;
+    a.counts = dCounts + first;
+    a.n = (int)(n - first < perLaunch ? n - first : perLaunch);
+    HIPCHK(c, launch_rayquery_multi(c->stream, a, nBlocks, (flags & MOPTIX_MULTI_COUNT_ALL) != 0), "launch multi-hit ray query");
+  }
+  return MOPTIX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -66,6 +102,28 @@ int moptix_query_rays(moptix_context c, const float* rays, int64_t n, int32_t mo
   HIPCHK(c, hipMemcpyAsync(c->query.rays.p, rays, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, c->stream), "upload query rays");
   if ((rc = enqueue_query(c, c->query.rays.p, n, mode, c->query.out.p)) != MOPTIX_OK) return rc;
   return read_back(c, { { out, c->query.out.p, bytes } }, "read query results");
+}
+
+int moptix_query_rays_multi_device(moptix_context c, const float* dRays, int64_t n, int32_t maxHits, uint32_t flags, void* dHits, int32_t* dCounts) {
+  int rc = check_multi(c, dRays, n, maxHits, flags, dHits, dCounts);
+  if (rc != MOPTIX_OK || n == 0) return rc;
+  if ((reinterpret_cast<uintptr_t>(dRays) & 15u) != 0 || (reinterpret_cast<uintptr_t>(dHits) & 15u) != 0 || (reinterpret_cast<uintptr_t>(dCounts) & 3u) != 0)
+    return fail(c, MOPTIX_ERR_INVALID, "multi-hit queries read rays and write hit records 16 bytes at a time, counts 4: misaligned device pointer");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  return enqueue_multi(c, dRays, n, maxHits, flags, dHits, dCounts);
+}
+
+int moptix_query_rays_multi(moptix_context c, const float* rays, int64_t n, int32_t maxHits, uint32_t flags, moptix_hit* hits, int32_t* counts) {
+  int rc = check_multi(c, rays, n, maxHits, flags, hits, counts);
+  if (rc != MOPTIX_OK || n == 0) return rc;
+  if ((rc = begin_call(c, false)) != MOPTIX_OK) return rc;
+  const size_t hitBytes = sizeof(moptix_hit) * (size_t)maxHits * (size_t)n, countBytes = sizeof(int32_t) * (size_t)n;      // counts behind the records
+  HIPCHK(c, c->query.rays.ensure(8 * (size_t)n), "alloc query rays");
+  HIPCHK(c, c->query.out.ensure(hitBytes + countBytes), "alloc query results");
+  HIPCHK(c, hipMemcpyAsync(c->query.rays.p, rays, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, c->stream), "upload query rays");
+  int32_t* dCounts = reinterpret_cast<int32_t*>(c->query.out.p + hitBytes);
+  if ((rc = enqueue_multi(c, c->query.rays.p, n, maxHits, flags, c->query.out.p, dCounts)) != MOPTIX_OK) return rc;
+  return read_back(c, { { maxHits > 0 ? hits : nullptr, c->query.out.p, hitBytes }, { counts, dCounts, countBytes } }, "read multi-hit results");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "pt_lanestack.h"
+#include "pt_multihit.h"
 #include "pt_query.h"
 #include "querykernel.h"
 
@@ -55,6 +56,33 @@ __global__ void __launch_bounds__(kBlockThreads) pt_rayquery(const QueryArgs a) 
   }
 }
 
+// Multi-hit (pt_multihit.h): the same grid, loop and stack.  The K candidates of a ray live in its own slice of the output while it walks
+// (16-byte keys, turned into records in place at the end), so K costs no registers and no LDS: the lane holds the count and the K-th key.
+template <bool N64, bool ALL>
+__global__ void __launch_bounds__(kBlockThreads) pt_rayquery_multi(const MultiArgs a) {
+  __shared__ int ldsStack[kWavesPerBlock * kLdsStack * 64];
+  const SceneView& sc = a.scene;
+  const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
+  LaneStack<kLdsStack> st;
+  st.init(ldsStack, a.stackOverflow, gthread, stride);
+  const uint4* __restrict__ rays = reinterpret_cast<const uint4*>(a.rays);
+  Counters ct;                      // not counted: never written
+  for (int i = gthread; i < a.n; i += stride) {           // n x max(maxHits, 1) <= kQueryMaxLaunch: the record index fits 32 bits too
+    const uint4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+    const float r[8] = { i2f((int32_t)r0.x), i2f((int32_t)r0.y), i2f((int32_t)r0.z), i2f((int32_t)r0.w),
+                         i2f((int32_t)r1.x), i2f((int32_t)r1.y), i2f((int32_t)r1.z), i2f((int32_t)r1.w) };
+    PathState ps;
+    Trav tv;
+    HitList hl;
+    const bool valid = query_ray(r, ps);
+    hl.init(static_cast<Word4*>(a.hits) + 2 * (size_t)i * (size_t)a.maxHits, a.maxHits);      // maxHits 0: never dereferenced
+    multi_begin<ALL>(sc, ps, valid, tv, hl);
+    while (tv.node != kTravDone) multi_step<ALL, N64>(sc, ps, tv, st, hl, ct);
+    multi_finish(sc, ps, hl);
+    a.counts[i] = ALL ? hl.total : hl.count;
+  }
+}
+
 }  // namespace
 
 int querykernel_blocks(int nCUs, int blocksPerCU) { return (nCUs > 0 ? nCUs : 256) * blocksPerCU; }
@@ -69,6 +97,19 @@ hipError_t launch_rayquery(hipStream_t stream, const QueryArgs& a, int nBlocks, 
   } else {
     if (n64) pt_rayquery<false, true><<<blocks, kBlockThreads, 0, stream>>>(a);
     else     pt_rayquery<false, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_rayquery_multi(hipStream_t stream, const MultiArgs& a, int nBlocks, bool countAll) {
+  const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);
+  const bool n64 = a.scene.nodes64 != nullptr;
+  if (countAll) {
+    if (n64) pt_rayquery_multi<true, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_rayquery_multi<false, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+  } else {
+    if (n64) pt_rayquery_multi<true, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_rayquery_multi<false, false><<<blocks, kBlockThreads, 0, stream>>>(a);
   }
   return hipGetLastError();
 }
