@@ -281,7 +281,11 @@ int moptix_unpack_tiles(moptix_context ctx, int32_t rank, int32_t nRanks, const 
  *                      of a counted launch then vary a little from run to run (the frontier's visiting order follows its atomics).  The one
  *                      documented exception to order independence -- a grazing hit outside its triangle's own box, below -- can in principle
  *                      make a drained path's result depend on that order; no such case in 3,300 fuzz cases with the drain kernel on
- * read-only (get_option): "kernel_variant_used", "node_format_used", "path_slots", "num_cus", "comm_ranks" (size of the context's
+ *   "specialize"       variant 4: 1 (default) = a scene whose tables hold no textured material, no sphere light, no Lambertian / metal /
+ *                      glass material and no analytic sphere is traced by a build of the trace kernel without those programs; 0 = always
+ *                      the general build.  Decided at every launch from the tables as they are then; same image bits either way
+ * read-only (get_option): "kernel_variant_used", "kernel_features_used" (the programs compiled into the last launch's trace kernel:
+ *   1 textures | 2 sphere lights | 4 Lambertian / metal / glass | 8 analytic spheres; 15 = the general build, 0 = the lean one), "node_format_used", "path_slots", "num_cus", "comm_ranks" (size of the context's
  *   communicator, 0 without one), "comm_nonblocking_used" (1: that communicator is non-blocking), and after moptix_render_counted
  *   "counted_span_us" (first wave in -> last wave out of the trace kernel) / "counted_tail_us" (the part of it after the last
  *   work item was handed out: the launch's drain; -1 for the per-lane kernel)

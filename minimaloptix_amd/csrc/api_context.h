@@ -64,6 +64,7 @@ struct Options {
   int slotsInUse = -1;            // -1 = chosen per launch from its size
   int drainBelow = 64;            // a workgroup of the packet kernel with this many paths left hands them to the drain kernel (0 = off)
   int auxDepth = 16;              // variant 4: depth from which a path's shadow rays get slots of their own (0 = off)
+  int specialize = 1;             // variant 4: a scene whose tables rule out every FEAT_* program (pt_types.h) runs the build without them (0 = always the general one)
   int queryBlocksPerCU = 32;      // ray queries (querykernel.hip): the grid's cap in workgroups per CU; beyond it lanes loop over rays
   int temporalFaceMotion = 0;     // 1 = moptix_denoise_temporal reprojects moved triangles through their own motion (api_temporal.hip)
   int radianceBufferMB = 256;     // radiance queries (radiancekernel.hip): the per-sample scratch a launch may use; a longer call runs in passes
@@ -117,6 +118,7 @@ struct moptix_context_t {
   bool formatDecided = false;
   unsigned long long probeCounts[4] = { 0, 0, 0, 0 };     // node steps, triangle tests of the probe rays under Node128; the same under Node64
   int lastVariant = -1;              // what the last render ran (get_option "kernel_variant_used")
+  int lastFeatures = pt::FEAT_ALL;   // the FEAT_* mask compiled into that render's trace kernel (get_option "kernel_features_used")
   int countedSpanUs = -1, countedTailUs = -1;   // last counted launch: first wave in -> last wave out, and the part of it after the last work item was handed out
   double kernelMs = 0.0, reduceMs = 0.0; uint64_t nLaunches = 0;
   bool asyncPending = false;
@@ -321,6 +323,8 @@ int begin_call(moptix_context c, bool withAccum);
 struct ReadBack { void* dst; const void* src; size_t bytes; };
 int read_back(moptix_context c, std::initializer_list<ReadBack> copies, const char* what);
 void fill_view(moptix_context c, SceneView& v);
+// The FEAT_* programs (pt_types.h) the scene's tables can reach, as they are now: materials, lights and textures change between launches.
+int scene_features(moptix_context c);
 // The scene as a query sees it (api_query.hip, api_radiance.hip, api_point.hip): the 64-byte nodes wherever the tree has them and option
 // "node_format" does not say 128 -- the node-format verdict of the render path is not consulted.  Returns the launch's cap of workgroups.
 int fill_query_view(moptix_context c, SceneView& v);
@@ -336,6 +340,7 @@ inline float* denoise_out(moptix_context c) { return c->dn.bound ? c->dn.bound :
 struct LaunchPlan {
   const TraceKernel* kernel;      // kPacketKernel, kQueueKernel, kLeanQueueKernel, or null = the per-lane megakernel (launch_megakernel)
   int variant;                    // the same as get_option "kernel_variant_used" reports it: 4, 3, 0
+  int features;                   // FEAT_* programs the trace kernel must contain (FEAT_ALL: no specialised build asked for)
   int nItems, tilesX;             // pixel slots of this rank (local tiles * 64); 8x8 tiles per row of the frame
   int nBlocks;
   long long perPass;              // launches per pass, before the out-of-memory halving of the per-sample buffer

@@ -75,6 +75,17 @@ void fill_view(moptix_context c, SceneView& v) {
   v.nTextures = (int)c->textures.size(); v.textures = c->dTextures.p;
 }
 
+// Conservative on purpose: a material in the table counts whether or not a primitive uses it.
+int scene_features(moptix_context c) {
+  int f = c->spheres.empty() ? 0 : FEAT_SPHERES;
+  for (const DevMaterial& m : c->mats) {
+    if (m.albedoTex != 0) f |= FEAT_TEXTURE;
+    if (m.kind == MAT_LAMBERTIAN || m.kind == MAT_METAL || m.kind == MAT_GLASS) f |= FEAT_PLAIN_MATERIALS;
+  }
+  for (const DevLight& l : c->lights) if (l.shape == LIGHT_SPHERE) f |= FEAT_SPHERE_LIGHT;
+  return f;
+}
+
 int fill_query_view(moptix_context c, SceneView& v) {
   fill_view(c, v);
   const bool node64 = c->bvh.nodes64 != nullptr && c->opt.nodeFormat != 128 && v.rootRef != kEmptyRef;

@@ -40,6 +40,7 @@ const Option kOptions[] = {
   { "analytic_queue", &Options::analyticQueue, nullptr, -1, 1, "in {-1,0,1}" },
   { "aux_depth", &Options::auxDepth, nullptr, 0, 100000, "in [0,100000]" },
   { "drain_below", &Options::drainBelow, nullptr, 0, 64, "in [0,64]" },
+  { "specialize", &Options::specialize, nullptr, 0, 1, "in {0,1}" },
   { "slots_in_use", &Options::slotsInUse, nullptr, -1, 1024, "in [-1,1024]" },
   { "builder", &Options::builder, nullptr, 0, 1, "in {0,1}", kAccelIfChanged },
   { "fast_shading", &Options::fastShading, nullptr, 0, 1, "in {0,1}" },
@@ -55,6 +56,7 @@ const Option kOptions[] = {
   { "comm_nonblocking_used", nullptr, [](moptix_context c) { return c->comm.nonBlocking ? 1 : 0; } },
   { "node_format_used", nullptr, [](moptix_context c) { return c->nodeFormatUsed; } },
   { "kernel_variant_used", nullptr, [](moptix_context c) { return c->lastVariant; } },
+  { "kernel_features_used", nullptr, [](moptix_context c) { return c->lastFeatures; } },      // FEAT_* mask (pt_types.h) of the last render's trace kernel; 15 = every program
   { "counted_span_us", nullptr, [](moptix_context c) { return c->countedSpanUs; } },
   { "counted_tail_us", nullptr, [](moptix_context c) { return c->countedTailUs; } },
   { "path_slots", nullptr, [](moptix_context) { return packetkernel_slots(); } },

@@ -170,6 +170,8 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   const bool useQueue = !usePacket && (byPixelSlots || ((variant >= 3) && (hasTris || analyticQueue)));
   p.kernel = usePacket ? &kPacketKernel : !useQueue ? nullptr : hasTris ? &kQueueKernel : &kLeanQueueKernel;      // scenes without triangles: queuekernel_lean.hip
   p.variant = usePacket ? 4 : useQueue ? 3 : 0;
+  // the packet kernel has a build without the programs this scene's tables cannot reach (packetkernel.hip; option "specialize" 0: never)
+  p.features = (usePacket && c->opt.specialize != 0) ? scene_features(c) : FEAT_ALL;
   // no tree to walk (queuekernel_lean.hip): a fourth workgroup per CU instead of path slots and stack entries
   if (p.kernel == &kLeanQueueKernel && c->opt.blocksPerCU == 3) p.nBlocks = c->numCUs * 4;
   // Slots without a path are what deep paths borrow for their shadow rays (packetkernel.hip, "aux_depth"); once the work
@@ -248,6 +250,7 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   if ((rc = plan_launch(c, a.scene, nSeeds, byPixelSlots, p)) != MOPTIX_OK || p.nItems == 0) return rc;
   c->lastVariant = p.variant;
   r.counted = counted; r.fast = c->opt.fastShading != 0;
+  c->lastFeatures = p.kernel == &kPacketKernel ? packetkernel_features(r.counted, r.fast, p.features) : FEAT_ALL;
 
   // ---- what the plan asks for ----
   a.accum = accum_ptr(c);
@@ -334,7 +337,7 @@ int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, con
   if (over) a.tileOrder = over->order;
   else if (a.tileMajor && a.tileCost) HIPCHK(c, c->tiles.sort(c->stream), "sort tiles");      // deepest path seen so far first, ties in raster order
   HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
-  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast), p.kernel->launchWhat);
+  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast, p.features), p.kernel->launchWhat);
   else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
   if (p.drainBelow > 0) HIPCHK(c, launch_drainkernel(c->stream, a, c->numCUs, r.counted, r.fast), "launch drain kernel");
   // Since the drain kernel came, a packet launch WITHOUT it ("drain_below" 0) has been followed by the per-lane megakernel: it finds the work counter

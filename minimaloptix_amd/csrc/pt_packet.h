@@ -52,14 +52,14 @@ struct PacketSink {
 // so that the three of them are not held in registers across the BRDF evaluations that follow).
 
 // Material.cu:172-221 for one hit, without the traces (ps.N, ps.V, ps.mat, ps.o set by on_result; ps.light == 0).
-template <bool CNT, bool FAST = false, class Sink = PacketSink>
+template <bool CNT, bool FAST = false, class Sink = PacketSink, int F = FEAT_ALL>
 PT_HD void on_lights_packet(const SceneView& sc, PathState& ps, Packet& pk, Counters& ct, const Sink& sink) {
   const DevMaterial m = load_const(at32(sc.mats, ps.mat));
   packet_clear(pk);
   const Onb onb = make_onb(ps.N);
   const DisneyView dv = disney_view<FAST>(m, onb, ps.V);      // shared by the evaluations of this hit (up to three lights + the bounce)
   v3 Cdlin = m.Cdlin, Cspec0 = m.Cspec0, Csheen = m.Csheen;
-  if (m.albedoTex != 0) {
+  if (has<F>(FEAT_TEXTURE) && m.albedoTex != 0) {
     Cdlin = ps.cdlin;
     disney_color_constants(Cdlin, m.specular, m.specularTint, m.sheenTint, m.metallic, Cspec0, Csheen);
   }
@@ -68,7 +68,7 @@ PT_HD void on_lights_packet(const SceneView& sc, PathState& ps, Packet& pk, Coun
     const DevLight* lt = &ltv;
     cnt<CNT>(ct.lightLoads); census<CNT>(ct, CR_LIGHT_DRAW);
     v3 pointOnLight, normalOnLight;
-    if (lt->shape == LIGHT_SPHERE) {
+    if (has<F>(FEAT_SPHERE_LIGHT) && lt->shape == LIGHT_SPHERE) {
       pointOnLight = lt->position + rand_in_unit_sphere(ps.seed) * lt->radius;
       normalOnLight = normalize(pointOnLight - lt->position);
     } else {
@@ -115,7 +115,7 @@ PT_HD void on_lights_packet(const SceneView& sc, PathState& ps, Packet& pk, Coun
 
 // The packet has been traced: att[i] = attenuation of shadow ray i (disneyAnyHit), tv = nearest hit of the continuation.
 // Runs until the path owns a new packet (ps.mode == M_TRACE) or the sample has ended (M_NEW_SAMPLE).
-template <bool CNT, bool FAST = false, class Sink = PacketSink>
+template <bool CNT, bool FAST = false, class Sink = PacketSink, int F = FEAT_ALL>
 PT_HD void on_result_packet(const SceneView& sc, PathState& ps, Packet& pk, const Trav& tv, const v3 att[kPacketShadows], Counters& ct,
                             const Sink& sink) {
   census<CNT>(ct, CR_RESULT);
@@ -132,8 +132,8 @@ PT_HD void on_result_packet(const SceneView& sc, PathState& ps, Packet& pk, cons
   if (!pk.hasBounce) { end_sample(ps); return; }
   if (pk.hasScale) ps.thr = (ps.thr * pk.bscale) * pk.binv;      // Material.cu:217-219 indirect = brdf * child / pdf
   ps.kind = RK_RADIANCE;
-  on_result<CNT>(sc, ps, tv, ct);
-  if (ps.mode == M_LIGHTS) { on_lights_packet<CNT, FAST, Sink>(sc, ps, pk, ct, sink); return; }
+  on_result<CNT, F>(sc, ps, tv, ct);
+  if (ps.mode == M_LIGHTS) { on_lights_packet<CNT, FAST, Sink, F>(sc, ps, pk, ct, sink); return; }
   if (ps.mode == M_TRACE) { packet_clear(pk); pk.hasBounce = 1; }       // glass / lambertian / metal: the continuation only
 }
 

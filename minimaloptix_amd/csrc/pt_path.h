@@ -129,7 +129,8 @@ PT_HD v3 neg_o_inv(v3 o, v3 inv) { return mk3(-(o.x * inv.x), -(o.y * inv.y), -(
 // 4) passes false: its scenes are triangle meshes with a handful of analytic primitives at most, the chunk never runs there, and
 // with the window test compiled in its register allocation came out with 69 spilled vector registers instead of 5 (+7 % on the
 // benchmark frame); without the chunk altogether with 37.  The allocation of that kernel is that fragile (NOTEBOOK.md).
-template <bool CNT, bool WINDOW = true>
+// F (pt_types.h FEAT_*): without FEAT_SPHERES the sphere loops are not compiled (the caller's scene has no analytic spheres).
+template <bool CNT, bool WINDOW = true, int F = FEAT_ALL>
 PT_HD void trav_begin(const SceneView& sc, const PathState& ps, Trav& tv, Counters& ct) {
   tv.tbest = ps.tmax; tv.bestPrim = -1; tv.bestTri = -1; tv.beta = 0.f; tv.gamma = 0.f;
   tv.att = mk3(1.f, 1.f, 1.f);
@@ -146,7 +147,7 @@ PT_HD void trav_begin(const SceneView& sc, const PathState& ps, Trav& tv, Counte
     // Four spheres per trip: their discriminants are four independent chains (one sphere alone is a chain of ~16 dependent
     // instructions behind a scalar load), the roots are taken only where a discriminant is not negative.  Same operations
     // per sphere as sphere_roots, and the equal-t rule of potential() makes the outcome independent of the order anyway.
-    for (; i0 + PT_SPHERE_CHUNK <= sc.nSpheres; i0 += PT_SPHERE_CHUNK) {
+    for (; has<F>(FEAT_SPHERES) && i0 + PT_SPHERE_CHUNK <= sc.nSpheres; i0 += PT_SPHERE_CHUNK) {
       float bq[PT_SPHERE_CHUNK], dq[PT_SPHERE_CHUNK];
 #pragma unroll
       for (int k = 0; k < PT_SPHERE_CHUNK; k++) {
@@ -177,7 +178,7 @@ PT_HD void trav_begin(const SceneView& sc, const PathState& ps, Trav& tv, Counte
       }
     }
 #endif
-    for (int i = i0; i < sc.nSpheres; i++) {              // sphereIntersect, Geometry.cu:18-55
+    for (int i = i0; has<F>(FEAT_SPHERES) && i < sc.nSpheres; i++) {              // sphereIntersect, Geometry.cu:18-55
       const DevSphere s = sc.spheres[i];
       float t1, t2;
       if (sphere_roots(s.center, s.radius, ps.o, ps.d, t1, t2)) {
@@ -193,7 +194,7 @@ PT_HD void trav_begin(const SceneView& sc, const PathState& ps, Trav& tv, Counte
     }
     cnt<CNT>(ct.analyticTests, (uint32_t)(sc.nSpheres + sc.nQuads));
   } else if (sc.anyDisneyAnalytic) {
-    for (int i = 0; i < sc.nSpheres && !terminated; i++) {
+    for (int i = 0; has<F>(FEAT_SPHERES) && i < sc.nSpheres && !terminated; i++) {
       const int mat = load_uniform(sc.sphereMat + i);
       if (sc.mats[mat].kind != MAT_DISNEY) continue;
       const DevSphere s = load_uniform(sc.spheres + i);
@@ -530,9 +531,10 @@ PT_HD void glass_body(const SceneView& sc, PathState& ps, float ior, v3 tint, co
 }
 
 // Hit attributes of the nearest primitive (Geometry.cu:30-37, 81-86, 134-157)
+template <int F = FEAT_ALL>
 PT_HD void hit_attributes(const SceneView& sc, const PathState& ps, const Trav& tv, HitAttr& h) {
   const float t = tv.tbest;
-  if (tv.bestPrim < sc.nSpheres) {
+  if (has<F>(FEAT_SPHERES) && tv.bestPrim < sc.nSpheres) {
     const DevSphere s = sc.spheres[tv.bestPrim];
     const v3 p = ray_at(ps.o, ps.d, t);
     h.geoNormal = normalize(p - s.center);
@@ -558,7 +560,7 @@ PT_HD void hit_attributes(const SceneView& sc, const PathState& ps, const Trav& 
     const int hasNormals = sp->hasNormals;
     h.mat = tp->mat;
     h.texu = 0.f; h.texv = 0.f;
-    if (sc.triUV != nullptr && at32(sc.mats, h.mat)->albedoTex != 0) {               // Geometry.cu:141-148
+    if (has<F>(FEAT_TEXTURE) && sc.triUV != nullptr && at32(sc.mats, h.mat)->albedoTex != 0) {               // Geometry.cu:141-148
       const TriUV* up = sc.triUV + tp->prim;
       if (up->hasUV) {
         const float w0 = 1.f - tv.beta - tv.gamma;
@@ -579,7 +581,7 @@ PT_HD void hit_attributes(const SceneView& sc, const PathState& ps, const Trav& 
 
 // The ray in flight has finished: run miss / closest-hit (radiance) or fold the shadow
 // result into the radiance (shadow).
-template <bool CNT>
+template <bool CNT, int F = FEAT_ALL>
 PT_HD void on_result(const SceneView& sc, PathState& ps, const Trav& tv, Counters& ct) {
   if (ps.kind == RK_SHADOW) {                                   // Material.cu:193-201
     if (ps.pendInv != 0.f && length_is_nonzero(tv.att)) {
@@ -598,7 +600,7 @@ PT_HD void on_result(const SceneView& sc, PathState& ps, const Trav& tv, Counter
   }
   cnt<CNT>(ct.closestHits); census<CNT>(ct, CR_HIT);
   HitAttr h;
-  hit_attributes(sc, ps, tv, h);
+  hit_attributes<F>(sc, ps, tv, h);
   const DevMaterial m = load_const(at32(sc.mats, h.mat));
   if (m.kind == MAT_LIGHT) {                                    // light, Material.cu:238-240
     census<CNT>(ct, CR_LIGHT);
@@ -611,7 +613,7 @@ PT_HD void on_result(const SceneView& sc, PathState& ps, const Trav& tv, Counter
   // at (1,1,1).
   if (ps.depth > sc.maxDepth) { census<CNT>(ct, CR_DEPTHCAP); end_sample(ps); return; }
 
-  if (m.kind == MAT_LAMBERTIAN) {                               // Material.cu:28-43
+  if (has<F>(FEAT_PLAIN_MATERIALS) && m.kind == MAT_LAMBERTIAN) {                               // Material.cu:28-43
     census<CNT>(ct, CR_LAMBERT);
     const v3 no = ray_at(ps.o, ps.d, tv.tbest);
     const v3 nd = normalize(h.geoNormal + rand_in_unit_sphere(ps.seed));
@@ -619,7 +621,7 @@ PT_HD void on_result(const SceneView& sc, PathState& ps, const Trav& tv, Counter
     ps.thr = ps.thr * m.albedo;
     cnt<CNT>(ct.bounceRays);
     bounce(sc, ps, no, nd, childSeed);
-  } else if (m.kind == MAT_METAL) {                             // Material.cu:49-66
+  } else if (has<F>(FEAT_PLAIN_MATERIALS) && m.kind == MAT_METAL) {                             // Material.cu:49-66
     census<CNT>(ct, CR_METAL);
     const v3 no = ray_at(ps.o, ps.d, tv.tbest);
     const v3 nd = normalize(reflect(ps.d, h.geoNormal) + rand_in_unit_sphere(ps.seed) * m.fuzz);
@@ -627,12 +629,12 @@ PT_HD void on_result(const SceneView& sc, PathState& ps, const Trav& tv, Counter
     ps.thr = ps.thr * m.albedo;
     cnt<CNT>(ct.bounceRays);
     bounce(sc, ps, no, nd, childSeed);
-  } else if (m.kind == MAT_GLASS) {                             // Material.cu:72-110
+  } else if (has<F>(FEAT_PLAIN_MATERIALS) && m.kind == MAT_GLASS) {                             // Material.cu:72-110
     census<CNT>(ct, CR_GLASS);
     glass_body<CNT>(sc, ps, m.refIdx, m.albedo, h, ct);
   } else {                                                      // disney, Material.cu:118-223
     v3 baseColor = m.color;
-    if (m.albedoTex != 0) {                                     // Material.cu:128-132
+    if (has<F>(FEAT_TEXTURE) && m.albedoTex != 0) {             // Material.cu:128-132
       baseColor = xyz(tex2d(sc.textures[m.albedoTex - 1], h.texu, h.texv));
       ps.cdlin = srgb2lin(baseColor);
     }

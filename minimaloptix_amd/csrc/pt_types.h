@@ -135,6 +135,12 @@ static_assert(sizeof(DevLight) == 80, "DevLight must be 80 bytes");
 enum { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_GLASS = 2, MAT_DISNEY = 3, MAT_LIGHT = 4 };
 enum { BRDF_NORMAL = 0, BRDF_GLASS = 1 };
 enum { LIGHT_SPHERE = 0, LIGHT_QUAD = 1 };
+// Programs a scene's tables can rule out as a whole (pt_path.h, pt_packet.h: template parameter F of the functions that hold their
+// tests).  A kernel instantiated without a bit does not contain that program; the host (api_core.hip scene_features) launches it only
+// for a scene whose tables cannot reach it, so the result is the same by construction.  FEAT_PLAIN_MATERIALS: the Lambertian, metal
+// and glass closest-hit programs (a Disney material whose brdfType is BRDF_GLASS is not one of them).
+enum { FEAT_TEXTURE = 1, FEAT_SPHERE_LIGHT = 2, FEAT_PLAIN_MATERIALS = 4, FEAT_SPHERES = 8, FEAT_ALL = 15 };
+template <int F> PT_HD constexpr bool has(int bit) { return (F & bit) != 0; }
 // What a primitive is to a shadow ray (disneyAnyHit, Material.cu:225-232): no any-hit program at all (lights, non-Disney
 // materials), an opaque Disney surface (attenuation 0, rtTerminateRay) or a Disney GLASS surface (attenuation *= colour).  The
 // builder writes it into every triangle record, so that a shadow ray's leaf visit needs the material table only for the
