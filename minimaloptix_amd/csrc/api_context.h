@@ -352,6 +352,7 @@ struct LaunchPlan {
 struct RenderLaunch {
   LaunchPlan p; LaunchArgs a;
   long long perPass;              // the plan's, after the out-of-memory halving
+  int handoutDivisor, handoutSeeds;      // what the hand-out constants in front of the work counter were made for (megakernel.h handout_consts)
   bool counted, fast;
 };
 // What an adaptive pass hands to launch_pass instead of the defaults: its own order list (the first nWork / nSeeds entries are the

@@ -171,7 +171,10 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   p.kernel = usePacket ? &kPacketKernel : !useQueue ? nullptr : hasTris ? &kQueueKernel : &kLeanQueueKernel;      // scenes without triangles: queuekernel_lean.hip
   p.variant = usePacket ? 4 : useQueue ? 3 : 0;
   // the packet kernel has a build without the programs this scene's tables cannot reach (packetkernel.hip; option "specialize" 0: never)
-  p.features = (usePacket && c->opt.specialize != 0) ? scene_features(c) : FEAT_ALL;
+  // (its hit records, pt_types.h TriFace, are addressed by a 32-bit byte offset from the TriShade array they follow: where the two arrays together reach
+  // 4 GB -- above 38 million triangles -- the scene runs the general build)
+  const bool faceTableOk = (unsigned long long)tri_face_offset(0) + (unsigned long long)scene.nTris * (sizeof(TriShade) + sizeof(TriFace)) + 64ull < (1ull << 32);
+  p.features = (usePacket && c->opt.specialize != 0 && faceTableOk) ? scene_features(c) : FEAT_ALL;
   // no tree to walk (queuekernel_lean.hip): a fourth workgroup per CU instead of path slots and stack entries
   if (p.kernel == &kLeanQueueKernel && c->opt.blocksPerCU == 3) p.nBlocks = c->numCUs * 4;
   // Slots without a path are what deep paths borrow for their shadow rays (packetkernel.hip, "aux_depth"); once the work
@@ -196,8 +199,9 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   } else {      // per thread, not per slot; LaunchArgs::ovfDepth stays 0
     p.overflowInts = lane_stack_overflow_entries((size_t)p.nBlocks * 256, c->bvh.stackBound, megakernel_lds_stack_entries());
   }
-  // [0] work counter, [1] watchdog flag, then (variant 4) the drain list (megakernel.h kDrain*): counters, capacity, threshold, entries
-  p.workInts = 2 + drain_list_ints(p.nBlocks, p.drainBelow);
+  // the hand-out constants (megakernel.h HandoutConsts), then [0] work counter, [1] watchdog flag, then (variant 4) the drain list
+  // (megakernel.h kDrain*): counters, capacity, threshold, entries; LaunchArgs::workCounter points at [0]
+  p.workInts = kHandoutWords + 2 + drain_list_ints(p.nBlocks, p.drainBelow);
   p.tileMajor = byPixelSlots ? 3 : p.kernel ? c->opt.tileMajor : 0;
   p.unitShift = p.tileMajor == 3 ? 0 : 6;
   p.historyUnits = (localTiles * 64) >> p.unitShift;
@@ -281,11 +285,15 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   a.sampleBuf = c->dSampleBuf.p;
   HIPCHK(c, c->dWork.ensure(p.workInts), "alloc work counter");
   {
-    const int hdr[2 + kDrainEntries] = { 0, 0, 0, 0, 0, 0, p.nBlocks * p.drainBelow, p.drainBelow };
-    HIPCHK(c, hipMemcpyAsync(c->dWork.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream), "init work counter");
-    HIPCHK(c, hipStreamSynchronize(c->stream), "sync");      // hdr lives on this stack frame
+    // the first pass takes min(perPass, nSeeds) seeds: its hand-out constants travel with the header (launch_pass writes them again for a pass of another size)
+    struct { HandoutConsts hc; int hdr[2 + kDrainEntries]; } w = { handout_consts(p.tileMajor, a.nItems, (int)std::min<long long>(perPass, nSeeds), a.tilesX, a.nRanks),
+                                                                   { 0, 0, 0, 0, 0, 0, p.nBlocks * p.drainBelow, p.drainBelow } };
+    static_assert(sizeof(w) == sizeof(int) * (kHandoutWords + 2 + kDrainEntries), "the work header is packed");
+    HIPCHK(c, hipMemcpyAsync(c->dWork.p, &w, sizeof(w), hipMemcpyHostToDevice, c->stream), "init work counter");
+    HIPCHK(c, hipStreamSynchronize(c->stream), "sync");      // w lives on this stack frame
+    r.handoutDivisor = handout_divisor(p.tileMajor, a.nItems, (int)std::min<long long>(perPass, nSeeds)); r.handoutSeeds = (int)std::min<long long>(perPass, nSeeds);
   }
-  a.workCounter = c->dWork.p;
+  a.workCounter = c->dWork.p + kHandoutWords;
   a.tileMajor = p.tileMajor; a.unitShift = p.unitShift;
   if (p.tileMajor) {
     HIPCHK(c, c->tiles.ensure(p.historyUnits, c->stream), "start depth history");      // new frame size / partition / granularity: afresh
@@ -333,7 +341,13 @@ int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, con
   LaunchArgs& a = r.a;
   const LaunchPlan& p = r.p;
   a.seeds = dSeeds; a.nSeeds = n; a.nWork = over ? over->nWork : n * a.nItems;
-  HIPCHK(c, hipMemsetAsync(c->dWork.p, 0, (2 + kDrainCap) * sizeof(int), c->stream), "zero work counter");      // counters only: capacity and threshold stay
+  if (handout_divisor(a.tileMajor, a.nItems, n) != r.handoutDivisor || n != r.handoutSeeds) {      // a pass of another size than the last (a batch's remainder, an adaptive pass): its own constants
+    const HandoutConsts hc = handout_consts(a.tileMajor, a.nItems, n, a.tilesX, a.nRanks);
+    HIPCHK(c, hipMemcpyAsync(a.workCounter - kHandoutWords, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream), "write hand-out constants");
+    HIPCHK(c, hipStreamSynchronize(c->stream), "sync");      // hc lives on this stack frame
+    r.handoutDivisor = handout_divisor(a.tileMajor, a.nItems, n); r.handoutSeeds = n;
+  }
+  HIPCHK(c, hipMemsetAsync(a.workCounter, 0, (2 + kDrainCap) * sizeof(int), c->stream), "zero work counter");      // counters only: capacity and threshold stay
   if (over) a.tileOrder = over->order;
   else if (a.tileMajor && a.tileCost) HIPCHK(c, c->tiles.sort(c->stream), "sort tiles");      // deepest path seen so far first, ties in raster order
   HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
@@ -412,7 +426,7 @@ int moptix_sync(moptix_context c) {
     if (hipEventElapsedTime(&ms2, c->ev1, c->ev2) == hipSuccess) c->reduceMs += ms2;
     c->asyncPending = false;
     int flags[2] = { 0, 0 };
-    if (c->dWork.p) HIPCHK(c, hipMemcpy(flags, c->dWork.p, sizeof(flags), hipMemcpyDeviceToHost), "read watchdog flag");
+    if (c->dWork.p) HIPCHK(c, hipMemcpy(flags, c->dWork.p + kHandoutWords, sizeof(flags), hipMemcpyDeviceToHost), "read watchdog flag");
     if (flags[1] != 0) return fail(c, MOPTIX_ERR_HIP, "render kernel hit its watchdog (option watchdog_ms); this pass was not added to accuBuffer");
   }
   return MOPTIX_OK;

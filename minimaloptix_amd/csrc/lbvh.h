@@ -9,7 +9,8 @@ struct LbvhResult {
   Node128* nodes = nullptr;    // device, nNodes (four-wide)
   Node64* nodes64 = nullptr;   // device, nNodes: the same nodes compressed (pt_lbvh.h compress_node), or nullptr if a node is too wide for the grid
   Tri48* tris = nullptr;       // device, nTris (sorted / leaf order)
-  TriShade* shade = nullptr;   // device, nTris
+  TriShade* shade = nullptr;   // device, nTris; behind them in the same allocation the nTris TriFace records of the lean packet kernel, which
+                               // SceneView::triShade and nTris therefore reach (pt_types.h tri_face_slot) without another kernel argument
   int nTris = 0, nNodes = 0, rootRef = kEmptyRef, depth = 0, leafSize = 0;   // depth: levels of four-wide nodes
   int stackBound = 0;          // most entries a traversal stack can hold (3 per level + 1)
   float buildMs = 0.f;

@@ -107,6 +107,7 @@ __global__ void k_leaves(int n, const uint64_t* __restrict__ keys, const float* 
     sh.n0 = mk3(q[0], q[1], q[2]); sh.n1 = mk3(q[3], q[4], q[5]); sh.n2 = mk3(q[6], q[7], q[8]); sh.hasNormals = 1;
   }
   shade[k] = sh;
+  *tri_face_slot(shade, n, k) = make_tri_face(t, sh);
   const float ex = ordered_to_float(box->sHi[0]) - ordered_to_float(box->sLo[0]);
   const float ey = ordered_to_float(box->sHi[1]) - ordered_to_float(box->sLo[1]);
   const float ez = ordered_to_float(box->sHi[2]) - ordered_to_float(box->sLo[2]);
@@ -548,7 +549,8 @@ hipError_t lbvh_build(hipStream_t stream, const float* dFacePos, const float* dF
   LB_CHECK(dmalloc(&left, (size_t)ni)); LB_CHECK(dmalloc(&right, (size_t)ni)); LB_CHECK(dmalloc(&first, (size_t)ni)); LB_CHECK(dmalloc(&last, (size_t)ni));
   LB_CHECK(dmalloc(&parentI, (size_t)ni)); LB_CHECK(dmalloc(&parentL, (size_t)n)); LB_CHECK(dmalloc(&kept, (size_t)ni + 1)); LB_CHECK(dmalloc(&newIndex, (size_t)ni + 1)); LB_CHECK(dmalloc(&opened, 2 * (size_t)ni + 2));
   LB_CHECK(dmalloc(&arrivals, (size_t)ni)); LB_CHECK(dmalloc(&box, (size_t)kReplicas)); LB_CHECK(dmalloc(&dDepth, 1));
-  LB_CHECK(dmalloc(&out->tris, (size_t)n)); LB_CHECK(dmalloc(&out->shade, (size_t)n));
+  LB_CHECK(dmalloc(&out->tris, (size_t)n));
+  LB_CHECK(hipMalloc((void**)&out->shade, (size_t)tri_face_offset(n) + sizeof(TriFace) * (size_t)n));      // [TriShade x n][TriFace x n]: pt_types.h tri_face_slot
   LB_CHECK(rocprim::radix_sort_keys(nullptr, tmpSort, keys, keysSorted, (size_t)n, 0, 64, stream));
   if (ni > 0) LB_CHECK(rocprim::exclusive_scan(nullptr, tmpScan, kept, newIndex, 0, (size_t)ni, rocprim::plus<int>(), stream));
   if (builder == 1 && n > leafSize) {

@@ -47,14 +47,13 @@ constexpr int kDrainDeep = 24;      // paths at least this deep go to the front 
 //   [kDrainBelow] the threshold (0 = off); an entry = the path's slot record, as an index into poolCold
 constexpr int kDrainList = 2, kDrainDeepN = 0, kDrainNext = 1, kDrainOtherN = 2, kDrainCap = 4, kDrainBelow = 5, kDrainEntries = 6;
 
-#if defined(__HIPCC__)
 // work item k -> (sample index, pixel).  Slot i = k % nItems is the (i & 63)-th pixel of this
 // rank's (i >> 6)-th 8x8 tile.  Tiles are dealt to the ranks in raster order, nRanks at a time, and the deal
 // rotates by one rank from each group of nRanks tiles to the next (tile-interleaved multi-GPU partition,
 // SURVEY 8e): a plain t % nRanks gives every rank the same columns in every row when nRanks divides the
 // tiles of a row (1920 / 8 = 240 tiles, 8 ranks), and the ranks' ray counts then differ by 3-4 %.
 // False for pixels outside the frame (this includes the tiles past the end of a rank's last group).
-__device__ __forceinline__ bool item_to_pixel(const LaunchArgs& a, int k, int& sample, int& pixel) {
+PT_HD bool item_to_pixel(const LaunchArgs& a, int k, int& sample, int& pixel) {
   sample = k / a.nItems;
   const int i = k - sample * a.nItems;
   const int lt = i >> 6, in = i & 63;
@@ -67,7 +66,7 @@ __device__ __forceinline__ bool item_to_pixel(const LaunchArgs& a, int k, int& s
 // Hand-out index k -> canonical work item (the index item_to_pixel and the per-sample buffer use).  Tile-major:
 // all samples of a tile are handed out back to back, tile after tile in tileOrder; the paths that bounce 256 times
 // (a chain of ~1000 dependent rays, ~28 ms) then start early and overlap the bulk instead of forming the tail.
-__device__ __forceinline__ int handout_to_item(const LaunchArgs& a, int k) {
+PT_HD int handout_to_item(const LaunchArgs& a, int k) {
   if (!a.tileMajor) return k;
   if (a.tileMajor == 3) {                               // all samples of a pixel back to back, deepest pixels first
     const int ui = k / a.nSeeds, sample = k - ui * a.nSeeds;
@@ -82,6 +81,69 @@ __device__ __forceinline__ int handout_to_item(const LaunchArgs& a, int k) {
   }
   return (r >> 6) * a.nItems + (lt << 6) + (r & 63);
 }
+// The two functions above in one, for the lean packet kernel (packetkernel_body.h, F == 0): hand-out index k -> work item, sample, pixel.
+// handout_to_item knows the sample and the slot (tile, pixel in the tile) before it folds them into the item, and item_to_pixel has x and
+// y before it folds them into the pixel: carried along, the divisions that recover them (by nItems on the tile-major paths, by the
+// frame's width in begin_sample) are not made, and one rank skips the deal's rotation.  Same items, same pixels: a slot is below nItems on
+// every path (k < nWork; an order list holds units of this rank), so item / nItems and item % nItems are the sample and the slot.
+//
+// The divisions that remain divide by launch constants: the first divisor of the hand-out (handout_divisor), the tiles of a row and, with
+// more than one rank, the ranks.  Each is a multiplication and a shift by a pair the host computes once (magic_div):
+//   for a divisor d in [1, 2^31) let l = ceil(log2 d), shift = 31 + l, mul = ceil(2^shift / d).  Then mul * d = 2^shift + e with 0 <= e < d <= 2^l,
+//   and for a dividend 0 <= n < 2^31:  n * mul / 2^shift = n / d + n * e / (d * 2^shift), where n * e < 2^31 * 2^l = 2^shift, so the second
+//   term is below 1 / d -- too small to carry n / d (whose fraction is at most (d - 1) / d) to the next integer: floor(n * mul / 2^shift) =
+//   floor(n / d).  2^(l - 1) < d gives mul <= 2^32 - 1 for d > 1 (mul = 2^31 for d = 1): mul is a 32-bit word, and n * mul < 2^63 is an
+//   unsigned 64-bit product.  (A 32-bit high product alone will not do: d = 1 needs shift = 31.)
+// Every dividend here is a hand-out index below nWork, a tile number or rank + tile number: non-negative ints, which plan_launch keeps below 2^31.
+// The pairs are not kernel arguments (sixteen more bytes of those cost 0.8 %, above): they sit in FRONT of the work counter, at
+// workCounter[-kHandoutWords ..], where the host writes them with the rest of the work header, and are read by scalar loads where they are used.
+struct MagicDiv { unsigned int mul, shift; };
+struct HandoutConsts { MagicDiv first, tilesX, ranks, seeds; };      // seeds: "tile_major" 2 alone divides by nSeeds a second time
+constexpr int kHandoutWords = 8;
+static_assert(sizeof(HandoutConsts) == kHandoutWords * sizeof(int), "HandoutConsts is kHandoutWords ints");
+inline MagicDiv magic_div(int d) {
+  int l = 0;
+  while ((1ll << l) < (long long)d) l++;
+  MagicDiv m; m.shift = 31u + (unsigned int)l;
+  m.mul = (unsigned int)(((1ull << m.shift) + (unsigned long long)d - 1ull) / (unsigned long long)d);
+  return m;
+}
+PT_HD int magic_quot(int n, MagicDiv m) { return (int)(((unsigned long long)(unsigned int)n * (unsigned long long)m.mul) >> m.shift); }
+// what the hand-out divides k by first: the work items of a sample, of a pixel or of a tile
+inline int handout_divisor(int tileMajor, int nItems, int nSeeds) { return !tileMajor ? nItems : tileMajor == 3 ? nSeeds : nSeeds << 6; }
+inline HandoutConsts handout_consts(int tileMajor, int nItems, int nSeeds, int tilesX, int nRanks) {
+  HandoutConsts h;
+  h.first = magic_div(handout_divisor(tileMajor, nItems, nSeeds)); h.tilesX = magic_div(tilesX); h.ranks = magic_div(nRanks); h.seeds = magic_div(nSeeds);
+  return h;
+}
+
+struct WorkItem { int item, sample, x, y, pixel; };
+PT_HD bool handout_lean(const LaunchArgs& a, const HandoutConsts* hc, int k, WorkItem& w) {      // each pair is loaded where it is used: two scalar registers, briefly
+  int slot;
+  const int q = magic_quot(k, load_uniform(&hc->first));      // k / (nItems | nSeeds | nSeeds << 6)
+  if (!a.tileMajor) {
+    w.sample = q; slot = k - q * a.nItems;
+  } else if (a.tileMajor == 3) {
+    w.sample = k - q * a.nSeeds;
+    slot = a.tileOrder ? a.tileOrder[q] : q;
+  } else {
+    const int r = k - q * (a.nSeeds << 6);
+    const int lt = a.tileOrder ? a.tileOrder[q] : q;
+    int in;
+    if (a.tileMajor == 2) { in = magic_quot(r, load_uniform(&hc->seeds)); w.sample = r - in * a.nSeeds; }
+    else { w.sample = r >> 6; in = r & 63; }
+    slot = (lt << 6) + in;
+  }
+  w.item = a.tileMajor ? w.sample * a.nItems + slot : k;
+  const int lt = slot >> 6, in = slot & 63;
+  int gt = lt;
+  if (__builtin_expect(a.nRanks != 1, 0)) { const int s = a.rank + lt; gt = lt * a.nRanks + (s - magic_quot(s, load_uniform(&hc->ranks)) * a.nRanks); }
+  const int ty = magic_quot(gt, load_uniform(&hc->tilesX)), tx = gt - ty * a.tilesX;
+  w.x = tx * 8 + (in & 7); w.y = ty * 8 + (in >> 3);
+  w.pixel = w.y * a.scene.width + w.x;
+  return (w.x < a.scene.width) & (w.y < a.scene.height);
+}
+#if defined(__HIPCC__)
 // Camera.cu:39 result of one sample; Camera.cu:41 (the add) happens in k_reduce_samples
 __device__ __forceinline__ void store_sample(const LaunchArgs& a, int item, v3 value) {
   float* sp = a.sampleBuf + 3 * (size_t)item;

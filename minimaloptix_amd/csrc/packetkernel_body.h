@@ -397,14 +397,21 @@
       }
       if (run) {
         if (ps.mode == M_RESULT) {
-          on_result_packet<CNT, FAST, SlotSink, F>(sc, ps, pk, res, att, ct, sink);
+          on_result_packet<CNT, FAST, SlotSink, (F == 0 && !N64) ? FEAT_SPLIT_HIT : F>(sc, ps, pk, res, att, ct, sink);      // pt_types.h FEAT_SPLIT_HIT
         } else {  // M_NEW_PIXEL: next (pixel, sample) work item
           int k = atomicAdd(a.workCounter, 1);
+          if constexpr (F == 0) {      // the lean build: one routine that carries sample, x and y along and divides by multiplying (megakernel.h handout_lean)
+            const HandoutConsts* hc = reinterpret_cast<const HandoutConsts*>(a.workCounter) - 1;      // read by scalar loads, dead when the branch ends
+            WorkItem w;
+            if (k >= a.nWork) { ps.mode = M_DONE; }
+            else if (handout_lean(a, hc, k, w)) { ps.pixel = w.pixel; ps.item = w.item; begin_sample_xy<CNT>(sc, ps, w.x, w.y, a.seeds[w.sample], ct); packet_primary(pk); }
+          } else {
           k = (k >= a.nWork) ? -1 : handout_to_item(a, k);
           if (CNT && k < 0) atomicMin(a.counters + kCntItemsRanOut, (unsigned long long)__builtin_amdgcn_s_memrealtime());   // first time the items ran out
           int s;
           if (k < 0) { ps.mode = M_DONE; }
           else if (item_to_pixel(a, k, s, ps.pixel)) { ps.item = k; begin_sample<CNT>(sc, ps, a.seeds[s], ct); packet_primary(pk); }
+          }
         }
       }
     }

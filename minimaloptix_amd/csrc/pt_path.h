@@ -477,9 +477,9 @@ PT_HD void trav_step(const SceneView& sc, const PathState& ps, Trav& tv, Stack& 
 // ---------------------------------------------------------------------------------------
 
 // Camera.cu:21-38: per-pixel seed, thin-lens offset, jittered pixel, primary ray
+// (x, y): the pixel's column and row, for a caller that has them at hand; begin_sample recovers them from ps.pixel
 template <bool CNT>
-PT_HD void begin_sample(const SceneView& sc, PathState& ps, int launchSeed, Counters& ct) {
-  const int x = ps.pixel % sc.width, y = ps.pixel / sc.width;
+PT_HD void begin_sample_xy(const SceneView& sc, PathState& ps, int x, int y, int launchSeed, Counters& ct) {
   ps.depth = 1;
   ps.seed = tea16((uint32_t)y * (uint32_t)sc.width + (uint32_t)x, (uint32_t)launchSeed);
   ps.thr = mk3(1.f, 1.f, 1.f); ps.rad = mk3(0.f, 0.f, 0.f);
@@ -493,6 +493,11 @@ PT_HD void begin_sample(const SceneView& sc, PathState& ps, int launchSeed, Coun
   ps.tmin = sc.epsT; ps.tmax = kRtDefaultMax; ps.kind = RK_RADIANCE;
   ps.mode = M_TRACE;
   cnt<CNT>(ct.samples); cnt<CNT>(ct.primaryRays); census<CNT>(ct, CR_GEN);
+}
+template <bool CNT>
+PT_HD void begin_sample(const SceneView& sc, PathState& ps, int launchSeed, Counters& ct) {
+  const int x = ps.pixel % sc.width, y = ps.pixel / sc.width;
+  begin_sample_xy<CNT>(sc, ps, x, y, launchSeed, ct);
 }
 
 // Camera.cu:39: clamp the sample.  The add into accuBuffer (Camera.cu:41) is done by the
@@ -530,10 +535,26 @@ PT_HD void glass_body(const SceneView& sc, PathState& ps, float ior, v3 tint, co
   bounce(sc, ps, no, nd, childSeed);
 }
 
+// A triangle hit of the lean packet kernel: the face's one 64-byte record (pt_types.h TriFace), the geometric normal as the builder evaluated it
+PT_HD void hit_attributes_face(const SceneView& sc, const PathState& ps, const Trav& tv, HitAttr& h) {
+  const TriFace fv = load_const(tri_face(sc, tv.bestTri));
+  h.mat = fv.matNrm & 0x7fffffff;
+  h.texu = 0.f; h.texv = 0.f;
+  h.geoNormal = fv.gn;
+  if (fv.matNrm < 0) {
+    const v3 n0 = mk3(fv.n0x, fv.n0y, fv.n0z), n1 = mk3(fv.n1x, fv.n1y, fv.n1z), n2 = mk3(fv.n2x, fv.n2y, fv.n2z);
+    h.shadingNormal = normalize((n1 * tv.beta + n2 * tv.gamma) + n0 * (1.f - tv.beta - tv.gamma));
+  } else {
+    h.shadingNormal = h.geoNormal;
+  }
+  refine_hitpoint(ray_at(ps.o, ps.d, tv.tbest), ps.d, h.geoNormal, fv.p0, h.back, h.front);
+}
+
 // Hit attributes of the nearest primitive (Geometry.cu:30-37, 81-86, 134-157)
 template <int F = FEAT_ALL>
 PT_HD void hit_attributes(const SceneView& sc, const PathState& ps, const Trav& tv, HitAttr& h) {
   const float t = tv.tbest;
+  if constexpr (F == 0) { if (tv.bestPrim >= sc.nSpheres + sc.nQuads) { hit_attributes_face(sc, ps, tv, h); return; } }
   if (has<F>(FEAT_SPHERES) && tv.bestPrim < sc.nSpheres) {
     const DevSphere s = sc.spheres[tv.bestPrim];
     const v3 p = ray_at(ps.o, ps.d, t);

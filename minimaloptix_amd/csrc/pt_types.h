@@ -105,6 +105,31 @@ struct alignas(16) TriShade {
 };
 static_assert(sizeof(TriShade) == 48, "TriShade must be 48 bytes");
 
+// Everything a closest hit reads of its face, in one 64-byte line, for the lean packet kernel (pt_path.h hit_attributes<0>): p0, the vertex
+// normals, the material and the geometric normal ready-made -- normalize(cross(e1, e0)) depends on the face alone, and a hit evaluated it
+// every time (a cross product, a correctly rounded square root and division: ~40 instructions of a kernel that vector issue binds).  Four
+// 16-byte look-ups instead of Tri48 + TriShade's six.  Written wherever Tri48 and TriShade are (lbvh.hip k_leaves, refitkernel.hip
+// k_refit_tris), by make_tri_face from those two records: the normal is the very expression hit_attributes evaluates, on the very e0 / e1
+// the other kernels read, so the bits are the same by construction.  The records follow the TriShade array in the same allocation
+// (tri_face_slot; same index as SceneView::tris), so that SceneView::triShade and nTris reach them and the view keeps its size.
+struct alignas(64) TriFace {
+  v3 p0; float n0x;
+  float n0y, n0z, n1x, n1y;
+  float n1z, n2x, n2y, n2z;
+  v3 gn; int matNrm;                  // normalize(cross(e1, e0)); material id, bit 31 = the face has vertex normals
+};
+static_assert(sizeof(TriFace) == 64, "TriFace must be 64 bytes");
+// byte offset of the TriFace records from the TriShade array they follow: its end, rounded up to a whole record
+PT_HD uint32_t tri_face_offset(int nTris) { return ((uint32_t)nTris * (uint32_t)sizeof(TriShade) + 63u) & ~63u; }
+PT_HD TriFace* tri_face_slot(TriShade* shade, int nTris, int tri) { return reinterpret_cast<TriFace*>(reinterpret_cast<char*>(shade) + tri_face_offset(nTris)) + tri; }
+PT_HD TriFace make_tri_face(const Tri48& t, const TriShade& sh) {
+  TriFace f;
+  f.gn = normalize(cross(t.e1, t.e0)); f.matNrm = t.mat | (sh.hasNormals ? (int)0x80000000u : 0);
+  f.p0 = t.p0; f.n0x = sh.n0.x; f.n0y = sh.n0.y; f.n0z = sh.n0.z;
+  f.n1x = sh.n1.x; f.n1y = sh.n1.y; f.n1z = sh.n1.z; f.n2x = sh.n2.x; f.n2y = sh.n2.y; f.n2z = sh.n2.z;
+  return f;
+}
+
 // texcoords of one face (upload order, indexed by Tri48::prim); fetched only when the hit material is textured
 struct alignas(16) TriUV { float u0, v0, u1, v1, u2, v2; int hasUV; int pad; };
 static_assert(sizeof(TriUV) == 32, "TriUV must be 32 bytes");
@@ -140,6 +165,10 @@ enum { LIGHT_SPHERE = 0, LIGHT_QUAD = 1 };
 // for a scene whose tables cannot reach it, so the result is the same by construction.  FEAT_PLAIN_MATERIALS: the Lambertian, metal
 // and glass closest-hit programs (a Disney material whose brdfType is BRDF_GLASS is not one of them).
 enum { FEAT_TEXTURE = 1, FEAT_SPHERE_LIGHT = 2, FEAT_PLAIN_MATERIALS = 4, FEAT_SPHERES = 8, FEAT_ALL = 15 };
+// Not a program and not part of FEAT_ALL: a lean build whose triangle hit still reads Tri48 + TriShade instead of the one TriFace record
+// (hit_attributes<0>).  The 128-byte-node lean packet kernels are instantiated with it: with the record their scalar spills rise (22 / 22 against
+// the 21 / 22 of tests/test_packet_features_cpu.py, under every layout and statement order tried: NOTEBOOK.md round 20).
+constexpr int FEAT_SPLIT_HIT = 16;
 template <int F> PT_HD constexpr bool has(int bit) { return (F & bit) != 0; }
 // What a primitive is to a shadow ray (disneyAnyHit, Material.cu:225-232): no any-hit program at all (lights, non-Disney
 // materials), an opaque Disney surface (attenuation 0, rtTerminateRay) or a Disney GLASS surface (attenuation *= colour).  The
@@ -198,5 +227,11 @@ struct SceneView {
   const TriUV* triUV;             // per face in upload order, or nullptr (no mesh has texcoords)
   int nTextures; const DevTexture* textures;
 };
+// A triangle's TriFace record through SceneView::triShade: the view -- a kernel argument of every trace kernel -- stays the size it is
+// (megakernel.h: sixteen more bytes cost the packet kernel 0.8 %).  The form of at32: the array's base in scalar registers plus one 32-bit
+// byte offset; api_render.hip plan_launch keeps a scene whose TriShade and TriFace arrays together reach 4 GB on the general kernel.
+PT_HD const TriFace* tri_face(const SceneView& sc, int tri) {
+  return reinterpret_cast<const TriFace*>(reinterpret_cast<const char*>(sc.triShade) + (uint32_t)(tri_face_offset(sc.nTris) + ((uint32_t)tri << 6)));
+}
 
 }  // namespace pt

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kBlock) k_refit_tris(const RefitArgs a) {
     const bool hasNrm = a.faceNrm != nullptr && a.faceHasNrm != nullptr && a.faceHasNrm[f] != 0;
     Tri48 t; TriShade sh; RefitBox raw;
     refit_triangle(a.facePos + 9 * (size_t)f, a.faceNrm + 9 * (size_t)f, hasNrm, old, t, sh, raw);
-    a.tris[k] = t; a.shade[k] = sh; a.raw[k] = raw;
+    a.tris[k] = t; a.shade[k] = sh; *tri_face_slot(a.shade, a.nTris, k) = make_tri_face(t, sh); a.raw[k] = raw;
     l[0] = raw.lox; l[1] = raw.loy; l[2] = raw.loz; h[0] = raw.hix; h[1] = raw.hiy; h[2] = raw.hiz;
   }
   const float v[6] = { wave_min(l[0]), wave_min(l[1]), wave_min(l[2]), wave_max(h[0]), wave_max(h[1]), wave_max(h[2]) };
