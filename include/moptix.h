@@ -248,7 +248,9 @@ int moptix_unpack_tiles(moptix_context ctx, int32_t rank, int32_t nRanks, const 
  *                      path (-1 = chosen per launch: 7/8 of them for variant 4 launches under 1e8 samples, else all); the others
  *                      are what deep paths borrow, see "aux_depth"
  *   "aux_depth"        variant 4: a path this deep (default 16; 0 = never) traces the shadow rays of each hit in slots
- *                      borrowed from finished paths, at the same time as the continuation ray (DESIGN.md "Borrowed slots")
+ *                      borrowed from finished paths, at the same time as the continuation ray (DESIGN.md "Borrowed slots").
+ *                      A launch of 1e8 samples or more with "slots_in_use" left at -1 keeps no slot free to borrow and runs as
+ *                      under 0, whatever the value
  *   "analytic_queue"   scenes without triangles: 1 = through the queue kernel, 0 = per-lane kernel, -1 (default) = queue
  *                      kernel from 64 primitives on
  *   "leaf_size"        1..8 triangles per BVH leaf (default 4; takes effect at the next build_accel)
@@ -285,7 +287,8 @@ int moptix_unpack_tiles(moptix_context ctx, int32_t rank, int32_t nRanks, const 
  *                      glass material and no analytic sphere is traced by a build of the trace kernel without those programs; 0 = always
  *                      the general build.  Decided at every launch from the tables as they are then; same image bits either way
  * read-only (get_option): "kernel_variant_used", "kernel_features_used" (the programs compiled into the last launch's trace kernel:
- *   1 textures | 2 sphere lights | 4 Lambertian / metal / glass | 8 analytic spheres; 15 = the general build, 0 = the lean one), "node_format_used", "path_slots", "num_cus", "comm_ranks" (size of the context's
+ *   1 textures | 2 sphere lights | 4 Lambertian / metal / glass | 8 analytic spheres; 15 = the general build, 0 = the lean one), "kernel_slim_used" (1: the last launch ran the lean
+ *   build without borrowed slots and, unless shadow rays keep their nearest candidate, without Disney GLASS; else 0), "node_format_used", "path_slots", "num_cus", "comm_ranks" (size of the context's
  *   communicator, 0 without one), "comm_nonblocking_used" (1: that communicator is non-blocking), and after moptix_render_counted
  *   "counted_span_us" (first wave in -> last wave out of the trace kernel) / "counted_tail_us" (the part of it after the last
  *   work item was handed out: the launch's drain; -1 for the per-lane kernel)

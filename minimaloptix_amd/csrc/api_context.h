@@ -119,6 +119,7 @@ struct moptix_context_t {
   unsigned long long probeCounts[4] = { 0, 0, 0, 0 };     // node steps, triangle tests of the probe rays under Node128; the same under Node64
   int lastVariant = -1;              // what the last render ran (get_option "kernel_variant_used")
   int lastFeatures = pt::FEAT_ALL;   // the FEAT_* mask compiled into that render's trace kernel (get_option "kernel_features_used")
+  int lastSlim = 0;                  // 1: that kernel was the packet kernel's slim build (get_option "kernel_slim_used")
   int countedSpanUs = -1, countedTailUs = -1;   // last counted launch: first wave in -> last wave out, and the part of it after the last work item was handed out
   double kernelMs = 0.0, reduceMs = 0.0; uint64_t nLaunches = 0;
   bool asyncPending = false;
@@ -341,6 +342,7 @@ struct LaunchPlan {
   const TraceKernel* kernel;      // kPacketKernel, kQueueKernel, kLeanQueueKernel, or null = the per-lane megakernel (launch_megakernel)
   int variant;                    // the same as get_option "kernel_variant_used" reports it: 4, 3, 0
   int features;                   // FEAT_* programs the trace kernel must contain (FEAT_ALL: no specialised build asked for)
+  bool slim;                      // variant 4: no borrowed slots (auxDepth 0) and no Disney GLASS where shadow rays do not keep their nearest candidate: a lean launch runs the slim build
   int nItems, tilesX;             // pixel slots of this rank (local tiles * 64); 8x8 tiles per row of the frame
   int nBlocks;
   long long perPass;              // launches per pass, before the out-of-memory halving of the per-sample buffer

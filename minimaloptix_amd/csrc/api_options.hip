@@ -57,6 +57,7 @@ const Option kOptions[] = {
   { "node_format_used", nullptr, [](moptix_context c) { return c->nodeFormatUsed; } },
   { "kernel_variant_used", nullptr, [](moptix_context c) { return c->lastVariant; } },
   { "kernel_features_used", nullptr, [](moptix_context c) { return c->lastFeatures; } },      // FEAT_* mask (pt_types.h) of the last render's trace kernel; 15 = every program
+  { "kernel_slim_used", nullptr, [](moptix_context c) { return c->lastSlim; } },              // 1: that kernel was the packet kernel's slim build (packetkernel.hip)
   { "counted_span_us", nullptr, [](moptix_context c) { return c->countedSpanUs; } },
   { "counted_tail_us", nullptr, [](moptix_context c) { return c->countedTailUs; } },
   { "path_slots", nullptr, [](moptix_context) { return packetkernel_slots(); } },

@@ -183,7 +183,12 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   // 66.7 ms with 448 of 512 slots in use against 70.1 ms with all of them; a 4-way share: 130.3 against 125.0 ms.
   // A scene that is mostly glass has hardly any shadow rays to borrow slots for: all slots carry paths there (glass knot at 16 spp: 53.9 against 55.9 ms).
   p.slotsInUse = c->opt.slotsInUse >= 0 ? c->opt.slotsInUse : (usePacket && c->opt.auxDepth > 0 && nSamples < 1.0e8 && c->glassFaceShare <= 0.5 ? packetkernel_slots() * 7 / 8 : 0);
+  // A launch of 1e8 samples or more whose slots are not the caller's choice keeps none free (above), so nothing can be borrowed before the work items
+  // run out, and the paths that are left then go to the drain kernel: such a launch runs without borrowed slots.  (Measured on the benchmark frame,
+  // profiles/r21_slim_isa.txt: "aux_depth" 0 against 16 in the same kernel, warm frame 301.03 against 301.73 ms, a context's first frame 306.98
+  // against 307.62 ms -- not slower in either, so the rule does not ask for a depth history.)
   p.auxDepth = usePacket ? c->opt.auxDepth : 0;
+  if (usePacket && c->opt.slotsInUse < 0 && nSamples >= 1.0e8) p.auxDepth = 0;
   if (usePacket) {
     // variant 4: the packet kernel's workgroups hand their last paths to the drain kernel (drainkernel.hip; "drain_below" = 0 keeps them in the packet kernel)
     // (not under "shadow_rule" 0 in a scene with glass: there a shadow ray's attenuation is a PRODUCT over the glass surfaces it crosses, taken in
@@ -191,6 +196,11 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
     bool glassMaterial = false;
     for (const DevMaterial& m : c->mats) if (m.kind == MAT_DISNEY && m.brdfType == BRDF_GLASS) glassMaterial = true;
     p.drainBelow = (glassMaterial && !scene.shadowNearest) ? 0 : c->opt.drainBelow;
+    // The slim build of the lean kernel (packetkernel.hip: AUX = false, GLASS = NEAR) holds no borrowed-slot machinery and, where shadow rays do not keep
+    // their nearest candidate, no Disney GLASS code: a lean launch runs it when it borrows no slot and the material TABLE has no Disney GLASS entry
+    // (glass under "shadow_rule" 0 has shadowNearest false and tinted attenuations: the NEAR = false slim kernel is not for it).  Whether the launch is
+    // lean is known with its counting / fast_shading mode (prepare_launch, the launcher); same image bits in every build.
+    p.slim = p.auxDepth == 0 && (scene.shadowNearest || !glassMaterial);
   }
   if (p.kernel) {
     p.ovfDepth = hasTris ? std::max(0, c->bvh.stackBound - p.kernel->lds_stack_entries() + 1) : 0;
@@ -255,6 +265,7 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   c->lastVariant = p.variant;
   r.counted = counted; r.fast = c->opt.fastShading != 0;
   c->lastFeatures = p.kernel == &kPacketKernel ? packetkernel_features(r.counted, r.fast, p.features) : FEAT_ALL;
+  c->lastSlim = (p.kernel == &kPacketKernel && c->lastFeatures == 0 && p.slim) ? 1 : 0;
 
   // ---- what the plan asks for ----
   a.accum = accum_ptr(c);
@@ -351,7 +362,7 @@ int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, con
   if (over) a.tileOrder = over->order;
   else if (a.tileMajor && a.tileCost) HIPCHK(c, c->tiles.sort(c->stream), "sort tiles");      // deepest path seen so far first, ties in raster order
   HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
-  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast, p.features), p.kernel->launchWhat);
+  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast, p.features, p.slim), p.kernel->launchWhat);
   else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
   if (p.drainBelow > 0) HIPCHK(c, launch_drainkernel(c->stream, a, c->numCUs, r.counted, r.fast), "launch drain kernel");
   // Since the drain kernel came, a packet launch WITHOUT it ("drain_below" 0) has been followed by the per-lane megakernel: it finds the work counter

@@ -35,6 +35,8 @@
 // analytic primitive (shadow rays then need the brute-force lists at every ray start).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "megakernel.h"
 #include "pt_lanestack.h"
 #include "pt_path.h"
@@ -168,6 +170,19 @@ struct SlotSink {
   }
 };
 
+// The same sink for a kernel without borrowed slots (AUX = false, below): no `axp` to carry through the Disney visit.
+struct OwnSlotSink {
+  SlotCold* cold; int slot; v4* nodeA; v4* nodeB; const PathState* ps; int root;
+  __device__ __forceinline__ OwnSlotSink(SlotCold* cold_, int slot_, v4* nodeA_, v4* nodeB_, int (*)[kStackN + 1], const PathState* ps_, int root_, int /*axp*/)
+      : cold(cold_), slot(slot_), nodeA(nodeA_), nodeB(nodeB_), ps(ps_), root(root_) {}
+  __device__ __forceinline__ void shadow(int j, v3 d, float tmax, v3 w, float inv) const {
+    SlotCold* cw = at32(cold, slot);
+    slot_store(&cw->pend[j], mk4(w.x, w.y, w.z, inv));
+    if (j == 0) { nodeA[slot] = mk4(ps->o.x, ps->o.y, ps->o.z, tmax); nodeB[slot] = mk4(d.x, d.y, d.z, i2f(root)); }   // ps->o: the hit point
+    else slot_store(&cw->ray[j - 1], mk4(d.x, d.y, d.z, tmax));
+  }
+};
+
 // NEAR: the scene has a Disney GLASS material, shadow rays keep their nearest any-hit candidate (pt_path.h, rule D5).  A template
 // parameter so that scenes without one -- the benchmark scene -- run code in which that logic does not exist.
 // F (pt_types.h FEAT_*): the programs the per-lane code of a kernel contains.  The same reasoning one step further: this kernel's
@@ -175,20 +190,51 @@ struct SlotSink {
 // lights -- the benchmark scene -- cannot reach the texture path (three double-precision pow() expansions), the sphere-light draw, the
 // Lambertian / metal / glass programs or the analytic sphere loops.
 //
-// Two __global__ templates, one body.  The lean kernel (no FEAT_* bit: what a scene like the benchmark's runs, plan_launch's choice) keeps the
+//
+// AUX, GLASS (round 21): two more things a launch can rule out, compile-time switches of the body and no FEAT_* bits.  AUX = false: the launch
+// borrows no slots (LaunchArgs::auxDepth 0 -- what plan_launch gives a launch of 1e8 samples or more, which keeps no slot free to borrow) and
+// the kernel holds none of that machinery: no `axp` live across the Disney visit, no join test in the leaf pass and the leave handler, no
+// claim loop in the batch store.  GLASS = false: no material is Disney GLASS, so a shadow ray's attenuation is (1,1,1) or (0,0,0): no
+// tinted `att` rows in the leaf pass and the batch load, no material id kept per leaf triangle.  A NEAR kernel always has GLASS.
+// The Disney program's glass arm (pt_path.h on_result -> glass_body) STAYS in every build: compiled out as well, the timed kernel took all
+// 168 vector registers and 28 spilled scalar ones (with it: 148 and 21; its twin: 159 and 25) for 0.85 ms of a 291 ms frame, which is
+// no gain by the project's rule (profiles/r21_slim_ab.txt), and tests/test_packet_slim_cpu.py holds the slim kernels to their twins' numbers.
+//
+// Three __global__ templates, one body.  The SLIM kernel (no FEAT_* bit, AUX = false, GLASS = NEAR: what the benchmark frame runs) keeps the
 // name the kernel has had since round 3 -- the profiles, tools/kernel_resources.py listings and the resource pin of the timed instantiation
-// go by it; the kernel that contains every program is pt_packetkernel_general.  The body is packetkernel_body.h, included into both as
+// go by it.  pt_packetkernel_aux is the lean kernel of rounds 19-20 (no FEAT_* bit, borrowed slots, glass): lean launches that borrow slots
+// (short launches, "aux_depth" with "slots_in_use") or meet glass under "shadow_rule" 0.  The kernel that contains every program is
+// pt_packetkernel_general.  The body is packetkernel_body.h, included into each as
 // their own statements: behind a call, even a forced-inline one, the general kernels came out with other register numbers and another
 // instruction order than they have had (same spill counts; the glass knot ran 0.75 % slower, NOTEBOOK.md round 19, as round 18 had found
 // for the point kernels).  Included, they are the parent's instruction for instruction.
+// -DPT_PK_SLIM_GLASS / -DPT_PK_SLIM_AUX (experiment builds, profiles/r21_slim_ab.txt): the slim kernel with one switch alone.
+#ifdef PT_PK_SLIM_GLASS
+constexpr bool kSlimKeepsGlass = true;
+#else
+constexpr bool kSlimKeepsGlass = false;
+#endif
+#ifdef PT_PK_SLIM_AUX
+constexpr bool kSlimKeepsAux = true;
+#else
+constexpr bool kSlimKeepsAux = false;
+#endif
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(const LaunchArgs a) {
   constexpr int F = 0;
+  constexpr bool AUX = kSlimKeepsAux, GLASS = NEAR || kSlimKeepsGlass;
+#include "packetkernel_body.h"
+}
+template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
+__global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_aux(const LaunchArgs a) {
+  constexpr int F = 0;
+  constexpr bool AUX = true, GLASS = true;
 #include "packetkernel_body.h"
 }
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_general(const LaunchArgs a) {
   constexpr int F = FEAT_ALL;
+  constexpr bool AUX = true, GLASS = true;
 #include "packetkernel_body.h"
 }
 
@@ -199,8 +245,9 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_
 // scheduling strategy is a per-file flag (Makefile), "max-ilp" is 0.85 % faster than the default on the 64-byte kernels (coffee 312.5 -> 309.9 ms,
 // glass knot -1.5 %) and 2-4 % SLOWER on the 128-byte ones (dining room) and on the queue kernels (random spheres) -- measured, round 6.
 #ifndef PT_PK_N128
-// Two builds exist per node format and shadow rule: every program (FEAT_ALL) and none of the optional ones (0), the latter uncounted and
-// with exact shading only.  A scene that needs any one of the programs runs the general build.
+// Three builds exist per node format and shadow rule: every program (FEAT_ALL) and none of the optional ones (0), the latter uncounted and
+// with exact shading only, with borrowed slots and glass (_aux) or without (the slim build).  A scene that needs any one of the programs runs
+// the general build.
 int packetkernel_features(bool counted, bool fastShading, int sceneFeatures) { return (counted || fastShading || sceneFeatures != 0) ? FEAT_ALL : 0; }
 int packetkernel_lds_stack_entries() { return kStackN; }
 int packetkernel_slots() { return kP * kWaves; }
@@ -218,20 +265,24 @@ static void launch_pk(dim3 grid, dim3 block, hipStream_t stream, const LaunchArg
   if (a.scene.shadowNearest) pt_packetkernel_general<CNT, true, FAST, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
   else                       pt_packetkernel_general<CNT, true, FAST, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
 }
-hipError_t PT_PK_LAUNCH(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features) {
+hipError_t PT_PK_LAUNCH(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim) {
   dim3 grid(nBlocks), block(kBlockThreads);
-  if (packetkernel_features(counted, fastShading, features) == 0) {      // the lean build: uncounted, exact shading
+  if (packetkernel_features(counted, fastShading, features) == 0 && slim) {      // the slim build: lean, and the plan rules borrowed slots and (NEAR = false) glass out
+    if (a.auxDepth != 0 && !kSlimKeepsAux) return hipErrorInvalidValue;                           // (the kernel would ignore it: the plan never asks for this)
     if (a.scene.shadowNearest) pt_packetkernel<false, true, false, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
     else                       pt_packetkernel<false, true, false, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
+  } else if (packetkernel_features(counted, fastShading, features) == 0) {      // the lean build: uncounted, exact shading
+    if (a.scene.shadowNearest) pt_packetkernel_aux<false, true, false, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
+    else                       pt_packetkernel_aux<false, true, false, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
   } else if (fastShading) { if (counted) launch_pk<true, true>(grid, block, stream, a); else launch_pk<false, true>(grid, block, stream, a); }
   else             { if (counted) launch_pk<true, false>(grid, block, stream, a); else launch_pk<false, false>(grid, block, stream, a); }
   return hipGetLastError();
 }
 #ifndef PT_PK_N128
-hipError_t launch_packetkernel_n128(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features);
-hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features) {
+hipError_t launch_packetkernel_n128(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);
+hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim) {
   // api_core.hip fill_view: the option node_format decides whether the scene view carries the 64-byte nodes
-  return a.scene.nodes64 != nullptr ? launch_packetkernel_n64(stream, a, nBlocks, counted, fastShading, features) : launch_packetkernel_n128(stream, a, nBlocks, counted, fastShading, features);
+  return a.scene.nodes64 != nullptr ? launch_packetkernel_n64(stream, a, nBlocks, counted, fastShading, features, slim) : launch_packetkernel_n128(stream, a, nBlocks, counted, fastShading, features, slim);
 }
 #endif
 

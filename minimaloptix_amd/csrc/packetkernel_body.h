@@ -1,7 +1,11 @@
-// packetkernel_body.h -- the statements of the packet kernel (packetkernel.hip), included into its two __global__ templates
-// pt_packetkernel (F = 0) and pt_packetkernel_general (F = FEAT_ALL).  Not a header in its own right: it sees the template parameters
-// CNT, SHARED, FAST, NEAR, N64, the constant F and the argument `a` of the kernel it is included into, and everything packetkernel.hip
-// declares in front of them.  packetkernel.hip says why this is an include and not a function.
+// packetkernel_body.h -- the statements of the packet kernel (packetkernel.hip), included into its three __global__ templates
+// pt_packetkernel (F = 0, the slim build), pt_packetkernel_aux (F = 0) and pt_packetkernel_general (F = FEAT_ALL).  Not a header in its own
+// right: it sees the template parameters CNT, SHARED, FAST, NEAR, N64, the constants F, AUX, GLASS and the argument `a` of the kernel it is
+// included into, and everything packetkernel.hip declares in front of them.  packetkernel.hip says why this is an include and not a function.
+// AUX = false: no borrowed slots (the launch runs with LaunchArgs::auxDepth 0); GLASS = false: the scene has no Disney GLASS material, a
+// shadow ray's attenuation is (1,1,1) or (0,0,0) and never a tinted row.  Both only take code away that such a launch cannot reach.
+// (GLASS stops at the rows: the Disney program keeps its glass arm, packetkernel.hip says why.)
+  static_assert(GLASS || !NEAR, "a scene whose shadow rays keep their nearest candidate has a Disney GLASS material");
   constexpr int NS = SHARED ? kP * kWaves : kP;          // slots per pool
   __shared__ PoolLds<NS> sPool[SHARED ? 1 : kWaves];
   __shared__ WavePriv<NS> sPriv[kWaves];
@@ -81,19 +85,22 @@
   // Flag word of a slot after a traversal step.  While the slot's shadow rays are out in borrowed slots, other waves
   // count down in the join bits of the word: the owner then leaves those bits alone.
   auto store_flags = [&](int slot, int value) {
+    if constexpr (!AUX) W.stack[slot][0] = value;
+    else {
     if (__builtin_expect((value & kHasAux) != 0, 0)) { atomicAnd(&W.stack[slot][0], kJoinMask); atomicOr(&W.stack[slot][0], value & ~kJoinMask); }
     else W.stack[slot][0] = value;
+    }
   };
   // The path slot's own ray is done.  True = some shadow rays are still out: the slot parks (in no queue) and the last
   // of them pushes it to Q_SHADE.
-  auto arrive_parks = [&](int slot) -> bool {
+  [[maybe_unused]] auto arrive_parks = [&](int slot) -> bool {
     const int old = atomicOr(&W.stack[slot][0], kArrived);
     return ((old >> kJoinShift) & 3) != 0;
   };
   // A borrowed slot's shadow ray is done (its attenuation is in its flag word / att row, read by the path slot's next
   // visit).  Returns the path slot if this was the last one out and the path slot's own ray is done as well (the caller
   // pushes it to Q_SHADE), else -1.
-  auto aux_done = [&](int fl, int& dest) -> int {
+  [[maybe_unused]] auto aux_done = [&](int fl, int& dest) -> int {
     const int parent = aux_parent(fl);
     const int old = atomicSub(&W.stack[parent][0], 1 << kJoinShift);
     const bool last = (old & kJoinMask) == ((1 << kJoinShift) | kArrived);
@@ -106,14 +113,16 @@
   // about 70 us with all 512 slots of every pool, so a path that bounces to the depth cap (about 1000 dependent rays)
   // takes 70-90 ms however short the launch is.  A short launch (one rank's share of a multi-GPU frame) therefore
   // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, api_render.hip plan_launch).
-  const bool auxOn = SHARED && a.auxDepth > 0 && sc.rootRef >= 0;
+  [[maybe_unused]] const bool auxOn = SHARED && a.auxDepth > 0 && sc.rootRef >= 0;
   const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? (SHARED ? a.slotsInUse : max(64, a.slotsInUse / kWaves)) : NS;
   {
+    if constexpr (AUX) {
     if (SHARED && threadIdx.x < NS / 32) {      // slots without a path can be borrowed from the start
       const int lo = (int)threadIdx.x * 32;
       W.freeMask[threadIdx.x] = !auxOn || nUse >= lo + 32 ? 0u : (nUse <= lo ? ~0u : ~0u << (nUse - lo));
     }
     if (threadIdx.x == 0) W.nFree = auxOn ? NS - nUse : 0;
+    }
     const int first = SHARED ? threadIdx.x : lane, step = SHARED ? kBlockThreads : 64;
     for (int s = first; s < nUse; s += step) {
       i4 ctl; ctl.x = -1; ctl.y = 0; ctl.z = 0; ctl.w = M_NEW_PIXEL;     // item -1: whatever sample comes first is "new" (rows get written)
@@ -227,7 +236,9 @@
       // end it at any leaf) or a leaf reached with an empty stack; a radiance ray with entries on its stack goes on after this leaf
       if (more && (isSwitch || shadow || (fl & kSpMask) == 0)) { wn = slot_load(&cs->ray[cur]); PT_ROWS(2, 1); }
       if (!isSwitch) {
+        if constexpr (GLASS) {
         if (shadow) { if (fl_stat(fl, cur) == 2) { wr = slot_load(&cs->att[cur]); PT_ROWS(2, 1); } }
+        }
         // the continuation's hit row stays where it is: tbest (LDS) decides every candidate except one at EXACTLY tbest, and
         // only then the primitive id of the hit the slot holds is needed (below).  The row is in a 100 MB pool, the slowest
         // fetch of this pass by far.
@@ -252,14 +263,19 @@
         tv.inv = mk3(0.f, 0.f, 0.f); tv.tbest = na.w;      // the leaf step does not use 1/d
         tv.node = node0; tv.sp = fl & kSpMask;
         tv.bestTri = -1; tv.bestPrim = -1; tv.beta = 0.f; tv.gamma = 0.f; tv.att = mk3(1.f, 1.f, 1.f); tv.bestCls = SHADOW_NONE;
+        if constexpr (GLASS) {
         if (shadow) { if (fl_stat(fl, cur) == 2) { tv.att = mk3(wr.x, wr.y, wr.z); if (sc.shadowNearest) tv.bestPrim = f2i(wr.w); } }
         else if (hitValid) tv.bestPrim = kPrimUnknown;       // "some primitive at tbest": any candidate at exactly tbest passes potential() for now
+        } else { if (!shadow && hitValid) tv.bestPrim = kPrimUnknown; }
         const int oldPrim = tv.bestPrim;
-        const v3 oldAtt = tv.att;
+        [[maybe_unused]] const v3 oldAtt = tv.att;
         SlotStack st = make_stack(slot);
-        trav_leaf_step_fetched<CNT>(sc, ps, tv, st, ct, ch);
+        trav_leaf_step_fetched<CNT, GLASS>(sc, ps, tv, st, ct, ch);
         int nfl = fl & ~kSpMask;
-        if (shadow) {
+        if (!GLASS && shadow) {
+          // no glass: the only any-hit verdict is an opaque surface's, which ends the ray with attenuation (0,0,0) -- status 1, no row
+          if (tv.att.x == 0.f) nfl = (nfl & ~(3 << (kStatShift + 2 * cur))) | (1 << (kStatShift + 2 * cur));
+        } else if (shadow) {
           if (sc.shadowNearest) {
             // the verdict of the nearest any-hit surface so far and that surface's id (equal-t rule) travel in the att row
             if (tv.bestPrim != oldPrim) {
@@ -289,11 +305,13 @@
           W.nodeB[slot].w = i2f(tv.node);
           store_flags(slot, tv.sp | nfl);
           pendDest = tv.node == kTravDone ? ((nfl & kShadeFlag) ? Q_SHADE : Q_GEN) : (tv.node >= 0 ? Q_NODE : Q_LEAF);
+          if constexpr (AUX) {
           if (__builtin_expect(tv.node == kTravDone && (nfl & (kHasAux | kAuxSlot)) != 0, 0)) {      // rare: deep paths only
             if (nfl & kAuxSlot) {
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");        // the att row written above is read by the path slot's visit
               pendSlot = aux_done(nfl, pendDest);
             } else if (arrive_parks(slot)) pendDest = DEST_NONE;
+          }
           }
         }
       }
@@ -330,7 +348,7 @@
       const int fl = W.stack[slot][0];
       const bool hitValid = (fl & kHitValid) != 0;
       const int nSh = (fl >> kPendShift) & 3;          // 0 for a slot that waits for a work item (flags are cleared then)
-      const bool hadAux = (fl & kHasAux) != 0;         // its shadow rays were traced by the borrowed slots
+      const bool hadAux = AUX && (fl & kHasAux) != 0;  // its shadow rays were traced by the borrowed slots
       const i4 ctl = slot_load(&cs->ctl);
 #ifdef PT_EVLOG
       if (ctl.y >= 100) sEvOn = 1;
@@ -338,7 +356,7 @@
       const v4 thrIn = slot_load(&cs->thr), radIn = slot_load(&cs->rad);
       v4 wh = mk4(0.f, 0.f, 0.f, 0.f), wb = mk4(1.f, 1.f, 1.f, 1.f);
       v4 wp[kPacketShadows], wa[kPacketShadows];
-      if (ctl.w & kCtlHoldsAux) axp = f2i(thrIn.w);
+      if constexpr (AUX) { if (ctl.w & kCtlHoldsAux) axp = f2i(thrIn.w); }
       PT_ROWS(0, 3);
       if (hitValid) { wh = slot_load(&cs->hit); PT_ROWS(0, 1); }
       if (fl & kHasScale) { wb = slot_load(&cs->bsc); PT_ROWS(0, 1); }
@@ -349,8 +367,10 @@
           wp[i] = slot_load(&cs->pend[i]); PT_ROWS(0, 1);
           const int ax = (axp >> (kSlotBits * i)) & kSlotMask;                 // only used with hadAux
           const int stt = hadAux ? fl_stat(W.stack[ax][0], 0) : fl_stat(fl, i);
+          if constexpr (GLASS) {
           if (stt == 2) { wa[i] = hadAux ? slot_load(&at32(cold, ax)->att[0]) : slot_load(&cs->att[i]); PT_ROWS(0, 1); }
           else if (stt == 1) wa[i] = mk4(0.f, 0.f, 0.f, 0.f);
+          } else { if (stt == 1) wa[i] = mk4(0.f, 0.f, 0.f, 0.f); }
         }
       }
       const v4 na = W.nodeA[slot], wd = W.nodeB[slot];
@@ -369,7 +389,8 @@
       if (hitValid) { res.bestTri = f2i(wh.x); res.bestPrim = f2i(wh.y); res.beta = wh.z; res.gamma = wh.w; }
       if (ps.mode == M_TRACE) ps.mode = M_RESULT;
     }
-    const SlotSink sink{ cold, slot >= 0 ? slot : 0, W.nodeA, W.nodeB, W.stack, &ps, sc.rootRef, axp };
+    using Sink = std::conditional_t<AUX, SlotSink, OwnSlotSink>;
+    const Sink sink{ cold, slot >= 0 ? slot : 0, W.nodeA, W.nodeB, W.stack, &ps, sc.rootRef, axp };
     if (CNT) { __builtin_amdgcn_s_waitcnt(0); PT_SUB(tBLoad); }
 #ifdef PT_EVLOG
     __builtin_amdgcn_s_waitcnt(0); PT_EV(2, 0);
@@ -397,7 +418,7 @@
       }
       if (run) {
         if (ps.mode == M_RESULT) {
-          on_result_packet<CNT, FAST, SlotSink, (F == 0 && !N64) ? FEAT_SPLIT_HIT : F>(sc, ps, pk, res, att, ct, sink);      // pt_types.h FEAT_SPLIT_HIT
+          on_result_packet<CNT, FAST, Sink, (F == 0 && !N64) ? FEAT_SPLIT_HIT : F>(sc, ps, pk, res, att, ct, sink);      // pt_types.h FEAT_SPLIT_HIT
         } else {  // M_NEW_PIXEL: next (pixel, sample) work item
           int k = atomicAdd(a.workCounter, 1);
           if constexpr (F == 0) {      // the lean build: one routine that carries sample, x and y along and divides by multiplying (megakernel.h handout_lean)
@@ -423,13 +444,16 @@
     if (have) {
       SlotCold* cw = at32(cold, slot);
       // borrowed slots go back when the path has ended (the lane may hold a new path's camera ray by now)
+      if constexpr (AUX) {
       if (axp >= 0 && !(ps.mode == M_TRACE && ps.depth >= a.auxDepth)) {
         for (int j = 0; j < kPacketShadows; j++) { const int ax = (axp >> (kSlotBits * j)) & kSlotMask; atomicOr(&W.freeMask[ax >> 5], 1u << (ax & 31)); }
         atomicAdd(&W.nFree, kPacketShadows);
         axp = -1;
       }
+      }
       // a path that gets deep borrows three slots (one per possible shadow ray of a hit; used from its next hit on)
       int axpNext = axp;
+      if constexpr (AUX) {
       if (auxOn) {
         const bool wantAux = axp < 0 && ps.mode == M_TRACE && ps.depth >= a.auxDepth;
         if (wantAux && W.nFree >= kPacketShadows) {                // rare: lanes take their turn at the free list (LDS atomics)
@@ -446,6 +470,7 @@
           if (got == kPacketShadows) { axpNext = pack; atomicSub(&W.nFree, kPacketShadows); }
           else for (int j = 0; j < got; j++) { const int ax = (pack >> (kSlotBits * j)) & kSlotMask; atomicOr(&W.freeMask[ax >> 5], 1u << (ax & 31)); }
         }
+      }
       }
       i4 ctl; ctl.x = ps.item; ctl.y = ps.depth; ctl.z = (int)ps.seed;
       ctl.w = ps.mode | (pk.nShadow << 3) | (pk.hasBounce << 5) | (pk.hasScale << 6);
@@ -468,7 +493,7 @@
         if (hitNow) { slot_store(&cw->hit, mk4(i2f(-1), i2f(bp0), 0.f, 0.f)); PT_ROWS(1, 1); }
         // rows the packet's sink wrote during the visit (SlotSink::shadow): one weight row per shadow ray, one ray row for each after the first
         PT_ROWS(1, pk.nShadow + ((axp >= 0 || pk.nShadow == 0) ? 0 : pk.nShadow - 1));
-        useAux = axp >= 0 && pk.nShadow > 0;               // the shadow rays sit in the borrowed slots (SlotSink)
+        if constexpr (AUX) useAux = axp >= 0 && pk.nShadow > 0;      // the shadow rays sit in the borrowed slots (SlotSink)
         const int nOwnSh = useAux ? 0 : pk.nShadow;
         const int nRays = nOwnSh + pk.hasBounce;
         const v4 rb = mk4(ps.d.x, ps.d.y, ps.d.z, tb0);                                     // the continuation: last ray of the list
@@ -495,13 +520,17 @@
       } else {
         W.stack[slot][0] = 0;
         pendDest = (ps.mode == M_NEW_PIXEL) ? Q_GEN : DEST_DONE;
+        if constexpr (AUX) {
         if (auxOn && ps.mode != M_NEW_PIXEL) {               // no work item left for this slot: deep paths may borrow it
           atomicOr(&W.freeMask[slot >> 5], 1u << (slot & 31)); atomicAdd(&W.nFree, 1);
         }
+        }
       }
     }
+    if constexpr (AUX) {
     if (auxOn && __ballot(useAux) != 0ull) {                // the borrowed slots start at the root, with this wave
       for (int j = 0; j < kPacketShadows; j++) local_push((useAux && j < pk.nShadow) ? Q_NODE : DEST_NONE, (axp >> (kSlotBits * j)) & kSlotMask);
+    }
     }
     if constexpr (!SHARED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     PT_SUB(tBStore);
@@ -524,11 +553,13 @@
           const int nodeOut = (ntv.node == kTravDone && fl_more(nsFlag)) ? kSwitchRef : ntv.node;   // ray done, packet not: the leaf pass switches rays
           W.nodeB[ns].w = i2f(nodeOut); store_flags(ns, ntv.sp | nsFlag);
           dest = (nodeOut == kTravDone) ? ((nsFlag & kShadeFlag) ? Q_SHADE : Q_GEN) : Q_LEAF;   // a lane leaves at a leaf, at a ray switch or finished
+          if constexpr (AUX) {
           if (__builtin_expect(nodeOut == kTravDone && (nsFlag & (kHasAux | kAuxSlot)) != 0, 0)) {     // rare: deep paths only
             if (nsFlag & kAuxSlot) {
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");    // att rows written by this wave's last leaf pass
               pushSlot = aux_done(nsFlag, dest);
             } else if (arrive_parks(ns)) dest = DEST_NONE;
+          }
           }
         }
         local_push(dest, pushSlot);
@@ -661,6 +692,7 @@
         int fl = W.stack[slot][0];
         const i4 ctl = slot_load(&cw->ctl);
         if ((ctl.w & 7) != M_TRACE) continue;           // a slot that only waits for a work item (there is none)
+        if constexpr (AUX) {
         if (fl & kHasAux) {
           const int axp = f2i(slot_load(&cw->thr).w);
           const int nS = (fl >> kPendShift) & 3;
@@ -674,6 +706,7 @@
             }
           }
           fl &= ~(kHasAux | kJoinMask);
+        }
         }
         const v4 na = W.nodeA[slot], nb = W.nodeB[slot];
         slot_store(&cw->spare[0], na);

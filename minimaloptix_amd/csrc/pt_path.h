@@ -102,10 +102,12 @@ PT_HD void shadow_candidate(const SceneView& sc, int mat, float t, int prim, flo
 }
 
 // The same two for a triangle, whose record says what it is to a shadow ray (Tri48::shadow): only a glass surface's colour is
-// still read from the material table.
+// still read from the material table.  GLASS = false: the caller's scene has no Disney GLASS material (no triangle is SHADOW_GLASS), the
+// tint does not exist and `mat` is not read.
+template <bool GLASS = true>
 PT_HD bool shadow_any_hit_tri(const SceneView& sc, int cls, int mat, v3& att) {
   if (cls == SHADOW_NONE) return false;
-  if (cls == SHADOW_GLASS) { att = att * load_const(&at32(sc.mats, mat)->color); return false; }
+  if constexpr (GLASS) { if (cls == SHADOW_GLASS) { att = att * load_const(&at32(sc.mats, mat)->color); return false; } }
   att = mk3(0.f, 0.f, 0.f);
   return true;
 }
@@ -424,7 +426,7 @@ PT_HD void leaf_fetch4(const SceneView& sc, int leafRef, int base, LeafChunk& ch
     ch.p0[j] = tp->p0; ch.e0[j] = tp->e0; ch.e1[j] = tp->e1; ch.mat[j] = tp->mat; ch.prim[j] = tp->prim; ch.shadow[j] = tp->shadow;
   }
 }
-template <bool CNT, class Stack>
+template <bool CNT, bool GLASS = true, class Stack>
 PT_HD void trav_leaf_step_fetched(const SceneView& sc, const PathState& ps, Trav& tv, Stack& st, Counters& ct, LeafChunk& ch) {
   {
     const int first = leaf_first(tv.node), count = leaf_count(tv.node);
@@ -448,7 +450,7 @@ PT_HD void trav_leaf_step_fetched(const SceneView& sc, const PathState& ps, Trav
               }
             } else if (sc.shadowNearest) {
               shadow_candidate_tri(sc, ch.shadow[j], ch.mat[j], t, triBase + ch.prim[j], ps.tmin, tv.tbest, tv.bestPrim, tv.att);
-            } else if (shadow_any_hit_tri(sc, ch.shadow[j], ch.mat[j], tv.att)) terminated = true;
+            } else if (shadow_any_hit_tri<GLASS>(sc, ch.shadow[j], ch.mat[j], tv.att)) terminated = true;
           }
         }
       }

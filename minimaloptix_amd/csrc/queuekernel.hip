@@ -648,7 +648,7 @@ static void launch_qk(dim3 grid, dim3 block, hipStream_t stream, const LaunchArg
   if (a.scene.shadowNearest) pt_queuekernel<CNT, true, FAST, true><<<grid, block, 0, stream>>>(a);
   else                       pt_queuekernel<CNT, true, FAST, false><<<grid, block, 0, stream>>>(a);
 }
-hipError_t PT_QK_EXPORT(launch_queuekernel)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int /*features*/) {
+hipError_t PT_QK_EXPORT(launch_queuekernel)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int /*features*/, bool /*slim*/) {
   dim3 grid(nBlocks), block(kBlockThreads);
   // fastShading: opt-in approximate BRDF arithmetic (pt_disney.h ShadeMath)
   if (fastShading) { if (counted) launch_qk<true, true>(grid, block, stream, a); else launch_qk<false, true>(grid, block, stream, a); }
