@@ -7,8 +7,8 @@
 // hit's work that does not depend on a trace (every light draw, the facing tests, disneyPdf / disneyEval per light, the
 // BRDF sample, the seed fork) and leaves a PACKET: up to three shadow rays and the continuation ray, all from the hit
 // point.  The slot then traces the packet's rays one after the other WITHOUT going back to shading: when a ray ends and
-// another one is pending, the next leaf pass loads that ray (16 bytes of the slot record) and restarts the slot at the
-// root.  The visit that follows folds the shadow results into the radiance in light order and shades the continuation's
+// another one is pending, the next leaf pass -- or, in a kernel built with SWITCH (below), the scheduler loop itself where the ray
+// ended in the node loop -- loads that ray (16 bytes of the slot record) and restarts the slot at the root.  The visit that follows folds the shadow results into the radiance in light order and shades the continuation's
 // hit.  Same random draws, same decisions, same floating-point operations on the path's values as variants 0-3 (the
 // images are bit-identical); a path of depth k is a chain of k visits instead of up to 4k.
 //
@@ -28,6 +28,9 @@
 //
 //   * round 6: a workgroup that is down to its last paths (the launch's drain) stops shading partial batches and, once every path it has left waits in
 //     Q_SHADE / Q_GEN, hands them to drainkernel.hip BEHIND the main loop and leaves (the block after the loop says why it is there and not in it);
+//   * round 22: a third compile-time switch of the body, SWITCH, beside AUX and GLASS (all three are described in front of the kernels below): the
+//     NEAR = false slim kernels take a packet's next ray up in the scheduler loop's leave handler where a ray ends in the node loop, and their leaf
+//     pass has no switch arm; every other kernel keeps the hop through the leaf ring (kSwitchRef);
 //   * this file is compiled twice (Makefile): as it stands for the 64-byte-node instantiations, with LLVM's max-ilp scheduling, and through
 //     packetkernel_n128.hip (PT_PK_N128) for the 128-byte-node ones with the default strategy -- each is a few per cent slower under the other's.
 //
@@ -101,12 +104,15 @@ struct PoolLds {
 template <int NS>
 struct WavePriv {
   unsigned short qnode[ring_capacity(NS)];   // node-ready slots owned by this wave (ring)
-  // One loop iteration pushes at most 128 slots (results of the last pass + lanes leaving the node loop).
+  // One loop iteration pushes at most 128 slots (results of the last pass + lanes leaving the node loop) to the rings below.  (SWITCH: the ray
+  // switches finished at the top of an iteration are 64 more, all to one ring: qnode, which has room for every slot -- or, in a scene whose root
+  // is a leaf, qleaf, and then no lane ever walks the node loop, so none leaves it.)
   unsigned short qleaf[256];       // slots standing at a leaf, owned by this wave (ring; a pass runs at 64: < 64 + 128)
   unsigned short outbox[2][160];   // slots on their way to the pool's Q_SHADE / Q_GEN (flushed at 32: < 32 + 128)
 };
 
 typedef __attribute__((address_space(3))) int lds_int;
+typedef __attribute__((address_space(3))) volatile f4v lds_volatile_f4v;      // a 16-byte LDS store the compiler neither merges nor splits (packetkernel_body.h, SWITCH)
 
 // The LDS part is addressed through an address_space(3) pointer so that push/pop compile to
 // ds_write_b32/ds_read_b32 (a generic pointer makes the compiler merge the LDS and the HBM
@@ -219,22 +225,41 @@ constexpr bool kSlimKeepsAux = true;
 #else
 constexpr bool kSlimKeepsAux = false;
 #endif
+// SWITCH (round 22): where a packet's next ray is taken up when a ray ends in the NODE LOOP (a step that enters no child with an empty stack: an
+// unoccluded shadow ray, a miss).  false: the lane leaves the slot at kSwitchRef on the leaf ring and a whole leaf pass carries it, only to load
+// one ray row.  true: the leave handler requests that row itself, the load travels while the wave runs its next pass, and the top of the next
+// scheduler iteration puts the slot back on the wave's node ring; the leaf pass then holds no switch arm at all.  Slim kernels only: a switch
+// needs the plain flag-word store of AUX = false, and the twins and the general kernels stay what they were.  And of the slim kernels only the
+// two with NEAR = false: the row and the slot id are five vector registers alive through the Disney visit, which take the NEAR kernels two
+// registers past their twins (161 / 160 against 159 / 158; tests/test_packet_slim_cpu.py holds them to the twins' numbers), so those keep the hop.
+// -DPT_PK_SWITCH_LEAF (experiment build, profiles/r22_switch_ab.txt): the slim kernels with the switch in the leaf pass, as before round 22.
+#ifdef PT_PK_SWITCH_LEAF
+constexpr bool kSlimSwitches = false;
+#else
+constexpr bool kSlimSwitches = true;
+#endif
+// -DPT_PK_SWITCH_ARM (experiment build): the leave handler switches, and the leaf pass keeps the arm nothing reaches -- the first step alone.
+#ifdef PT_PK_SWITCH_ARM
+constexpr bool kLeafKeepsSwitchArm = true;
+#else
+constexpr bool kLeafKeepsSwitchArm = false;
+#endif
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(const LaunchArgs a) {
   constexpr int F = 0;
-  constexpr bool AUX = kSlimKeepsAux, GLASS = NEAR || kSlimKeepsGlass;
+  constexpr bool AUX = kSlimKeepsAux, GLASS = NEAR || kSlimKeepsGlass, SWITCH = kSlimSwitches && !kSlimKeepsAux && !NEAR;
 #include "packetkernel_body.h"
 }
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_aux(const LaunchArgs a) {
   constexpr int F = 0;
-  constexpr bool AUX = true, GLASS = true;
+  constexpr bool AUX = true, GLASS = true, SWITCH = false;
 #include "packetkernel_body.h"
 }
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_general(const LaunchArgs a) {
   constexpr int F = FEAT_ALL;
-  constexpr bool AUX = true, GLASS = true;
+  constexpr bool AUX = true, GLASS = true, SWITCH = false;
 #include "packetkernel_body.h"
 }
 

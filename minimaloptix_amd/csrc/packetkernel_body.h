@@ -5,7 +5,10 @@
 // AUX = false: no borrowed slots (the launch runs with LaunchArgs::auxDepth 0); GLASS = false: the scene has no Disney GLASS material, a
 // shadow ray's attenuation is (1,1,1) or (0,0,0) and never a tinted row.  Both only take code away that such a launch cannot reach.
 // (GLASS stops at the rows: the Disney program keeps its glass arm, packetkernel.hip says why.)
+// SWITCH = true: a ray that ends in the node loop while its packet holds another one is switched by the leave handler of the scheduler loop (the
+// row load travels through the next pass) and never reaches the leaf pass at kSwitchRef; packetkernel.hip says which kernels have it.
   static_assert(GLASS || !NEAR, "a scene whose shadow rays keep their nearest candidate has a Disney GLASS material");
+  static_assert(!SWITCH || !AUX, "the ray switch of the leave handler writes the flag word with a plain store");
   constexpr int NS = SHARED ? kP * kWaves : kP;          // slots per pool
   __shared__ PoolLds<NS> sPool[SHARED ? 1 : kWaves];
   __shared__ WavePriv<NS> sPriv[kWaves];
@@ -169,6 +172,11 @@
   ntv.node = kTravDone; ntv.sp = 0; ntv.tbest = 0; ntv.inv = mk3(0, 0, 0); ntv.noi = mk3(0, 0, 0); ntv.bestPrim = -1; ntv.bestTri = -1;
   ntv.beta = 0; ntv.gamma = 0; ntv.att = mk3(1, 1, 1); ntv.started = 1;
 
+  // SWITCH: the ray switch a lane began when it left the node loop (leave handler), finished at the top of the next iteration: the slot (-1 = none)
+  // and the packet's next ray (SlotCold::ray[cur]), whose load is in flight in between
+  [[maybe_unused]] int swSlot = -1;
+  [[maybe_unused]] f4v swRow = { 0.f, 0.f, 0.f, 0.f };
+
   // result of the last pass, queued inside the next transaction
   int pendSlot = -1, pendDest = DEST_NONE;
 
@@ -223,7 +231,9 @@
       const v4 na = W.nodeA[slot], nb = W.nodeB[slot];
       const int fl = W.stack[slot][0];
       const int node0 = f2i(nb.w);
-      const bool isSwitch = node0 == kSwitchRef;
+      // SWITCH: no slot comes here at kSwitchRef, and the arm (dummy leaf reference, row load, the branch round the triangle tests) is compiled out
+      bool isSwitch = false;
+      if constexpr (!SWITCH || kLeafKeepsSwitchArm) isSwitch = node0 == kSwitchRef;
       const bool shadow = (fl & kShadowRay) != 0, hitValid = (fl & kHitValid) != 0;
       const int cur = fl_cur(fl);
       const SlotCold* cs = at32(cold, slot);
@@ -540,6 +550,23 @@
   unsigned int guard = 0;
   const unsigned long long wdStart = __builtin_amdgcn_s_memrealtime();
   for (;;) {
+    // SWITCH: the ray switches the last iteration's leave handler began are finished first -- what the leaf pass's next_ray does, with the row
+    // that has travelled through the pass in between (which waited for its own, later, loads).  In front of the watchdog on purpose: no switch is
+    // ever pending where the loop is left, the slot of one is back on a ring like every other slot.
+    if constexpr (SWITCH) {
+      const unsigned long long m = __ballot(swSlot >= 0);
+      if (m != 0ull) {
+        if (swSlot >= 0) {
+          // the row goes to LDS as it was loaded and the root reference over its fourth word (same wave, same address: LDS keeps the order).
+          // Written as one (x, y, z, root) vector, the compiler gathered that vector in the leave handler, behind a wait for the load.
+          *(lds_volatile_f4v*)&W.nodeB[swSlot] = swRow;
+          W.nodeB[swSlot].w = i2f(sc.rootRef);
+          W.nodeA[swSlot].w = swRow.w;
+        }
+        local_push(swSlot >= 0 ? (sc.rootRef >= 0 ? Q_NODE : Q_LEAF) : DEST_NONE, swSlot);
+        swSlot = -1;
+      }
+    }
     // bounded in wall-clock time (never hang the GPU): checked every 4096 iterations
     if ((++guard & 4095u) == 0u && __builtin_amdgcn_s_memrealtime() - wdStart > a.watchdogTicks) { if (lane == 0) atomicOr(a.workCounter + 1, 1); break; }
     PT_SUB0(); if (CNT) nIter++;
@@ -549,8 +576,25 @@
       const bool leave = ns >= 0 && !(ntv.node >= 0 && ntv.node != kTravDone);
       if (__ballot(leave) != 0ull) {
         int dest = DEST_NONE, pushSlot = ns;
-        if (leave) {
-          const int nodeOut = (ntv.node == kTravDone && fl_more(nsFlag)) ? kSwitchRef : ntv.node;   // ray done, packet not: the leaf pass switches rays
+        // SWITCH: ray done, packet not -- the lane asks for the packet's next ray itself and pushes nothing; the top of the next iteration finishes it
+        bool sw = false;
+        if constexpr (SWITCH) {
+          sw = leave && ntv.node == kTravDone && fl_more(nsFlag);
+          if (__ballot(sw) != 0ull) {
+            // the row was written by another lane of this wave in an earlier batch, or published by another wave: ordered as in leaf_pass
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (sw) {
+              const int cur = fl_cur(nsFlag);
+              swRow = slot_load(reinterpret_cast<const f4v*>(&at32(cold, ns)->ray[cur])); swSlot = ns;
+              // the new flag word is written here already (no register carries it): the slot is in no ring, nobody reads the word before the
+              // switch is finished.  nsFlag holds no stack pointer: the word is the one next_ray writes.
+              W.stack[ns][0] = (nsFlag & ~((3 << kCurShift) | kShadowRay)) | ((cur + 1) << kCurShift) | (cur + 1 < fl_nsh(nsFlag) ? kShadowRay : 0);
+            }
+          }
+        }
+        if (leave && !sw) {
+          const int nodeOut = (!SWITCH && ntv.node == kTravDone && fl_more(nsFlag)) ? kSwitchRef : ntv.node;   // ray done, packet not: the leaf pass switches rays
           W.nodeB[ns].w = i2f(nodeOut); store_flags(ns, ntv.sp | nsFlag);
           dest = (nodeOut == kTravDone) ? ((nsFlag & kShadeFlag) ? Q_SHADE : Q_GEN) : Q_LEAF;   // a lane leaves at a leaf, at a ray switch or finished
           if constexpr (AUX) {
@@ -587,6 +631,9 @@
     }
     const int nActive = __popcll(__ballot(ns >= 0));
     const bool starving = nActive <= 64 - a.starveLanes;
+    // lanes with work in flight: a pending ray switch (SWITCH) is a slot in no ring, so a wave that holds one neither idles nor leaves the loop
+    int nBusy = nActive;
+    if constexpr (SWITCH) nBusy += __popcll(__ballot(swSlot >= 0));
     int pass = -1;      // -1 node loop, 0 leaf, 1 shade, 2 gen, 3 idle, 4 exit
     int mySlot = -1;
     auto leaf_pop = [&]() -> int {              // up to 64 slots from this wave's own leaf ring
@@ -623,9 +670,9 @@
         // walked to the end of their packets; once every path that is left waits in one of the two queues the workgroup leaves the loop and
         // hands them to the drain kernel (after the loop: hand-over).  Only this branch knows about it -- the pass selection of a full pool
         // is what it was.
-        if (nDone >= W.drainAt) { if (nDone + sh + g == NS && nActive == 0 && l == 0) pass = 4; sh = 0; g = 0; }
+        if (nDone >= W.drainAt) { if (nDone + sh + g == NS && nBusy == 0 && l == 0) pass = 4; sh = 0; g = 0; }
         if (pass != 4) {
-          if (l + sh + g == 0) { if (nActive == 0) pass = (nDone == NS) ? 4 : 3; }
+          if (l + sh + g == 0) { if (nBusy == 0) pass = (nDone == NS) ? 4 : 3; }
           else pass = (l >= sh && l >= g) ? 0 : (sh >= g ? 1 : 2);
         }
       }
