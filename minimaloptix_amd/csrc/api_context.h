@@ -337,12 +337,11 @@ int denoise_begin(moptix_context c, bool ownGuide, size_t& px);
 void denoise_consts(moptix_context c, const moptix_denoise_params* p, DenoiseConsts& k);
 inline float* denoise_out(moptix_context c) { return c->dn.bound ? c->dn.bound : c->dn.out.p; }
 
-// ---- the launch plan (api_render.hip): what one batch of launches will run, decided from the context and the batch size alone ----
+// ---- the launch plan (api_render.hip): what one batch of launches will run, decided from the context, the batch size and whether it counts ----
 struct LaunchPlan {
   const TraceKernel* kernel;      // kPacketKernel, kQueueKernel, kLeanQueueKernel, or null = the per-lane megakernel (launch_megakernel)
   int variant;                    // the same as get_option "kernel_variant_used" reports it: 4, 3, 0
-  int features;                   // FEAT_* programs the trace kernel must contain (FEAT_ALL: no specialised build asked for)
-  bool slim;                      // variant 4: no borrowed slots (auxDepth 0) and no Disney GLASS where shadow rays do not keep their nearest candidate: a lean launch runs the slim build
+  PacketBuild build;              // variant 4: the build of the packet kernel the launches run (megakernel.h packet_build); General for every other kernel
   int nItems, tilesX;             // pixel slots of this rank (local tiles * 64); 8x8 tiles per row of the frame
   int nBlocks;
   long long perPass;              // launches per pass, before the out-of-memory halving of the per-sample buffer

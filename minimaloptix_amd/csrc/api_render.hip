@@ -126,10 +126,10 @@ int read_stats(moptix_context c, moptix_stats* stats) {
   return MOPTIX_OK;
 }
 
-// ---- the launch plan: what one batch of launches will run, decided from the context and the batch size alone --------------------------
+// ---- the launch plan: what one batch of launches will run, decided from the context, the batch size and whether it counts ------------
 // plan_launch touches neither the device nor the context's buffers; prepare_launch allocates what the plan (api_context.h LaunchPlan) asks
 // for and launch_pass launches it.  byPixelSlots: the plan of an adaptive pass (api_adaptive.hip).
-int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool byPixelSlots, LaunchPlan& p) {
+int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool counted, bool byPixelSlots, LaunchPlan& p) {
   memset(&p, 0, sizeof(p));
   const int tilesX = ((int)c->params.width + 7) / 8, tilesY = ((int)c->params.height + 7) / 8;
   const long long nTiles = (long long)tilesX * tilesY;
@@ -174,7 +174,7 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
   // (its hit records, pt_types.h TriFace, are addressed by a 32-bit byte offset from the TriShade array they follow: where the two arrays together reach
   // 4 GB -- above 38 million triangles -- the scene runs the general build)
   const bool faceTableOk = (unsigned long long)tri_face_offset(0) + (unsigned long long)scene.nTris * (sizeof(TriShade) + sizeof(TriFace)) + 64ull < (1ull << 32);
-  p.features = (usePacket && c->opt.specialize != 0 && faceTableOk) ? scene_features(c) : FEAT_ALL;
+  const int features = (usePacket && c->opt.specialize != 0 && faceTableOk) ? scene_features(c) : FEAT_ALL;
   // no tree to walk (queuekernel_lean.hip): a fourth workgroup per CU instead of path slots and stack entries
   if (p.kernel == &kLeanQueueKernel && c->opt.blocksPerCU == 3) p.nBlocks = c->numCUs * 4;
   // Slots without a path are what deep paths borrow for their shadow rays (packetkernel.hip, "aux_depth"); once the work
@@ -198,9 +198,10 @@ int plan_launch(moptix_context c, const SceneView& scene, int32_t nSeeds, bool b
     p.drainBelow = (glassMaterial && !scene.shadowNearest) ? 0 : c->opt.drainBelow;
     // The slim build of the lean kernel (packetkernel.hip: AUX = false, GLASS = NEAR) holds no borrowed-slot machinery and, where shadow rays do not keep
     // their nearest candidate, no Disney GLASS code: a lean launch runs it when it borrows no slot and the material TABLE has no Disney GLASS entry
-    // (glass under "shadow_rule" 0 has shadowNearest false and tinted attenuations: the NEAR = false slim kernel is not for it).  Whether the launch is
-    // lean is known with its counting / fast_shading mode (prepare_launch, the launcher); same image bits in every build.
-    p.slim = p.auxDepth == 0 && (scene.shadowNearest || !glassMaterial);
+    // (glass under "shadow_rule" 0 has shadowNearest false and tinted attenuations: the NEAR = false slim kernel is not for it).  Same image bits
+    // in every build.
+    const bool slimEligible = p.auxDepth == 0 && (scene.shadowNearest || !glassMaterial);
+    p.build = packet_build(counted, c->opt.fastShading != 0, features, slimEligible);
   }
   if (p.kernel) {
     p.ovfDepth = hasTris ? std::max(0, c->bvh.stackBound - p.kernel->lds_stack_entries() + 1) : 0;
@@ -261,11 +262,11 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
   LaunchPlan& p = r.p;
   memset(&a, 0, sizeof(a));
   fill_view(c, a.scene);
-  if ((rc = plan_launch(c, a.scene, nSeeds, byPixelSlots, p)) != MOPTIX_OK || p.nItems == 0) return rc;
+  if ((rc = plan_launch(c, a.scene, nSeeds, counted, byPixelSlots, p)) != MOPTIX_OK || p.nItems == 0) return rc;
   c->lastVariant = p.variant;
   r.counted = counted; r.fast = c->opt.fastShading != 0;
-  c->lastFeatures = p.kernel == &kPacketKernel ? packetkernel_features(r.counted, r.fast, p.features) : FEAT_ALL;
-  c->lastSlim = (p.kernel == &kPacketKernel && c->lastFeatures == 0 && p.slim) ? 1 : 0;
+  c->lastFeatures = p.build == PacketBuild::General ? FEAT_ALL : 0;
+  c->lastSlim = p.build == PacketBuild::Slim ? 1 : 0;
 
   // ---- what the plan asks for ----
   a.accum = accum_ptr(c);
@@ -362,7 +363,7 @@ int launch_pass(moptix_context c, RenderLaunch& r, const int* dSeeds, int n, con
   if (over) a.tileOrder = over->order;
   else if (a.tileMajor && a.tileCost) HIPCHK(c, c->tiles.sort(c->stream), "sort tiles");      // deepest path seen so far first, ties in raster order
   HIPCHK(c, hipEventRecord(c->ev0, c->stream), "event");
-  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast, p.features, p.slim), p.kernel->launchWhat);
+  if (p.kernel) HIPCHK(c, p.kernel->launch(c->stream, a, p.nBlocks, r.counted, r.fast, p.build), p.kernel->launchWhat);
   else HIPCHK(c, launch_megakernel(c->stream, a, p.nBlocks, r.counted), "launch megakernel");
   if (p.drainBelow > 0) HIPCHK(c, launch_drainkernel(c->stream, a, c->numCUs, r.counted, r.fast), "launch drain kernel");
   // Since the drain kernel came, a packet launch WITHOUT it ("drain_below" 0) has been followed by the per-lane megakernel: it finds the work counter

@@ -151,6 +151,17 @@ __device__ __forceinline__ void store_sample(const LaunchArgs& a, int item, v3 v
 }
 #endif
 
+// Which build of the packet kernel (packetkernel.hip) a launch runs.  General: every FEAT_* program (pt_types.h), counting and fast shading.
+// Aux and Slim are the lean builds -- no optional program, uncounted, exact shading -- with borrowed slots and glass (Aux) or without (Slim).
+// sceneFeatures: the FEAT_* programs the scene can reach, from the host's tables (api_core.hip scene_features; FEAT_ALL = do not specialise).
+// slimEligible: the plan rules out borrowed slots (LaunchArgs::auxDepth == 0) and, for a scene whose shadow rays do not keep their nearest
+// candidate, a Disney GLASS material.  Neither is a kernel argument: sixteen bytes of arguments cost the packet kernel 0.8 % (the drain list, above).
+enum class PacketBuild { General, Aux, Slim };      // General = 0: what a zeroed LaunchPlan holds, and what every other trace kernel is handed
+inline PacketBuild packet_build(bool counted, bool fastShading, int sceneFeatures, bool slimEligible) {
+  if (counted || fastShading || sceneFeatures != 0) return PacketBuild::General;
+  return slimEligible ? PacketBuild::Slim : PacketBuild::Aux;
+}
+
 int megakernel_lds_stack_entries();
 hipError_t launch_reduce_samples(hipStream_t stream, const LaunchArgs& a);
 hipError_t launch_megakernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted);
@@ -158,24 +169,18 @@ int queuekernel_lds_stack_entries();
 int queuekernel_slots();
 size_t queuekernel_cold_bytes(int nBlocks);
 size_t queuekernel_overflow_ints(int nBlocks, int ovfDepth);
-hipError_t launch_queuekernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);
+hipError_t launch_queuekernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild);
 // queuekernel_lean.hip: the same kernel with four workgroups per CU, for scenes without triangles
 int queuekernel_lds_stack_entries_lean();
 int queuekernel_slots_lean();
 size_t queuekernel_cold_bytes_lean(int nBlocks);
 size_t queuekernel_overflow_ints_lean(int nBlocks, int ovfDepth);
-hipError_t launch_queuekernel_lean(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);
+hipError_t launch_queuekernel_lean(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild);
 int packetkernel_lds_stack_entries();
 int packetkernel_slots();             // path slots per workgroup (variant 4)
 size_t packetkernel_cold_bytes(int nBlocks);
 size_t packetkernel_overflow_ints(int nBlocks, int ovfDepth);
-// features: the FEAT_* programs (pt_types.h) the scene can reach, from the host's tables (api_core.hip scene_features; FEAT_ALL = do not
-// specialise).  A kernel argument would have been simpler and is not an option: sixteen bytes of arguments cost the packet kernel 0.8 %
-// (the drain list, above).  packetkernel_features: the mask compiled into the kernel such a launch runs.
-// slim: the plan rules out borrowed slots (a.auxDepth == 0) and, for a scene whose shadow rays do not keep their nearest candidate, a Disney
-// GLASS material: a lean launch then runs the build without either (packetkernel.hip AUX, GLASS).  An argument for the same reason.
-hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);
-int packetkernel_features(bool counted, bool fastShading, int sceneFeatures);
+hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild build);      // build: packet_build of the same counted, fastShading
 // What the launch plan (api_render.hip) asks of a trace kernel that keeps its paths in slots: the stack entries a slot has in LDS, the bytes of
 // slot records and the ints of stack overflow that nBlocks workgroups need, and the launch itself.  (launch_megakernel has no slots and sizes
 // its overflow area per thread: it stays a special case there.)
@@ -184,7 +189,7 @@ struct TraceKernel {
   int (*lds_stack_entries)();
   size_t (*cold_bytes)(int nBlocks);
   size_t (*overflow_ints)(int nBlocks, int ovfDepth);
-  hipError_t (*launch)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);      // features, slim: the packet kernel's alone
+  hipError_t (*launch)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild build);      // build: the packet kernel's alone
 };
 inline constexpr TraceKernel kQueueKernel = { "launch queue megakernel", queuekernel_lds_stack_entries, queuekernel_cold_bytes, queuekernel_overflow_ints, launch_queuekernel };
 inline constexpr TraceKernel kLeanQueueKernel = { "launch queue megakernel (lean)", queuekernel_lds_stack_entries_lean, queuekernel_cold_bytes_lean, queuekernel_overflow_ints_lean, launch_queuekernel_lean };

@@ -1,6 +1,6 @@
 // packetkernel.hip -- megakernel variant 4: the scheduler of variant 3 (queuekernel.hip: path slots with their traversal
 // state in LDS, node / leaf / shade / gen queues shared by the workgroup, lanes as workers) around the PER-BOUNCE state
-// machine of pt_packet.h.
+// machine of pt_packet.h.  What the two schedulers declare alike (workgroup shape, queue ids, wave rings, slot stack, fresh_args) is in pt_sched.h.
 //
 // Variant 3 gives every ray its own shading visit: a Disney hit with three facing lights is four trips through the
 // shade queue, four slot-record round trips and four traversal set-ups, one after the other.  Here a visit does all of a
@@ -44,14 +44,13 @@
 #include "pt_lanestack.h"
 #include "pt_path.h"
 #include "pt_packet.h"
+#include "pt_sched.h"
 #include "pt_slot.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = 256;
-constexpr int kWaves = kBlockThreads / 64;
 // Path slots per wave and LDS stack entries per slot: what a workgroup's third of the CU's LDS (53,760 bytes for three workgroups:
 // 42 blocks of 1,280; a 54,128-byte build ran two per CU) is spent on.  A slot costs 32 B of ray + 4 (entries + 1) B of stack + 12 B of ring space.  Measured on
 // coffee at 64 spp, same bits (profiles/r04_slots.txt): 512 slots x 11 entries 95.3 ms, 544 x 10 93.8, 576 x 9 93.3, 608 x 8 93.9,
@@ -72,15 +71,10 @@ constexpr int kStackN = PT_STACKN;      // LDS stack entries per slot; deeper le
 constexpr int kWavesPerSimd = PT_WAVES_PER_SIMD;   // occupancy target: 3 workgroups per CU (VGPR <= 168, LDS <= 53 KB)
 // Rings hold exactly NS entries (a slot sits in at most one ring): sized to the next power of two they would cost 640 -> 1024
 // entries each and the workgroup its third of the CU's LDS.  An index is head + count + rank < 2 NS: one conditional subtract.
-constexpr int ring_capacity(int n) { return n; }
 template <int NS> __device__ __forceinline__ int ring_wrap(int i) {
   if constexpr ((NS & (NS - 1)) == 0) return i & (NS - 1); else return i >= NS ? i - NS : i;
 }
 static_assert(PT_KP * kWaves <= (1 << kSlotBits), "slot ids are 10 bits");
-
-
-// pool-wide queues first (they index PoolLds::queue); Q_NODE / Q_LEAF are per-wave rings (WavePriv)
-enum { Q_SHADE = 0, Q_GEN = 1, kNumQ = 2, Q_NODE = 2, Q_LEAF = 3, DEST_DONE = 4, DEST_NONE = -1 };
 
 // LDS image of NS slots
 template <int NS>
@@ -89,9 +83,9 @@ struct PoolLds {
   v4 nodeA[NS];           // o.xyz, tbest
   v4 nodeB[NS];           // d.xyz, node (int bits); a lane that picks the slot up for the node loop derives 1/d from it
   int stack[NS][kStackN + 1];   // [0] = sp | packet description (see the flag bits below), [1..] = entries
-  unsigned short queue[kNumQ][ring_capacity(NS)];
-  int qHead[kNumQ], qCount[kNumQ];   // SHARED only
-  int done, lock;                    // SHARED only
+  unsigned short queue[kNumQ][NS];
+  int qHead[kNumQ], qCount[kNumQ];
+  int done, lock;
   int drainAt;                       // once this many slots are done the pool stops shading and hands its last paths to the drain kernel (set at start-up)
   // Concurrent shadow rays for deep paths (LaunchArgs::auxDepth): a slot whose path is done (the work items ran out, or
   // LaunchArgs::slotsInUse left it without one) can be borrowed by a deep path, one per shadow ray of a hit, so that
@@ -101,62 +95,9 @@ struct PoolLds {
   int nFree;                         // set bits in freeMask (approximate: read without the lock)
 };
 
-template <int NS>
-struct WavePriv {
-  unsigned short qnode[ring_capacity(NS)];   // node-ready slots owned by this wave (ring)
-  // One loop iteration pushes at most 128 slots (results of the last pass + lanes leaving the node loop) to the rings below.  (SWITCH: the ray
-  // switches finished at the top of an iteration are 64 more, all to one ring: qnode, which has room for every slot -- or, in a scene whose root
-  // is a leaf, qleaf, and then no lane ever walks the node loop, so none leaves it.)
-  unsigned short qleaf[256];       // slots standing at a leaf, owned by this wave (ring; a pass runs at 64: < 64 + 128)
-  unsigned short outbox[2][160];   // slots on their way to the pool's Q_SHADE / Q_GEN (flushed at 32: < 32 + 128)
-};
-
-typedef __attribute__((address_space(3))) int lds_int;
 typedef __attribute__((address_space(3))) volatile f4v lds_volatile_f4v;      // a 16-byte LDS store the compiler neither merges nor splits (packetkernel_body.h, SWITCH)
 
-// The LDS part is addressed through an address_space(3) pointer so that push/pop compile to
-// ds_write_b32/ds_read_b32 (a generic pointer makes the compiler merge the LDS and the HBM
-// overflow path into one flat_load).
-struct SlotStack {
-  lds_int* lds;           // &stack[slot][1]
-  int* ovf;               // this slot's overflow area in HBM (or nullptr)
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (__builtin_expect(sp < kStackN, 1)) lds[sp] = v; else ovf[sp - kStackN] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    int v;
-    if (__builtin_expect(sp < kStackN, 1)) v = lds[sp]; else v = ovf[sp - kStackN];
-    return v;
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kStackN; }     // three pushes stay in LDS
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp] = v; }
-  // pt_path.h node_step_nearfar's branch-free tail: m pushes on top of sp entries stay in LDS and entry sp exists (the dead
-  // store of a step that enters nothing lands there); the entry a pop would take (sp - 1; for sp = 0 the slot's flag word, unused)
-  static constexpr bool kFlat = true;
-  __device__ __forceinline__ bool fits_fast(int sp, int m) const { return sp + m <= kStackN && sp < kStackN; }
-  __device__ __forceinline__ int peek_fast(int sp) const { return lds[min(sp, kStackN) - 1]; }
-};
-
-// The launch arguments again, read from the kernel-argument segment through a pointer the compiler cannot see through.
-// The kernel is one loop; whatever it reads from its arguments is loop-invariant, so the compiler loads ALL of it in front
-// of the loop and keeps it in scalar registers for the whole launch: camera (19 words), background, a dozen table pointers,
-// the hand-out parameters -- about 100 words against 102 registers, and the rest of the kernel's scalar state (queue heads,
-// exec masks of the scheduler) then lives in lanes of a spill VGPR, one v_readlane / v_writelane (4.4 clocks of the vector
-// pipe each, tools/micro/valu_issue.hip) per access: 111 spilled scalar registers in round 3.  A pass that needs the scene
-// (shading batch, leaf pass) therefore takes its own copy here: s_load where the value is used, dead when the pass ends,
-// and only what the node loop and the scheduler need stays resident.
-__device__ __forceinline__ const LaunchArgs& fresh_args() {
-  typedef __attribute__((address_space(4))) const LaunchArgs CA;
-  unsigned long long p = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const LaunchArgs*)(CA*)p;
-}
-
-// destination queue of a slot after a traversal step / a ray set-up
-__device__ __forceinline__ int route(int node, int kind, int bestPrim) {
-  if (node == kTravDone) return (kind == RK_SHADOW || bestPrim >= 0) ? Q_SHADE : Q_GEN;
-  return node >= 0 ? Q_NODE : Q_LEAF;
-}
+using SlotStack = LdsStack<kStackN, true>;      // pt_path.h node_step_nearfar: this stack takes the branch-free tail
 
 // pt_packet.h's sink for the shadow rays of a new packet: each goes to the slot as soon as it is known (weight row; the ray
 // itself to LDS if it is the first of the list, else to its ray row) -- or, for a deep path that has borrowed slots, each
@@ -204,7 +145,7 @@ struct OwnSlotSink {
 // tinted `att` rows in the leaf pass and the batch load, no material id kept per leaf triangle.  A NEAR kernel always has GLASS.
 // The Disney program's glass arm (pt_path.h on_result -> glass_body) STAYS in every build: compiled out as well, the timed kernel took all
 // 168 vector registers and 28 spilled scalar ones (with it: 148 and 21; its twin: 159 and 25) for 0.85 ms of a 291 ms frame, which is
-// no gain by the project's rule (profiles/r21_slim_ab.txt), and tests/test_packet_slim_cpu.py holds the slim kernels to their twins' numbers.
+// no gain by the project's rule (profiles/r21_slim_ab.txt), and tests/test_packet_resources_cpu.py holds the slim kernels to their twins' numbers.
 //
 // Three __global__ templates, one body.  The SLIM kernel (no FEAT_* bit, AUX = false, GLASS = NEAR: what the benchmark frame runs) keeps the
 // name the kernel has had since round 3 -- the profiles, tools/kernel_resources.py listings and the resource pin of the timed instantiation
@@ -231,7 +172,7 @@ constexpr bool kSlimKeepsAux = false;
 // scheduler iteration puts the slot back on the wave's node ring; the leaf pass then holds no switch arm at all.  Slim kernels only: a switch
 // needs the plain flag-word store of AUX = false, and the twins and the general kernels stay what they were.  And of the slim kernels only the
 // two with NEAR = false: the row and the slot id are five vector registers alive through the Disney visit, which take the NEAR kernels two
-// registers past their twins (161 / 160 against 159 / 158; tests/test_packet_slim_cpu.py holds them to the twins' numbers), so those keep the hop.
+// registers past their twins (161 / 160 against 159 / 158; tests/test_packet_resources_cpu.py holds them to the twins' numbers), so those keep the hop.
 // -DPT_PK_SWITCH_LEAF (experiment build, profiles/r22_switch_ab.txt): the slim kernels with the switch in the leaf pass, as before round 22.
 #ifdef PT_PK_SWITCH_LEAF
 constexpr bool kSlimSwitches = false;
@@ -270,10 +211,9 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_
 // scheduling strategy is a per-file flag (Makefile), "max-ilp" is 0.85 % faster than the default on the 64-byte kernels (coffee 312.5 -> 309.9 ms,
 // glass knot -1.5 %) and 2-4 % SLOWER on the 128-byte ones (dining room) and on the queue kernels (random spheres) -- measured, round 6.
 #ifndef PT_PK_N128
-// Three builds exist per node format and shadow rule: every program (FEAT_ALL) and none of the optional ones (0), the latter uncounted and
-// with exact shading only, with borrowed slots and glass (_aux) or without (the slim build).  A scene that needs any one of the programs runs
-// the general build.
-int packetkernel_features(bool counted, bool fastShading, int sceneFeatures) { return (counted || fastShading || sceneFeatures != 0) ? FEAT_ALL : 0; }
+// Three builds exist per node format and shadow rule (megakernel.h PacketBuild): every program (FEAT_ALL) and none of the optional ones (0), the
+// latter uncounted and with exact shading only, with borrowed slots and glass (_aux) or without (the slim build).  A scene that needs any one
+// of the programs runs the general build.
 int packetkernel_lds_stack_entries() { return kStackN; }
 int packetkernel_slots() { return kP * kWaves; }
 size_t packetkernel_cold_bytes(int nBlocks) { return (size_t)nBlocks * kWaves * kP * sizeof(SlotCold); }
@@ -290,24 +230,30 @@ static void launch_pk(dim3 grid, dim3 block, hipStream_t stream, const LaunchArg
   if (a.scene.shadowNearest) pt_packetkernel_general<CNT, true, FAST, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
   else                       pt_packetkernel_general<CNT, true, FAST, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
 }
-hipError_t PT_PK_LAUNCH(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim) {
+hipError_t PT_PK_LAUNCH(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild build) {
   dim3 grid(nBlocks), block(kBlockThreads);
-  if (packetkernel_features(counted, fastShading, features) == 0 && slim) {      // the slim build: lean, and the plan rules borrowed slots and (NEAR = false) glass out
+  switch (build) {
+  case PacketBuild::Slim:      // lean, and the plan rules borrowed slots and (NEAR = false) glass out
     if (a.auxDepth != 0 && !kSlimKeepsAux) return hipErrorInvalidValue;                           // (the kernel would ignore it: the plan never asks for this)
     if (a.scene.shadowNearest) pt_packetkernel<false, true, false, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
     else                       pt_packetkernel<false, true, false, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
-  } else if (packetkernel_features(counted, fastShading, features) == 0) {      // the lean build: uncounted, exact shading
+    break;
+  case PacketBuild::Aux:       // lean: uncounted, exact shading
     if (a.scene.shadowNearest) pt_packetkernel_aux<false, true, false, true, kThisFileN64><<<grid, block, 0, stream>>>(a);
     else                       pt_packetkernel_aux<false, true, false, false, kThisFileN64><<<grid, block, 0, stream>>>(a);
-  } else if (fastShading) { if (counted) launch_pk<true, true>(grid, block, stream, a); else launch_pk<false, true>(grid, block, stream, a); }
-  else             { if (counted) launch_pk<true, false>(grid, block, stream, a); else launch_pk<false, false>(grid, block, stream, a); }
+    break;
+  case PacketBuild::General:
+    if (fastShading) { if (counted) launch_pk<true, true>(grid, block, stream, a); else launch_pk<false, true>(grid, block, stream, a); }
+    else             { if (counted) launch_pk<true, false>(grid, block, stream, a); else launch_pk<false, false>(grid, block, stream, a); }
+    break;
+  }
   return hipGetLastError();
 }
 #ifndef PT_PK_N128
-hipError_t launch_packetkernel_n128(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim);
-hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int features, bool slim) {
+hipError_t launch_packetkernel_n128(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild build);
+hipError_t launch_packetkernel(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild build) {
   // api_core.hip fill_view: the option node_format decides whether the scene view carries the 64-byte nodes
-  return a.scene.nodes64 != nullptr ? launch_packetkernel_n64(stream, a, nBlocks, counted, fastShading, features, slim) : launch_packetkernel_n128(stream, a, nBlocks, counted, fastShading, features, slim);
+  return a.scene.nodes64 != nullptr ? launch_packetkernel_n64(stream, a, nBlocks, counted, fastShading, build) : launch_packetkernel_n128(stream, a, nBlocks, counted, fastShading, build);
 }
 #endif
 

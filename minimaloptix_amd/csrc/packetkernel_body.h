@@ -1,7 +1,7 @@
 // packetkernel_body.h -- the statements of the packet kernel (packetkernel.hip), included into its three __global__ templates
 // pt_packetkernel (F = 0, the slim build), pt_packetkernel_aux (F = 0) and pt_packetkernel_general (F = FEAT_ALL).  Not a header in its own
-// right: it sees the template parameters CNT, SHARED, FAST, NEAR, N64, the constants F, AUX, GLASS and the argument `a` of the kernel it is
-// included into, and everything packetkernel.hip declares in front of them.  packetkernel.hip says why this is an include and not a function.
+// right: it sees the template parameters CNT, FAST, NEAR, N64, the constants F, AUX, GLASS and the argument `a` of the kernel it is
+// included into, and everything packetkernel.hip and pt_sched.h declare in front of them.  packetkernel.hip says why this is an include and not a function.
 // AUX = false: no borrowed slots (the launch runs with LaunchArgs::auxDepth 0); GLASS = false: the scene has no Disney GLASS material, a
 // shadow ray's attenuation is (1,1,1) or (0,0,0) and never a tinted row.  Both only take code away that such a launch cannot reach.
 // (GLASS stops at the rows: the Disney program keeps its glass arm, packetkernel.hip says why.)
@@ -9,9 +9,10 @@
 // row load travels through the next pass) and never reaches the leaf pass at kSwitchRef; packetkernel.hip says which kernels have it.
   static_assert(GLASS || !NEAR, "a scene whose shadow rays keep their nearest candidate has a Disney GLASS material");
   static_assert(!SWITCH || !AUX, "the ray switch of the leave handler writes the flag word with a plain store");
-  constexpr int NS = SHARED ? kP * kWaves : kP;          // slots per pool
-  __shared__ PoolLds<NS> sPool[SHARED ? 1 : kWaves];
-  __shared__ WavePriv<NS> sPriv[kWaves];
+  static_assert(SHARED, "the workgroup's waves share one pool: per-wave pools are gone");      // the parameter is kept for the kernels' symbol names only
+  constexpr int NS = kP * kWaves;                        // slots per pool
+  __shared__ PoolLds<NS> sPool[1];                       // (an array of one, as in queuekernel.hip)
+  __shared__ WavePriv<NS> sPriv[kWaves];                 // rings sized exactly (packetkernel.hip ring_wrap)
   // -DPT_EVLOG (tools/gpu_lone_path.py EVLOG=1; not part of the product build): once a visit has seen a path deeper than 100 bounces, every
   // wave of that workgroup logs its passes with 100 MHz stamps -- the timeline of one capped path walking in an idle machine
 #ifdef PT_EVLOG
@@ -27,26 +28,18 @@
   scv.shadowNearest = NEAR ? 1 : 0;                 // compile-time constant from here on
   const SceneView& sc = scv;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  PoolLds<NS>& W = sPool[SHARED ? 0 : wave];
-  const int gpool = SHARED ? blockIdx.x : blockIdx.x * kWaves + wave;
+  PoolLds<NS>& W = sPool[0];
+  const int gpool = blockIdx.x;
   SlotCold* cold = reinterpret_cast<SlotCold*>(a.poolCold) + (size_t)gpool * NS;
   int* ovfBase = a.stackOverflow ? a.stackOverflow + (size_t)gpool * NS * a.ovfDepth : nullptr;
 
   // sub-phase clocks of the counting build
   unsigned long long tLocal = 0, tLock = 0, tTxn = 0, tIdle = 0, tBLoad = 0, tBRun = 0, tBStore = 0, nTxn = 0, nIter = 0;
   unsigned long long tSub = 0, nIterResult = 0, nIterLights = 0, nIterGen = 0, nodeRuns = 0, ringBacklog = 0, leafBacklog = 0;
-#define PT_SUB0() do { if (CNT) tSub = __builtin_amdgcn_s_memtime(); } while (0)
-#define PT_SUB(acc) do { if (CNT) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - tSub; tSub = now_; } } while (0)
-  // queue bookkeeping: registers (wave-uniform); with SHARED they mirror LDS inside a transaction
+  // queue bookkeeping: registers (wave-uniform) that mirror LDS inside a transaction
   int qHead[kNumQ] = { 0, 0 }, qCount[kNumQ] = { 0, 0 };
   int nDone = 0;
 
-  [[maybe_unused]] auto q_push = [&](int q, bool pred, int slot) {
-    const unsigned long long m = __ballot(pred);
-    if (m == 0ull) return;
-    if (pred) W.queue[q][ring_wrap<NS>(qHead[q] + qCount[q] + lane_rank(m))] = (unsigned short)slot;
-    qCount[q] += __popcll(m);
-  };
   auto q_pop = [&](int q, bool want) -> int {
     const unsigned long long m = __ballot(want);
     const int n = min((int)__popcll(m), qCount[q]);      // (int): min(long long, int) resolves to the double overload
@@ -57,26 +50,22 @@
     return slot;
   };
   auto txn_begin = [&]() {
-    if constexpr (SHARED) {
-      if (lane == 0) { while (atomicCAS(&W.lock, 0, 1) != 0) __builtin_amdgcn_s_sleep(1); }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      if (CNT) { (void)__builtin_amdgcn_readfirstlane(W.lock); PT_SUB(tLock); nTxn++; }
-      for (int q = 0; q < kNumQ; q++) {
-        qHead[q] = __builtin_amdgcn_readfirstlane(W.qHead[q]);
-        qCount[q] = __builtin_amdgcn_readfirstlane(W.qCount[q]);
-      }
-      nDone = __builtin_amdgcn_readfirstlane(W.done);
+    if (lane == 0) { while (atomicCAS(&W.lock, 0, 1) != 0) __builtin_amdgcn_s_sleep(1); }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (CNT) { (void)__builtin_amdgcn_readfirstlane(W.lock); PT_SUB(tLock); nTxn++; }
+    for (int q = 0; q < kNumQ; q++) {
+      qHead[q] = __builtin_amdgcn_readfirstlane(W.qHead[q]);
+      qCount[q] = __builtin_amdgcn_readfirstlane(W.qCount[q]);
     }
+    nDone = __builtin_amdgcn_readfirstlane(W.done);
   };
   auto txn_end = [&]() {
-    if constexpr (SHARED) {
-      if (lane == 0) {
-        for (int q = 0; q < kNumQ; q++) { W.qHead[q] = qHead[q]; W.qCount[q] = qCount[q]; }
-        W.done = nDone;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&W.lock, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (lane == 0) {
+      for (int q = 0; q < kNumQ; q++) { W.qHead[q] = qHead[q]; W.qCount[q] = qCount[q]; }
+      W.done = nDone;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(&W.lock, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   auto make_stack = [&](int slot) {
     SlotStack st;
@@ -116,39 +105,33 @@
   // about 70 us with all 512 slots of every pool, so a path that bounces to the depth cap (about 1000 dependent rays)
   // takes 70-90 ms however short the launch is.  A short launch (one rank's share of a multi-GPU frame) therefore
   // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, api_render.hip plan_launch).
-  [[maybe_unused]] const bool auxOn = SHARED && a.auxDepth > 0 && sc.rootRef >= 0;
-  const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? (SHARED ? a.slotsInUse : max(64, a.slotsInUse / kWaves)) : NS;
+  [[maybe_unused]] const bool auxOn = a.auxDepth > 0 && sc.rootRef >= 0;
+  const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? a.slotsInUse : NS;
   {
     if constexpr (AUX) {
-    if (SHARED && threadIdx.x < NS / 32) {      // slots without a path can be borrowed from the start
+    if (threadIdx.x < NS / 32) {      // slots without a path can be borrowed from the start
       const int lo = (int)threadIdx.x * 32;
       W.freeMask[threadIdx.x] = !auxOn || nUse >= lo + 32 ? 0u : (nUse <= lo ? ~0u : ~0u << (nUse - lo));
     }
     if (threadIdx.x == 0) W.nFree = auxOn ? NS - nUse : 0;
     }
-    const int first = SHARED ? threadIdx.x : lane, step = SHARED ? kBlockThreads : 64;
-    for (int s = first; s < nUse; s += step) {
+    for (int s = threadIdx.x; s < nUse; s += kBlockThreads) {
       i4 ctl; ctl.x = -1; ctl.y = 0; ctl.z = 0; ctl.w = M_NEW_PIXEL;     // item -1: whatever sample comes first is "new" (rows get written)
       cold[s].ctl = ctl;
       W.stack[s][0] = 0;
       W.queue[Q_GEN][s] = (unsigned short)s;
     }
-    if constexpr (SHARED) {
-      if (threadIdx.x == 0) {
-        for (int q = 0; q < kNumQ; q++) { W.qHead[q] = 0; W.qCount[q] = 0; }
-        W.qCount[Q_GEN] = nUse; const int below = a.workCounter[kDrainList + kDrainBelow];
-        // drainAt: "slots without a path" from which on the pool hands over.  Slots that never carried a path (NS - nUse) are in that count from the
-        // start, so the threshold is at least one above it: a slot only joins the count when it has found the work counter exhausted, and a pool
-        // must never stop shading while work items are left (slots_in_use <= drain_below would otherwise drain from the first transaction on,
-        // with most of the launch's items unrendered -- found by the option fuzzer, seed 103 case 252)
-        W.done = NS - nUse; W.drainAt = below > 0 ? max(NS - below, NS - nUse + 1) : 0x7fff; W.lock = 0;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-    } else {
-      qCount[Q_GEN] = nUse; nDone = NS - nUse;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (threadIdx.x == 0) {
+      for (int q = 0; q < kNumQ; q++) { W.qHead[q] = 0; W.qCount[q] = 0; }
+      W.qCount[Q_GEN] = nUse; const int below = a.workCounter[kDrainList + kDrainBelow];
+      // drainAt: "slots without a path" from which on the pool hands over.  Slots that never carried a path (NS - nUse) are in that count from the
+      // start, so the threshold is at least one above it: a slot only joins the count when it has found the work counter exhausted, and a pool
+      // must never stop shading while work items are left (slots_in_use <= drain_below would otherwise drain from the first transaction on,
+      // with most of the launch's items unrendered -- found by the option fuzzer, seed 103 case 252)
+      W.done = NS - nUse; W.drainAt = below > 0 ? max(NS - below, NS - nUse + 1) : 0x7fff; W.lock = 0;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
   }
 
   Counters ct = {};
@@ -160,7 +143,6 @@
   unsigned long long tBatch = 0, tSwap = 0, tNode = 0, tLeaf = 0, tStamp = 0;
   const unsigned long long tStart = CNT ? __builtin_amdgcn_s_memtime() : 0ull;
   [[maybe_unused]] const unsigned long long rtStart = CNT ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#define PT_STAMP(acc) do { if (CNT) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - tStamp; tStamp = now_; } } while (0)
   tStamp = tStart;
 
   // ---- node-loop worker context: the only per-lane state that survives between passes ----
@@ -326,10 +308,9 @@
         }
       }
     }
-    // Slot records in HBM are re-read by other lanes / waves.  With a shared pool a slot only reaches another wave
-    // through a queue transaction, whose release fence (txn_end) covers these stores: no wait here, the store
-    // latency overlaps with the bookkeeping that follows.
-    if constexpr (!SHARED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    // Slot records in HBM are re-read by other lanes / waves.  A slot only reaches another wave through a queue
+    // transaction, whose release fence (txn_end) covers these stores: no wait here, the store latency overlaps
+    // with the bookkeeping that follows.
     PT_EV(8, 0);
   };
 
@@ -542,7 +523,6 @@
       for (int j = 0; j < kPacketShadows; j++) local_push((useAux && j < pk.nShadow) ? Q_NODE : DEST_NONE, (axp >> (kSlotBits * j)) & kSlotMask);
     }
     }
-    if constexpr (!SHARED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     PT_SUB(tBStore);
     PT_EV(4, __popcll(__ballot(useAux)));
   };
@@ -722,7 +702,7 @@
   // holds the path (ctl thr rad hit bsc pend att); the 36 bytes that live in LDS go into the record's two spare rows, a borrowed slot's
   // verdict is copied to where an unborrowed packet would have left it, and the record's index goes on the drain list.  Outside the loop
   // on purpose: inside, as one more pass, the same code cost the benchmark frame 1 % through the loop's register allocation.
-  if constexpr (SHARED) {
+  {
     __syncthreads();
     // (everything this block needs is taken afresh from the arguments: nothing stays live through the loop for its sake)
     const LaunchArgs& a = fresh_args();

@@ -1,7 +1,7 @@
 // pt_slot.h -- the path-slot record of kernel variant 4 in HBM (SlotCold) and the bits of a slot's LDS flag word: shared by
 // packetkernel.hip, which owns the slots, and drainkernel.hip, which takes the last paths of a launch over at a packet boundary.
 #pragma once
-#include "pt_types.h"
+#include "pt_slotio.h"
 
 namespace pt {
 namespace {
@@ -9,15 +9,12 @@ namespace {
 constexpr int kSlotBits = 10;           // slot ids in packed words (borrowed slots, parent of a borrowed slot)
 constexpr int kSlotMask = (1 << kSlotBits) - 1;
 
-
-
 // Path-slot record in HBM, private to the pool: two 128-byte lines of 16-byte rows.
 //   line 0, the shading visit's rows: ctl thr rad hit bsc pend[3]
 //   line 1, the traversal's rows:     ray[3] (the packet's rays after the first, in trace order) att[3] (shadow
 //                                     attenuations, only once a glass surface was crossed)
 // A shading visit reads line 0 (the pend rows only for the packet's shadow rays) and writes it back; a ray switch reads
-// one ray row; the leaf pass reads / writes hit (continuation) or att (shadow ray, tinted only).
-struct alignas(16) i4 { int x, y, z, w; };
+// one ray row; the leaf pass reads / writes hit (continuation) or att (shadow ray, tinted only).  Rows move through pt_slotio.h slot_load / slot_store.
 struct alignas(128) SlotCold {
   i4 ctl;       // item, depth, seed, mode | nShadow << 3 | hasBounce << 5 | hasScale << 6 | holds borrowed slots << 7
   v4 thr;       // throughput (of the hit the packet left from: the shadow results are folded with it); .w = the three borrowed slots (int bits)
@@ -30,35 +27,6 @@ struct alignas(128) SlotCold {
   v4 spare[2];  // (the texture colour of a hit never outlives its visit here)
 };
 static_assert(sizeof(SlotCold) == 256, "SlotCold layout");
-
-// Slot records stream through the cache hierarchy once per visit; PT_SLOT_NT marks their loads/stores
-// non-temporal so that they do not push BVH nodes out of the 4 MB L2 of the XCD.
-#ifndef PT_SLOT_NT
-#define PT_SLOT_NT 0
-#endif
-typedef float f4v __attribute__((ext_vector_type(4)));
-template <class T> __device__ __forceinline__ T slot_load(const T* p) {
-  static_assert(sizeof(T) % 16 == 0, "16-byte granules");
-  if constexpr (PT_SLOT_NT) {
-    T out;
-    const f4v* src = reinterpret_cast<const f4v*>(p); f4v* dst = reinterpret_cast<f4v*>(&out);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 16; i++) dst[i] = __builtin_nontemporal_load(src + i);
-    return out;
-  } else {
-    return *p;
-  }
-}
-template <class T> __device__ __forceinline__ void slot_store(T* p, const T& v) {
-  static_assert(sizeof(T) % 16 == 0, "16-byte granules");
-  if constexpr (PT_SLOT_NT) {
-    const f4v* src = reinterpret_cast<const f4v*>(&v); f4v* dst = reinterpret_cast<f4v*>(p);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 16; i++) __builtin_nontemporal_store(src[i], dst + i);
-  } else {
-    *p = v;
-  }
-}
 
 // stack[slot][0]: bits 0-7 stack pointer, the rest describes the packet in flight
 constexpr int kSpMask = 0xff;

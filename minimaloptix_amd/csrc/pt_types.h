@@ -167,7 +167,7 @@ enum { LIGHT_SPHERE = 0, LIGHT_QUAD = 1 };
 enum { FEAT_TEXTURE = 1, FEAT_SPHERE_LIGHT = 2, FEAT_PLAIN_MATERIALS = 4, FEAT_SPHERES = 8, FEAT_ALL = 15 };
 // Not a program and not part of FEAT_ALL: a lean build whose triangle hit still reads Tri48 + TriShade instead of the one TriFace record
 // (hit_attributes<0>).  The 128-byte-node lean packet kernels are instantiated with it: with the record their scalar spills rise (22 / 22 against
-// the 21 / 22 of tests/test_packet_features_cpu.py, under every layout and statement order tried: NOTEBOOK.md round 20).
+// the 21 / 22 of tests/test_packet_resources_cpu.py, under every layout and statement order tried: NOTEBOOK.md round 20).
 constexpr int FEAT_SPLIT_HIT = 16;
 template <int F> PT_HD constexpr bool has(int bit) { return (F & bit) != 0; }
 // What a primitive is to a shadow ray (disneyAnyHit, Material.cu:225-232): no any-hit program at all (lights, non-Disney

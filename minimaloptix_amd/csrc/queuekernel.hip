@@ -1,4 +1,4 @@
-// queuekernel.hip -- megakernel variants 2 and 3: slot-resident traversal state + stage queues.
+// queuekernel.hip -- megakernel variant 3: slot-resident traversal state + stage queues.
 //
 // Measured on variant 1 (coffee, 32 spp): a wave spends 42 % of its time in BVH node steps that
 // run with 34 of 64 lanes, 22 % in leaf passes that run with 18 lanes, 11 % setting rays up for a
@@ -18,22 +18,20 @@
 // wave-level ray compaction + sorting by stage of the north star; the per-path arithmetic is the
 // same pt_path.h code as variants 0/1, so the images are bit-identical.
 //
-//   (SHARED = false, every wave with its own 128 slots and queues, was variant 2 of rounds 1-2; it is no longer instantiated)
-//   variant 3 (SHARED = true):  the 4 waves of a workgroup share 512 slots and one set of queues
-//       (a spin-lock in LDS guards one short queue transaction per pass), so that full batches
-//       of every stage are available almost all the time.
+// The 4 waves of a workgroup share 512 slots and one set of queues (a spin-lock in LDS guards one short queue transaction
+// per pass), so that full batches of every stage are available almost all the time.  (Rounds 1-2 also had every wave with a
+// pool of 128 slots and queues of its own, variant 2.)  What this scheduler declares like the packet kernel's is in pt_sched.h.
 #include <hip/hip_runtime.h>
 
 #include "megakernel.h"
 #include "pt_lanestack.h"
 #include "pt_path.h"
+#include "pt_sched.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlockThreads = 256;
-constexpr int kWaves = kBlockThreads / 64;
 #ifndef PT_KP
 #define PT_KP 128
 #endif
@@ -48,9 +46,6 @@ constexpr int kStackN = PT_STACKN;      // LDS stack entries per slot; deeper le
 constexpr int kWavesPerSimd = PT_WAVES_PER_SIMD;   // occupancy target: 3 workgroups per CU (VGPR <= 168, LDS <= 53 KB)
 constexpr int ring_capacity(int n) { int c = 1; while (c < n) c <<= 1; return c; }
 
-// pool-wide queues first (they index PoolLds::queue); Q_NODE / Q_LEAF are per-wave rings (WavePriv)
-enum { Q_SHADE = 0, Q_GEN = 1, kNumQ = 2, Q_NODE = 2, Q_LEAF = 3, DEST_DONE = 4, DEST_NONE = -1 };
-
 // Path-slot record in HBM, private to the pool: eight 16-byte rows, grouped by WHO needs them and WHEN they change, so
 // that a visit moves only the rows it uses (round 1 moved all 144 bytes in and out on every shading visit and 48-80
 // bytes on every leaf visit: 474 B of scheduler state per ray, most of the kernel's fabric traffic):
@@ -62,7 +57,6 @@ enum { Q_SHADE = 0, Q_GEN = 1, kNumQ = 2, Q_NODE = 2, Q_LEAF = 3, DEST_DONE = 4,
 // What the rows do not hold lives in LDS (origin, direction, tbest, node, stack; ray type and "hit row valid" in the
 // slot's flag word), or is implied: the pixel follows from the work item, tmin is the scene's epsilon, a radiance ray's
 // tmax is RT_DEFAULT_MAX and a shadow ray's tmax is the tbest the node loop carries (a shadow ray never shortens it).
-struct alignas(16) i4 { int x, y, z, w; };
 struct alignas(16) SlotCold {
   i4 ctl;     // item, depth, seed, mode | light << 3
   v4 thr;     // throughput, cdlin.y
@@ -75,35 +69,6 @@ struct alignas(16) SlotCold {
 };
 static_assert(sizeof(SlotCold) == 128, "SlotCold layout");
 
-// Slot records stream through the cache hierarchy once per visit; PT_SLOT_NT marks their loads/stores
-// non-temporal so that they do not push BVH nodes out of the 4 MB L2 of the XCD.
-#ifndef PT_SLOT_NT
-#define PT_SLOT_NT 0
-#endif
-typedef float f4v __attribute__((ext_vector_type(4)));
-template <class T> __device__ __forceinline__ T slot_load(const T* p) {
-  static_assert(sizeof(T) % 16 == 0, "16-byte granules");
-  if constexpr (PT_SLOT_NT) {
-    T out;
-    const f4v* src = reinterpret_cast<const f4v*>(p); f4v* dst = reinterpret_cast<f4v*>(&out);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 16; i++) dst[i] = __builtin_nontemporal_load(src + i);
-    return out;
-  } else {
-    return *p;
-  }
-}
-template <class T> __device__ __forceinline__ void slot_store(T* p, const T& v) {
-  static_assert(sizeof(T) % 16 == 0, "16-byte granules");
-  if constexpr (PT_SLOT_NT) {
-    const f4v* src = reinterpret_cast<const f4v*>(&v); f4v* dst = reinterpret_cast<f4v*>(p);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 16; i++) __builtin_nontemporal_store(src[i], dst + i);
-  } else {
-    *p = v;
-  }
-}
-
 // LDS image of NS slots
 template <int NS>
 struct PoolLds {
@@ -112,46 +77,17 @@ struct PoolLds {
   v4 nodeB[NS];           // d.xyz, node (int bits); a lane that picks the slot up for the node loop derives 1/d from it
   int stack[NS][kStackN + 1];   // [0] = sp | kShadeFlag, [1..] = entries
   unsigned short queue[kNumQ][ring_capacity(NS)];
-  int qHead[kNumQ], qCount[kNumQ];   // SHARED only
-  int done, lock;                    // SHARED only
+  int qHead[kNumQ], qCount[kNumQ];
+  int done, lock;
 };
 
-template <int NS>
-struct WavePriv {
-  unsigned short qnode[ring_capacity(NS)];   // node-ready slots owned by this wave (ring)
-  // One loop iteration pushes at most 128 slots (results of the last pass + lanes leaving the node loop).
-  unsigned short qleaf[256];       // slots standing at a leaf, owned by this wave (ring; a pass runs at 64: < 64 + 128)
-  unsigned short outbox[2][160];   // slots on their way to the pool's Q_SHADE / Q_GEN (flushed at 32: < 32 + 128)
-};
-
-typedef __attribute__((address_space(3))) int lds_int;
-
-// The LDS part is addressed through an address_space(3) pointer so that push/pop compile to
-// ds_write_b32/ds_read_b32 (a generic pointer makes the compiler merge the LDS and the HBM
-// overflow path into one flat_load).
 // flag bits next to the stack pointer in stack[slot][0]
 constexpr int kShadeFlag = 1 << 30;   // a finished ray goes to Q_SHADE (hit or shadow ray), not Q_GEN
 constexpr int kShadowRay = 1 << 29;   // the ray in flight is a shadow ray (MinimalOptiX.h:48 RAY_TYPE_SHADOW)
 constexpr int kHitValid = 1 << 28;    // SlotCold::hit holds this ray's nearest hit / attenuation (else: none yet / (1,1,1))
 constexpr int kSlotFlags = kShadeFlag | kShadowRay | kHitValid;
 
-struct SlotStack {
-  lds_int* lds;           // &stack[slot][1]
-  int* ovf;               // this slot's overflow area in HBM (or nullptr)
-  __device__ __forceinline__ void store(int sp, int v) {
-    if (__builtin_expect(sp < kStackN, 1)) lds[sp] = v; else ovf[sp - kStackN] = v;
-  }
-  __device__ __forceinline__ int load(int sp) const {
-    int v;
-    if (__builtin_expect(sp < kStackN, 1)) v = lds[sp]; else v = ovf[sp - kStackN];
-    return v;
-  }
-  __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= kStackN; }     // three pushes stay in LDS
-  __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp] = v; }
-  static constexpr bool kFlat = false;      // pt_path.h node_step_nearfar: this stack takes the branched tail
-  __device__ __forceinline__ bool fits_fast(int, int) const { return false; }
-  __device__ __forceinline__ int peek_fast(int) const { return 0; }
-};
+using SlotStack = LdsStack<kStackN, false>;      // pt_path.h node_step_nearfar: this stack takes the branched tail
 
 // destination queue of a slot after a traversal step / a ray set-up
 __device__ __forceinline__ int route(int node, int kind, int bestPrim) {
@@ -161,47 +97,31 @@ __device__ __forceinline__ int route(int node, int kind, int bestPrim) {
 
 // NEAR: the scene has a Disney GLASS material, shadow rays keep their nearest any-hit candidate (pt_path.h, rule D5).  A template
 // parameter so that scenes without one -- the benchmark scene -- run code in which that logic does not exist.
-// The launch arguments again, through a pointer the compiler cannot see through (packetkernel.hip fresh_args has the whole story): a pass that needs the
-// scene takes its own copy -- s_load where used, dead when the pass ends -- instead of ~100 loop-invariant words living in scalar registers for the whole launch
-// and the scheduler's own scalar state in lanes of spill registers (round 6: this kernel shipped with 118-120 spilled scalar registers).
-__device__ __forceinline__ const LaunchArgs& fresh_args() {
-  typedef __attribute__((address_space(4))) const LaunchArgs CA;
-  unsigned long long p = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const LaunchArgs*)(CA*)p;
-}
-
-template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false>
+// The passes read the launch arguments through fresh_args() (pt_sched.h has the whole story).
+template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false>      // SHARED: kept for the kernels' symbol names only
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(const LaunchArgs a) {
-  constexpr int NS = SHARED ? kP * kWaves : kP;          // slots per pool
+  static_assert(SHARED, "the workgroup's waves share one pool: per-wave pools are gone");
+  constexpr int NS = kP * kWaves;                        // slots per pool
   constexpr int RC = ring_capacity(NS);                  // ring capacity (power of two >= NS)
-  __shared__ PoolLds<NS> sPool[SHARED ? 1 : kWaves];
-  __shared__ WavePriv<NS> sPriv[kWaves];
+  __shared__ PoolLds<NS> sPool[1];                       // (an array of one: declared as a plain object, the LDS addressing of every kernel came out differently)
+  __shared__ WavePriv<RC> sPriv[kWaves];
 
   SceneView scv = a.scene;
   scv.shadowNearest = NEAR ? 1 : 0;                 // compile-time constant from here on
   const SceneView& sc = scv;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  PoolLds<NS>& W = sPool[SHARED ? 0 : wave];
-  const int gpool = SHARED ? blockIdx.x : blockIdx.x * kWaves + wave;
+  PoolLds<NS>& W = sPool[0];
+  const int gpool = blockIdx.x;
   SlotCold* cold = reinterpret_cast<SlotCold*>(a.poolCold) + (size_t)gpool * NS;
   int* ovfBase = a.stackOverflow ? a.stackOverflow + (size_t)gpool * NS * a.ovfDepth : nullptr;
 
   // sub-phase clocks of the counting build
   unsigned long long tLocal = 0, tLock = 0, tTxn = 0, tIdle = 0, tBLoad = 0, tBRun = 0, tBStore = 0, nTxn = 0, nIter = 0;
   unsigned long long tSub = 0, nIterResult = 0, nIterLights = 0, nIterGen = 0, nodeRuns = 0, ringBacklog = 0, leafBacklog = 0;
-#define PT_SUB0() do { if (CNT) tSub = __builtin_amdgcn_s_memtime(); } while (0)
-#define PT_SUB(acc) do { if (CNT) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - tSub; tSub = now_; } } while (0)
-  // queue bookkeeping: registers (wave-uniform); with SHARED they mirror LDS inside a transaction
+  // queue bookkeeping: registers (wave-uniform) that mirror LDS inside a transaction
   int qHead[kNumQ] = { 0, 0 }, qCount[kNumQ] = { 0, 0 };
   int nDone = 0;
 
-  [[maybe_unused]] auto q_push = [&](int q, bool pred, int slot) {
-    const unsigned long long m = __ballot(pred);
-    if (m == 0ull) return;
-    if (pred) W.queue[q][(qHead[q] + qCount[q] + lane_rank(m)) & (RC - 1)] = (unsigned short)slot;
-    qCount[q] += __popcll(m);
-  };
   auto q_pop = [&](int q, bool want) -> int {
     const unsigned long long m = __ballot(want);
     const int n = min((int)__popcll(m), qCount[q]);
@@ -212,26 +132,22 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
     return slot;
   };
   auto txn_begin = [&]() {
-    if constexpr (SHARED) {
-      if (lane == 0) { while (atomicCAS(&W.lock, 0, 1) != 0) __builtin_amdgcn_s_sleep(1); }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      if (CNT) { (void)__builtin_amdgcn_readfirstlane(W.lock); PT_SUB(tLock); nTxn++; }
-      for (int q = 0; q < kNumQ; q++) {
-        qHead[q] = __builtin_amdgcn_readfirstlane(W.qHead[q]);
-        qCount[q] = __builtin_amdgcn_readfirstlane(W.qCount[q]);
-      }
-      nDone = __builtin_amdgcn_readfirstlane(W.done);
+    if (lane == 0) { while (atomicCAS(&W.lock, 0, 1) != 0) __builtin_amdgcn_s_sleep(1); }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (CNT) { (void)__builtin_amdgcn_readfirstlane(W.lock); PT_SUB(tLock); nTxn++; }
+    for (int q = 0; q < kNumQ; q++) {
+      qHead[q] = __builtin_amdgcn_readfirstlane(W.qHead[q]);
+      qCount[q] = __builtin_amdgcn_readfirstlane(W.qCount[q]);
     }
+    nDone = __builtin_amdgcn_readfirstlane(W.done);
   };
   auto txn_end = [&]() {
-    if constexpr (SHARED) {
-      if (lane == 0) {
-        for (int q = 0; q < kNumQ; q++) { W.qHead[q] = qHead[q]; W.qCount[q] = qCount[q]; }
-        W.done = nDone;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&W.lock, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (lane == 0) {
+      for (int q = 0; q < kNumQ; q++) { W.qHead[q] = qHead[q]; W.qCount[q] = qCount[q]; }
+      W.done = nDone;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(&W.lock, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   auto make_stack = [&](int slot) {
     SlotStack st;
@@ -245,26 +161,20 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
   // about 70 us with all 512 slots of every pool, so a path that bounces to the depth cap (about 1000 dependent rays)
   // takes 70-90 ms however short the launch is.  A short launch (one rank's share of a multi-GPU frame) therefore
   // uses fewer slots: a little less throughput, a much shorter critical path (LaunchArgs::slotsInUse, api_render.hip plan_launch).
-  const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? (SHARED ? a.slotsInUse : max(64, a.slotsInUse / kWaves)) : NS;
+  const int nUse = (a.slotsInUse > 0 && a.slotsInUse < NS) ? a.slotsInUse : NS;
   {
-    const int first = SHARED ? threadIdx.x : lane, step = SHARED ? kBlockThreads : 64;
-    for (int s = first; s < nUse; s += step) {
+    for (int s = threadIdx.x; s < nUse; s += kBlockThreads) {
       i4 ctl; ctl.x = -1; ctl.y = 0; ctl.z = 0; ctl.w = M_NEW_PIXEL;     // item -1: whatever sample comes first is "new" (rows get written)
       cold[s].ctl = ctl;
       W.stack[s][0] = 0;
       W.queue[Q_GEN][s] = (unsigned short)s;
     }
-    if constexpr (SHARED) {
-      if (threadIdx.x == 0) {
-        for (int q = 0; q < kNumQ; q++) { W.qHead[q] = 0; W.qCount[q] = 0; }
-        W.qCount[Q_GEN] = nUse; W.done = NS - nUse; W.lock = 0;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-    } else {
-      qCount[Q_GEN] = nUse; nDone = NS - nUse;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (threadIdx.x == 0) {
+      for (int q = 0; q < kNumQ; q++) { W.qHead[q] = 0; W.qCount[q] = 0; }
+      W.qCount[Q_GEN] = nUse; W.done = NS - nUse; W.lock = 0;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
   }
 
   Counters ct = {};
@@ -272,7 +182,6 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
   unsigned long long tBatch = 0, tSwap = 0, tNode = 0, tLeaf = 0, tStamp = 0;
   const unsigned long long tStart = CNT ? __builtin_amdgcn_s_memtime() : 0ull;
   [[maybe_unused]] const unsigned long long rtStart = CNT ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#define PT_STAMP(acc) do { if (CNT) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - tStamp; tStamp = now_; } } while (0)
   tStamp = tStart;
 
   // ---- node-loop worker context: the only per-lane state that survives between passes ----
@@ -340,10 +249,9 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
                          ((shadow || tv.bestPrim >= 0) ? kShadeFlag : 0);
       pendDest = route(tv.node, ps.kind, tv.bestPrim);
     }
-    // Slot records in HBM are re-read by other lanes / waves.  With a shared pool a slot only reaches another wave
-    // through a queue transaction, whose release fence (txn_end) covers these stores: no wait here, the store
-    // latency overlaps with the bookkeeping that follows.
-    if constexpr (!SHARED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    // Slot records in HBM are re-read by other lanes / waves.  A slot only reaches another wave through a queue
+    // transaction, whose release fence (txn_end) covers these stores: no wait here, the store latency overlaps
+    // with the bookkeeping that follows.
   };
 
   // ---- shading / regeneration batch: run the path state machine for the popped slots ----
@@ -468,7 +376,6 @@ __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_queuekernel(c
         pendDest = (ps.mode == M_NEW_PIXEL) ? Q_GEN : DEST_DONE;
       }
     }
-    if constexpr (!SHARED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     PT_SUB(tBStore);
   };
 
@@ -648,7 +555,7 @@ static void launch_qk(dim3 grid, dim3 block, hipStream_t stream, const LaunchArg
   if (a.scene.shadowNearest) pt_queuekernel<CNT, true, FAST, true><<<grid, block, 0, stream>>>(a);
   else                       pt_queuekernel<CNT, true, FAST, false><<<grid, block, 0, stream>>>(a);
 }
-hipError_t PT_QK_EXPORT(launch_queuekernel)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, int /*features*/, bool /*slim*/) {
+hipError_t PT_QK_EXPORT(launch_queuekernel)(hipStream_t stream, const LaunchArgs& a, int nBlocks, bool counted, bool fastShading, PacketBuild /*the packet kernel's alone*/) {
   dim3 grid(nBlocks), block(kBlockThreads);
   // fastShading: opt-in approximate BRDF arithmetic (pt_disney.h ShadeMath)
   if (fastShading) { if (counted) launch_qk<true, true>(grid, block, stream, a); else launch_qk<false, true>(grid, block, stream, a); }

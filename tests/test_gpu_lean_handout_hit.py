@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 
 from common import M, write_glass_over_opaque_scene
+from packet_helpers import FEAT_ALL, bits as _bits, write_floor_block_scene
 
 pytestmark = pytest.mark.gpu
 
 W, H = 37, 19
-FEAT_ALL = 15
 SEED_COUNTS = (3, 17)
-
-
-def _bits(a):
-    return a.view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -36,28 +32,11 @@ def _defaults(ctx):
     ctx.set_option("specialize", 1); ctx.set_option("tile_major", 3); ctx.set_partition(0, 1)
 
 
-def _write_meshes(root, block_material="Block", floor_material="Floor"):
-    """A floor and a back wall WITH vertex normals, a block WITHOUT, untextured Disney materials, one quad light: lean-eligible."""
-    d = root / "scenes" / "cornell"
-    d.mkdir(parents=True, exist_ok=True)
-    (d / "floor.obj").write_text("v -3 0 -2\nv -3 0 2\nv 3 0 2\nv 3 0 -2\nvn 0 1 0\nvn 0.2 0.9 0.1\nf 1//1 2//2 3//1 4//2\n"
-                                 "v -3 0 2\nv -3 3.4 2\nv 3 3.4 2\nv 3 0 2\nvn 0 0 -1\nvn 0.1 0.2 -0.9\nf 5//3 6//4 7//3 8//4\n")
-    (d / "block.obj").write_text(
-        "v -0.5 0 -0.5\nv 0.5 0 -0.5\nv 0.5 0 0.5\nv -0.5 0 0.5\nv -0.5 0.8 -0.5\nv 0.5 0.8 -0.5\nv 0.5 0.8 0.5\nv -0.5 0.8 0.5\n"
-        "f 5 8 7 6\nf 1 2 6 5\nf 2 3 7 6\nf 3 4 8 7\nf 4 1 5 8\n")
-    (d / "cornell.scene").write_text(
-        "material Floor\n{\n\tcolor 0.7 0.7 0.7\n\troughness 0.6\n}\n"
-        "material Block\n{\n\tcolor 0.8 0.3 0.2\n\troughness 0.3\n\tclearcoat 0.5\n}\n"
-        "mesh\n{\n\tfile floor.obj\n\tmaterial %s\n}\n"
-        "mesh\n{\n\tfile block.obj\n\tmaterial %s\n}\n"
-        "light\n{\n\ttype Quad\n\tposition -1 2.5 -1\n\tv1 0 2.5 -1\n\tv2 -1 2.5 0\n\temission 12 12 12\n}\n" % (floor_material, block_material))
-    return str(root / "scenes") + "/"
-
-
 def _scene(name, tmp_path, width=W, height=H, **kw):
     if name == "panes":      # a Disney GLASS pane over an opaque one (tests/common.py): the NEAR = true lean kernels; every face has normals
         return M.HostScene("file:cornell", width, height, base_folder=write_glass_over_opaque_scene(tmp_path, True))
-    return M.HostScene("file:cornell", width, height, base_folder=_write_meshes(tmp_path, **kw))
+    # a floor and a back wall WITH vertex normals, a block WITHOUT
+    return M.HostScene("file:cornell", width, height, base_folder=write_floor_block_scene(tmp_path, tilted_normals=True, **kw))
 
 
 def _render(ctx, n, specialize):

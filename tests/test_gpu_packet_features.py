@@ -12,33 +12,20 @@ import numpy as np
 import pytest
 
 from common import M
+from packet_helpers import DRAIN_DEFAULT, FEAT_ALL, bits as _bits, packet_ctx, write_floor_block_scene      # noqa: F401 (packet_ctx: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 K = M._capi
 W, H = 320, 180
-FEAT_TEXTURE, FEAT_SPHERE_LIGHT, FEAT_PLAIN_MATERIALS, FEAT_SPHERES, FEAT_ALL = 1, 2, 4, 8, 15
-DRAIN_DEFAULT = 64     # option drain_below as moptix_create leaves it
+FEAT_TEXTURE, FEAT_SPHERE_LIGHT, FEAT_PLAIN_MATERIALS, FEAT_SPHERES = 1, 2, 4, 8
 SEEDS = M.launch_seeds(2)
-
-
-def _bits(a):
-    return a.view(np.uint32)
 
 
 def _render(ctx, counted=False):
     ctx.accum_clear()
     st = ctx.render_counted(SEEDS) if counted else ctx.render(SEEDS)
     return ctx.accum_read(), st
-
-
-@pytest.fixture
-def packet_ctx(gpu_ctx, request):
-    """The session's context with the packet kernel asked for; every option this file touches goes back to its default afterwards."""
-    gpu_ctx.set_option("kernel_variant", 4)
-    yield gpu_ctx
-    for name, value in (("kernel_variant", -1), ("node_format", 0), ("specialize", 1), ("drain_below", DRAIN_DEFAULT)):
-        gpu_ctx.set_option(name, value)
 
 
 # ---- lean scene, the same bits ---------------------------------------------------------------------------------------------------------
@@ -86,20 +73,7 @@ def test_lean_kernel_gives_the_general_kernels_bits(packet_ctx, tmp_path, scene,
 
 def _write_base_scene(tmp_path):
     """Untextured Disney meshes under one quad light: a floor, a back wall and a block -- lean-eligible, within variant 4's limits."""
-    d = tmp_path / "scenes" / "cornell"
-    d.mkdir(parents=True)
-    (d / "floor.obj").write_text("v -3 0 -2\nv -3 0 2\nv 3 0 2\nv 3 0 -2\nvn 0 1 0\nf 1//1 2//1 3//1 4//1\n"
-                                 "v -3 0 2\nv -3 3.4 2\nv 3 3.4 2\nv 3 0 2\nvn 0 0 -1\nf 5//2 6//2 7//2 8//2\n")
-    (d / "block.obj").write_text(
-        "v -0.5 0 -0.5\nv 0.5 0 -0.5\nv 0.5 0 0.5\nv -0.5 0 0.5\nv -0.5 0.8 -0.5\nv 0.5 0.8 -0.5\nv 0.5 0.8 0.5\nv -0.5 0.8 0.5\n"
-        "f 5 8 7 6\nf 1 2 6 5\nf 2 3 7 6\nf 3 4 8 7\nf 4 1 5 8\n")
-    (d / "cornell.scene").write_text(
-        "material Floor\n{\n\tcolor 0.7 0.7 0.7\n\troughness 0.6\n}\n"
-        "material Block\n{\n\tcolor 0.8 0.3 0.2\n\troughness 0.3\n\tclearcoat 0.5\n}\n"
-        "mesh\n{\n\tfile floor.obj\n\tmaterial Floor\n}\n"
-        "mesh\n{\n\tfile block.obj\n\tmaterial Block\n}\n"
-        "light\n{\n\ttype Quad\n\tposition -1 2.5 -1\n\tv1 0 2.5 -1\n\tv2 -1 2.5 0\n\temission 12 12 12\n}\n")
-    return M.HostScene("file:cornell", W, H, base_folder=str(tmp_path / "scenes") + "/")
+    return M.HostScene("file:cornell", W, H, base_folder=write_floor_block_scene(tmp_path))
 
 
 def _f32p(a):

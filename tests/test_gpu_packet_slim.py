@@ -5,41 +5,14 @@ A lean launch that borrows no slot ("aux_depth" 0, or 1e8 samples and more with 
 GLASS material -- or with one under "shadow_rule" 1, where shadow rays keep their nearest candidate -- runs the slim build
 ("kernel_slim_used" 1).  What it leaves out is code such a launch cannot reach, so every accumulator bit must be the other builds'.
 Small frames, "kernel_variant" 4 set explicitly so that they reach the packet kernel at all.  A render under test always follows a render
-of OTHER seeds: the per-sample buffer then holds nothing an unfinished sample could pass for."""
+of OTHER seeds (tests/packet_helpers.py render_after_other_seeds says why)."""
 import numpy as np
 import pytest
 
 from common import M, write_glass_over_opaque_scene
+from packet_helpers import DRAIN_DEFAULT, FEAT_ALL, bits as _bits, packet_ctx, render_after_other_seeds as _render      # noqa: F401 (packet_ctx: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-DRAIN_DEFAULT = 64     # options as moptix_create leaves them
-AUX_DEFAULT = 16
-FEAT_ALL = 15
-OTHER_SEEDS = M.launch_seeds(2, first=100)
-
-
-def _bits(a):
-    return a.view(np.uint32)
-
-
-@pytest.fixture
-def packet_ctx(gpu_ctx):
-    """The session's context with the packet kernel asked for; every option this file touches goes back to its default afterwards."""
-    gpu_ctx.set_option("kernel_variant", 4)
-    yield gpu_ctx
-    for name, value in (("kernel_variant", -1), ("specialize", 1), ("drain_below", DRAIN_DEFAULT), ("aux_depth", AUX_DEFAULT),
-                        ("slots_in_use", -1), ("shadow_rule", 1)):
-        gpu_ctx.set_option(name, value)
-
-
-def _render(ctx, seeds, **options):
-    """One frame of `seeds` under `options`, after a frame of other seeds under the same options."""
-    for name, value in options.items():
-        ctx.set_option(name, value)
-    ctx.accum_clear(); ctx.render(OTHER_SEEDS)
-    ctx.accum_clear(); ctx.render(seeds)          # raises if the watchdog flag is set (tests/test_gpu_configs.py)
-    return ctx.accum_read(), (ctx.get_option("kernel_variant_used"), ctx.get_option("kernel_features_used"), ctx.get_option("kernel_slim_used"))
 
 
 def test_coffee_slim_gives_the_bits_of_the_twin_with_borrowed_slots_the_general_build_and_the_per_lane_kernel(packet_ctx):

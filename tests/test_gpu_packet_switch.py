@@ -8,23 +8,16 @@ general build's ("specialize" 0) bit for bit -- on both node formats, on the NEA
 shadow rays never end early, every one ends by exhaustion), with pools down to their last paths while switches are pending and paths handed to
 the drain kernel, as each rank of a partition, after a vertex update with refit, and in the adaptive pass.  A render raises if the watchdog
 flag is set, so every case also says that no slot was lost.  64x64 frames, "kernel_variant" 4 and "aux_depth" 0 so that a launch this small
-runs the slim build at all; a render under test follows a render of other seeds (tests/test_gpu_packet_slim.py says why)."""
+runs the slim build at all; a render under test follows a render of other seeds (tests/packet_helpers.py says why)."""
 import numpy as np
 import pytest
 
 from common import M, write_glass_over_opaque_scene
+from packet_helpers import FEAT_ALL, bits as _bits, kernel_used, packet_ctx as _packet_ctx, render_after_other_seeds
 
 pytestmark = pytest.mark.gpu
 
 W = H = 64
-FEAT_ALL = 15
-DRAIN_DEFAULT = 64     # options as moptix_create leaves them
-AUX_DEFAULT = 16
-OTHER_SEEDS = M.launch_seeds(2, first=100)
-
-
-def _bits(a):
-    return a.view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -33,25 +26,17 @@ def coffee():
 
 
 @pytest.fixture
-def packet_ctx(gpu_ctx):
-    """The session's context with the packet kernel asked for and no borrowed slots; every option this file touches goes back to its default."""
-    gpu_ctx.set_option("kernel_variant", 4)
-    gpu_ctx.set_option("aux_depth", 0)
-    yield gpu_ctx
-    gpu_ctx.set_partition(0, 1)
-    for name, value in (("kernel_variant", -1), ("specialize", 1), ("drain_below", DRAIN_DEFAULT), ("aux_depth", AUX_DEFAULT),
-                        ("slots_in_use", -1), ("shadow_rule", 1), ("node_format", 0)):
-        gpu_ctx.set_option(name, value)
+def packet_ctx(_packet_ctx):
+    """tests/packet_helpers.py packet_ctx, and no borrowed slots."""
+    _packet_ctx.set_option("aux_depth", 0)
+    return _packet_ctx
 
 
 def _render(ctx, seeds, specialize):
     """One frame of `seeds` by the slim build (`specialize` 1) or the general one (0), after a frame of other seeds."""
-    ctx.set_option("specialize", specialize)
-    ctx.accum_clear(); ctx.render(OTHER_SEEDS)
-    ctx.accum_clear(); ctx.render(seeds)          # raises if the watchdog flag is set (tests/test_gpu_configs.py)
-    used = (ctx.get_option("kernel_variant_used"), ctx.get_option("kernel_features_used"), ctx.get_option("kernel_slim_used"))
+    frame, used = render_after_other_seeds(ctx, seeds, specialize=specialize)
     assert used == ((4, 0, 1) if specialize else (4, FEAT_ALL, 0)), used
-    return ctx.accum_read()
+    return frame
 
 
 def _slim_equals_general(ctx, seeds, what):
@@ -131,8 +116,7 @@ def test_adaptive_pass(packet_ctx, coffee):
         ctx.set_option("specialize", specialize)
         ctx.adaptive_clear()
         st = ctx.render_adaptive(seeds, threshold=0.05, min_samples=8, batch=8)
-        used = (ctx.get_option("kernel_variant_used"), ctx.get_option("kernel_features_used"), ctx.get_option("kernel_slim_used"))
-        assert used == ((4, 0, 1) if specialize else (4, FEAT_ALL, 0)), used
+        assert kernel_used(ctx) == ((4, 0, 1) if specialize else (4, FEAT_ALL, 0)), kernel_used(ctx)
         assert st["passes"] >= 2 and st["samples_traced"] < st["samples_uniform"]      # some pass rendered a subset of the pixels
         got.append((ctx.accum_read(), ctx.adaptive_read()["count"]))
     ctx.accum_clear()      # leave the context to plain renders
