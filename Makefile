@@ -4,6 +4,7 @@
 #   make host       -> minimaloptix_amd/lib/libmoptix_host.so, minimaloptix_amd/lib/moptix_render
 #   make oracle     -> oracle/liboracle.so                      (test infrastructure)
 #   make hostsim    -> tests/hostsim/libhostsim.so              (test infrastructure: the CPU mirrors of the kernels, one library)
+#   make pointmultisim -> tests/pointmultisim/libpointmultisim.so (test infrastructure: the CPU mirror of the K-nearest point queries)
 #   make loopback   -> tests/rccl_loopback/librccl_loopback.so  (test infrastructure: N ranks on one GPU without RCCL)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -30,7 +31,7 @@ HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(
 HOST_OBJS := $(patsubst $(HOST)/%.cpp,build/host_%.o,$(HOST_SRCS))
 HOST_HDRS := $(wildcard $(HOST)/*.h) $(wildcard $(CSRC)/pt_*.h) include/moptix.h include/moptix_host.h
 
-all: device host oracle hostsim loopback
+all: device host oracle hostsim pointmultisim loopback
 
 device: $(LIBDIR)/$(LIBNAME)
 host: $(LIBDIR)/libmoptix_host.so $(LIBDIR)/moptix_render
@@ -38,6 +39,8 @@ oracle:
 	$(MAKE) -C oracle -s
 hostsim:
 	$(MAKE) -C tests/hostsim -s
+pointmultisim:
+	$(MAKE) -C tests/pointmultisim -s
 loopback:
 	$(MAKE) -C tests/rccl_loopback -s
 
@@ -69,6 +72,6 @@ $(LIBDIR)/moptix_render: $(HOST)/main.cpp $(LIBDIR)/libmoptix_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST)/main.cpp -L$(LIBDIR) -lmoptix_host -lmoptix -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/rccl_loopback/librccl_loopback.so
+	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/pointmultisim/libpointmultisim.so tests/rccl_loopback/librccl_loopback.so
 
-.PHONY: all device host oracle hostsim loopback clean
+.PHONY: all device host oracle hostsim pointmultisim loopback clean

@@ -761,6 +761,42 @@ int moptix_query_points_signed(moptix_context ctx, const float* points, int64_t 
 int moptix_get_sign_info(moptix_context ctx, moptix_sign_info* out);
 int moptix_debug_read_sign_table(moptix_context ctx, void* table);
 
+/* ---- K-nearest point queries: the maxNear nearest primitives to each point, in order --------------------------------------------------
+ * Every face within a contact margin, the K best candidates of a correspondence (so that a wrong nearest triangle on a fold can be
+ * rejected), "how many primitives are within r" -- in one walk, and right at exactly equal distances (duplicated faces, shared vertices),
+ * where no re-launch of the closest query with another maxDist finds the second of two.
+ * A query is the point queries' four floats  x y z maxDist, valid or invalid by their rule; r2 = maxDist * maxDist, +inf = no limit.
+ * The near set S of a valid query is the set of pairs (d2(q, primitive), prim) over every primitive record with d2 < r2, d2 the
+ * per-primitive function of the point queries: one pair per primitive, a sphere included.  Every primitive counts, whatever its material.
+ * An invalid query has S = {}.  S is a function of the query and the device records alone.
+ *   hits    n x maxNear moptix_point_hit records, query-major.  For query i the first c = min(maxNear, |S|) records are the c least
+ *           elements of S by (d2, prim) ascending (rule D5's order), each filled exactly as MOPTIX_POINT_CLOSEST fills its record when that
+ *           primitive wins: dist one correctly rounded sqrt(d2); prim, mat, u, v, p as that mode sets them.  Records c .. maxNear - 1 are
+ *           that mode's miss record on the query (dist = the given maxDist's bits, prim = mat = -1, the rest 0).  Every byte is defined.
+ *           Record 0 has the bits of MOPTIX_POINT_CLOSEST on the same query.
+ *   counts  n x int32: c.  With MOPTIX_POINT_MULTI_COUNT_ALL: |S|, the number of primitives within maxDist -- the walk then cannot prune
+ *           at the maxNear-th key, only at r2.  counts[i] > 0 if and only if MOPTIX_POINT_ANY gives 1 on the same query.
+ *   maxNear 1..64.  With MOPTIX_POINT_MULTI_COUNT_ALL also 0, and hits may then be NULL: the pure in-range count.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part, and unlike the ray side there is no grazing
+ * exception: the point walk's prune is proven against the padded boxes, and csrc/pt_pointmulti.h states why the proof covers the
+ * maxNear-th bound.
+ *   moptix_query_points_multi_device  dPoints, dHits: device memory, 16-byte aligned; dCounts: device memory, 4-byte aligned.
+ *                                     Asynchronous on the context's stream.  While a point is walked its slice of dHits holds the
+ *                                     candidates; nothing else is allocated or written.  It uses the point queries' stack overflow area
+ *                                     (same grid cap and stack bound; allocated at the first point query of either kind on a tree).
+ *   moptix_query_points_multi         host pointers, blocking: upload, query, read back (the point queries' staging)
+ * n may be any int64 >= 0: longer batches are cut into launches of floor(2^30 / max(maxNear, 1)) queries, so that a launch writes at most
+ * 2^30 records and a record's index within it fits an int as a point's does; n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or misaligned
+ * pointers, n < 0, maxNear out of range, unknown flag bits; state errors as moptix_query_points ("faces dirty" before a refit included).
+ * A K-nearest query changes nothing else in the context: moptix_debug_buffer_addresses keeps its slots, and the ray queries' buffers are
+ * untouched.  Not offered: a signed list (the sign of a non-nearest primitive's pseudonormal says nothing about inside or outside),
+ * filters by primitive kind or material, lists longer than 64. */
+enum { MOPTIX_POINT_MULTI_COUNT_ALL = 1 };
+int moptix_query_points_multi_device(moptix_context ctx, const float* dPoints, int64_t n, int32_t maxNear, uint32_t flags,
+                                     void* dHits, int32_t* dCounts);
+int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n, int32_t maxNear, uint32_t flags,
+                              moptix_point_hit* hits, int32_t* counts);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)

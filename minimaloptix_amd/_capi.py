@@ -171,6 +171,8 @@ class PointHit(C.Structure):
 
 
 POINT_CLOSEST, POINT_ANY, POINT_SIGNED = 0, 1, 2
+POINT_MULTI_COUNT_ALL = 1
+POINT_MULTI_MAX_NEAR = 64
 RADIANCE_CLAMP = 1
 
 
@@ -213,6 +215,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_rays_device", "moptix_query_rays", "moptix_query_rays_multi_device", "moptix_query_rays_multi",
     "moptix_query_radiance_device", "moptix_query_radiance",
     "moptix_query_points_device", "moptix_query_points", "moptix_query_points_signed", "moptix_get_sign_info", "moptix_debug_read_sign_table",
+    "moptix_query_points_multi_device", "moptix_query_points_multi",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -316,6 +319,8 @@ def device_lib():
         L.moptix_query_points_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_points.argtypes = [vp, f32p, C.c_int64, i32, vp]
         L.moptix_query_points_signed.argtypes = [vp, f32p, C.c_int64, vp]
+        L.moptix_query_points_multi_device.argtypes = [vp, vp, C.c_int64, i32, C.c_uint32, vp, vp]
+        L.moptix_query_points_multi.argtypes = [vp, f32p, C.c_int64, i32, C.c_uint32, vp, i32p]
         L.moptix_get_sign_info.argtypes = [vp, C.POINTER(SignInfo)]
         L.moptix_debug_read_sign_table.argtypes = [vp, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]

@@ -62,6 +62,20 @@ def _record_views(out, first, last):
     return {"records": out, first: out[..., 0], "prim": ints[..., 1], "mat": ints[..., 2], "u": out[..., 3], "v": out[..., 4], last: out[..., 5:8]}
 
 
+def _point_rows(who, points, max_dist):
+    """The host path's queries of the point queries `who`: (n, 3) positions with max_dist a scalar or an (n,) array, or (n, 4) rows
+    x y z maxDist, as one contiguous (n, 4) float32 array."""
+    pts = np.asarray(points, np.float32)
+    if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+        raise ValueError("%s: points must be (n, 3) or (n, 4), not %r" % (who, pts.shape))
+    if pts.shape[1] == 3:
+        md = np.asarray(max_dist, np.float32)
+        if md.ndim > 1 or (md.ndim == 1 and len(md) != len(pts)):
+            raise ValueError("%s: max_dist must be a scalar or one value per point" % who)
+        pts = np.concatenate([pts, np.broadcast_to(md.reshape(-1, 1) if md.ndim else md, (len(pts), 1))], axis=1)
+    return np.ascontiguousarray(pts, np.float32)
+
+
 def _f3(v):
     return [float(v.x), float(v.y), float(v.z)]
 
@@ -670,15 +684,7 @@ class Context:
             raise ValueError("query_points: mode %r (closest, signed or any)" % (mode,))
         m = self.POINT_MODES[mode]
         if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
-            pts = np.asarray(points, np.float32)
-            if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-                raise ValueError("query_points: points must be (n, 3) or (n, 4), not %r" % (pts.shape,))
-            if pts.shape[1] == 3:
-                md = np.asarray(max_dist, np.float32)
-                if md.ndim > 1 or (md.ndim == 1 and len(md) != len(pts)):
-                    raise ValueError("query_points: max_dist must be a scalar or one value per point")
-                pts = np.concatenate([pts, np.broadcast_to(md.reshape(-1, 1) if md.ndim else md, (len(pts), 1))], axis=1)
-            pts = np.ascontiguousarray(pts, np.float32)
+            pts = _point_rows("query_points", points, max_dist)
             out = np.zeros(len(pts), np.int32 if m == K.POINT_ANY else POINT_DTYPE)
             pp = pts.ctypes.data_as(C.POINTER(C.c_float))
             if m == K.POINT_SIGNED:
@@ -699,6 +705,38 @@ class Context:
         if m == K.POINT_ANY:
             return out
         return _record_views(out, "dist", "p")
+
+    def query_points_multi(self, points, max_near=4, count_all=False, max_dist=np.inf):
+        """The max_near nearest primitives to each of the caller's points, in order of (distance, prim); blocking.  Returns (hits, counts):
+        per point max_near records, the nearest first and miss records behind them, and how many are primitives -- with count_all the
+        number of all primitives within max_dist instead, however many were kept (the walk then prunes at max_dist alone); max_near
+        1..64, with count_all also 0: the pure in-range count.
+        A numpy array takes the host path: (n, 3) positions with max_dist a scalar or an (n,) array, or (n, 4) rows x y z maxDist (max_dist
+        is then not consulted); hits is an (n, max_near) POINT_DTYPE array, counts an int32 array.
+        A contiguous (n, 4) float32 torch tensor on this context's device is read where it is, and the results are tensors on that device:
+        hits the dict of views dist, prim, mat, u, v, p of query_points into "records", here the (n, max_near, 8) float32 tensor of the raw
+        moptix_point_hit records, and counts an int32 tensor."""
+        k = int(max_near)
+        flags = K.POINT_MULTI_COUNT_ALL if count_all else 0
+        if k < (0 if count_all else 1) or k > K.POINT_MULTI_MAX_NEAR:
+            raise ValueError("query_points_multi: max_near %r (1..%d; 0 only with count_all)" % (max_near, K.POINT_MULTI_MAX_NEAR))
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            pts = _point_rows("query_points_multi", points, max_dist)
+            hits = np.zeros((len(pts), k), POINT_DTYPE)
+            counts = np.zeros(len(pts), np.int32)
+            self._chk(self._L.moptix_query_points_multi(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), k, flags,
+                                                        C.c_void_p(hits.ctypes.data) if k else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
+            return hits, counts
+        import torch
+        _check_tensor("query_points_multi", "points", points, ("torch.float32",), _rows(4), "shape (n, 4), x y z maxDist", self.device)
+        n = points.shape[0]
+        out = torch.empty((n, k, 8), dtype=torch.float32, device=points.device)
+        counts = torch.empty(n, dtype=torch.int32, device=points.device)
+        torch.cuda.current_stream(points.device).synchronize()      # the points are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_points_multi_device(self._h, C.c_void_p(points.data_ptr()), n, k, flags,
+                                                           C.c_void_p(out.data_ptr()) if k else None, C.c_void_p(counts.data_ptr())))
+        self.sync()
+        return _record_views(out, "dist", "p"), counts
 
     def sign_info(self):
         """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed

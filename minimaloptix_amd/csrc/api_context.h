@@ -249,7 +249,8 @@ struct moptix_context_t {
 
   // ---- point queries (api_point.hip): the stack overflow area of the point kernel, its own (eight bytes an entry: reference + box
   // distance), allocated at the first point query after a build and dropped with the tree it was sized for, where the ray queries' is;
-  // the staging of the host-pointer entry point ----
+  // the staging of the host-pointer entry point.  The K-nearest queries use all three as they are (out: the records, the counts behind
+  // them) ----
   struct Point {
     DevBuf<unsigned long long> overflow;
     DevBuf<float> points; DevBuf<uint8_t> out;

@@ -11,12 +11,14 @@
 // in LDS ([entry][lane], 32 KB per workgroup as the ray queries' 32 four-byte ones) with a global overflow column per thread.
 // The signed mode is the closest walk followed by point_hit_signed (pt_sign.h): the feature of the winner, one v3 of its sign record, the
 // sign.  Its argument record carries the table behind the others' (PointSignedArgs), so the kernel is a template over the record too.
+// The K-nearest queries (pt_pointmulti.h) are a kernel of their own beside it, pt_pointquery_multi: the same grid, loop and stack.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "pt_lanestack.h"
 #include "pt_sign.h"
+#include "pt_pointmulti.h"
 #include "pointkernel.h"
 
 namespace pt {
@@ -72,6 +74,32 @@ __global__ void __launch_bounds__(kBlockThreads) pt_pointquery(const Args s) {
   }
 }
 
+// K nearest (pt_pointmulti.h): the same grid, loop and stack.  The K candidates of a point live in its own slice of the output while it is
+// walked (16-byte keys, turned into records in place at the end), so K costs no registers and no LDS: the lane holds the count, the total
+// and the K-th key.
+template <bool N64, bool ALL>
+__global__ void __launch_bounds__(kBlockThreads) pt_pointquery_multi(const PointMultiArgs a) {
+  __shared__ unsigned long long ldsStack[kWavesPerBlock * kLdsStack * 64];
+  const SceneView& sc = a.scene;
+  const int gthread = blockIdx.x * kBlockThreads + threadIdx.x, stride = gridDim.x * kBlockThreads;
+  PointStack st;
+  st.init(ldsStack, a.stackOverflow, gthread, stride);
+  const uint4* __restrict__ points = reinterpret_cast<const uint4*>(a.points);
+  for (int i = gthread; i < a.n; i += stride) {           // n x max(maxNear, 1) <= kPointMaxLaunch: the record index fits 32 bits too
+    const uint4 r = points[(size_t)i];
+    const float p[4] = { i2f((int32_t)r.x), i2f((int32_t)r.y), i2f((int32_t)r.z), i2f((int32_t)r.w) };
+    const v3 q = mk3(p[0], p[1], p[2]);
+    const float r2 = p[3] * p[3];
+    PointTrav tv;
+    NearList nl;
+    nl.init(static_cast<Word4*>(a.hits) + 2 * (size_t)i * (size_t)a.maxNear, a.maxNear);      // maxNear 0: never dereferenced
+    pointmulti_begin<ALL>(sc, q, r2, point_valid(p), tv, nl);
+    while (tv.node != kTravDone) pointmulti_step<ALL, N64>(sc, q, r2, tv, st, nl);
+    pointmulti_finish(sc, q, p[3], nl);
+    a.counts[i] = ALL ? nl.total : nl.count;
+  }
+}
+
 }  // namespace
 
 size_t pointkernel_overflow_entries(int nBlocks, int stackBound) { return lane_stack_overflow_entries((size_t)nBlocks * kBlockThreads, stackBound, kLdsStack); }
@@ -89,6 +117,19 @@ hipError_t launch_pointquery(hipStream_t stream, const PointArgs& a, const SignR
   } else {
     if (n64) pt_pointquery<POINT_CLOSEST, true><<<blocks, kBlockThreads, 0, stream>>>(a);
     else     pt_pointquery<POINT_CLOSEST, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_pointquery_multi(hipStream_t stream, const PointMultiArgs& a, int nBlocks, bool countAll) {
+  const int blocks = (int)std::min<long long>(nBlocks, ((long long)a.n + kBlockThreads - 1) / kBlockThreads);
+  const bool n64 = a.scene.nodes64 != nullptr;
+  if (countAll) {
+    if (n64) pt_pointquery_multi<true, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery_multi<false, true><<<blocks, kBlockThreads, 0, stream>>>(a);
+  } else {
+    if (n64) pt_pointquery_multi<true, false><<<blocks, kBlockThreads, 0, stream>>>(a);
+    else     pt_pointquery_multi<false, false><<<blocks, kBlockThreads, 0, stream>>>(a);
   }
   return hipGetLastError();
 }

@@ -15,20 +15,17 @@
 //   multi_finish     turns the keys into records in place, from the last to the first (record j covers keys 2j and 2j + 1, both read
 //                    before), through query_hit on a Trav per key: the bits are the closest query's by construction.  A triangle's
 //                    barycentrics are not kept in the key: tri_test on the same ray and record gives them again, bit for bit.
-// The slice is read and written as Word4 only, keys and records alike, so nothing is accessed through two types.
+// The slice is read and written as Word4 only (pt_word4.h, with key_less, the order of two keys), keys and records alike, so nothing is
+// accessed through two types.
 // Used by the query kernel (querykernel.hip) and by its CPU mirror (tests/hostsim/multihitsim.cpp).
 #pragma once
 #include "pt_query.h"
+#include "pt_word4.h"
 
 namespace pt {
 
 enum { MULTI_COUNT_ALL = 1 };
 constexpr int kMultiMaxHits = 64;
-
-struct alignas(16) Word4 { uint32_t x, y, z, w; };
-PT_HD Word4 mkw4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { Word4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-
-PT_HD bool key_less(float t, int prim, float tb, int primb) { return (t < tb) | ((t == tb) & (prim < primb)); }
 
 struct HitList {
   Word4* e;         // the ray's K records; while walking, its K keys (t, prim, tri, 0), ascending
