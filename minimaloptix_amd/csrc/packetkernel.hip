@@ -31,6 +31,7 @@
 //   * round 22: a third compile-time switch of the body, SWITCH, beside AUX and GLASS (all three are described in front of the kernels below): the
 //     NEAR = false slim kernels take a packet's next ray up in the scheduler loop's leave handler where a ray ends in the node loop, and their leaf
 //     pass has no switch arm; every other kernel keeps the hop through the leaf ring (kSwitchRef);
+//   * round 24: DIET, four 4.3-clock vector instructions per node step taken out of the slim kernels at compile time (in front of the kernels below);
 //   * this file is compiled twice (Makefile): as it stands for the 64-byte-node instantiations, with LLVM's max-ilp scheduling, and through
 //     packetkernel_n128.hip (PT_PK_N128) for the 128-byte-node ones with the default strategy -- each is a few per cent slower under the other's.
 //
@@ -185,22 +186,44 @@ constexpr bool kLeafKeepsSwitchArm = true;
 #else
 constexpr bool kLeafKeepsSwitchArm = false;
 #endif
+// DIET (round 24): four 4.3-clock vector instructions per node step that the slim launch cannot need, taken out at compile time.  All four slim kernels
+// have it (their pins hold, profiles/r24_kernel_resources.txt); the twins and the general kernels do not and stay what they were.
+//   * the node loop's header finds the lanes at a node by ONE compare whose scalar register pair is the lane mask (the ballot of the three-part
+//     bool was a 0 / 1 select and a second compare, two 4.3-clock instructions per node step);
+//   * the slab test takes tmin and tbest into single v_max_f32 / v_min_f32 (pt_path.h lean_max / lean_min) where the compiler put a canonicalising
+//     v_max_f32 x, x in front of each, every step, because it cannot see that a kernel argument and an LDS word are not signalling NaNs.
+// Coffee 287.08 -> 282.61 ms (profiles/r24_diet_ab.txt).  Two more groups were built and measured on top and are NOT in the code, being no gain by
+// the project's rule (+0.2 to +0.3 ms, inside the spread): a leaf pass of one chunk for trees with leaves of at most four triangles, and the lens
+// sample's rejection test on the squared length (NOTEBOOK.md round 24).
+// -DPT_PK_NO_DIET_NODE (experiment build): the slim kernels of round 23, instruction for instruction.
+#ifdef PT_PK_NO_DIET_NODE
+constexpr bool kSlimDietNode = false;
+#else
+constexpr bool kSlimDietNode = true;
+#endif
+// tmin reaches the slab test's v_max_f32 through a vector register: one v_mov_b32 per step, and a v_readlane_b32 where its scalar register is a spilled one.  As the instruction's scalar operand it needs none
+// and was SLOWER: coffee 283.89 ms against 281.76 (parent 286.21; profiles/r24_diet_ab.txt), with one spilled scalar register more in every slim
+// kernel -- in the 128-byte-node NEAR = false one 19, past its twin's 18 (tests/test_packet_resources_cpu.py).  That form is not kept.
+using DietStack = LdsStack<kStackN, true, true>;      // pt_path.h node_step_nearfar, stack_diet: lean_max / lean_min for tmin and tbest
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel(const LaunchArgs a) {
   constexpr int F = 0;
   constexpr bool AUX = kSlimKeepsAux, GLASS = NEAR || kSlimKeepsGlass, SWITCH = kSlimSwitches && !kSlimKeepsAux && !NEAR;
+  constexpr bool DIET_NODE = kSlimDietNode && !AUX;
 #include "packetkernel_body.h"
 }
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_aux(const LaunchArgs a) {
   constexpr int F = 0;
   constexpr bool AUX = true, GLASS = true, SWITCH = false;
+  constexpr bool DIET_NODE = false;
 #include "packetkernel_body.h"
 }
 template <bool CNT, bool SHARED, bool FAST = false, bool NEAR = false, bool N64 = false>
 __global__ void __launch_bounds__(kBlockThreads, kWavesPerSimd) pt_packetkernel_general(const LaunchArgs a) {
   constexpr int F = FEAT_ALL;
   constexpr bool AUX = true, GLASS = true, SWITCH = false;
+  constexpr bool DIET_NODE = false;
 #include "packetkernel_body.h"
 }
 

@@ -10,6 +10,14 @@
   static_assert(GLASS || !NEAR, "a scene whose shadow rays keep their nearest candidate has a Disney GLASS material");
   static_assert(!SWITCH || !AUX, "the ray switch of the leave handler writes the flag word with a plain store");
   static_assert(SHARED, "the workgroup's waves share one pool: per-wave pools are gone");      // the parameter is kept for the kernels' symbol names only
+// DIET_NODE (the slim kernels; packetkernel.hip says what it takes out): lane masks by the ballot builtin on
+// the bool.  That alone is the compare's own scalar register pair only where the bool IS one compare of the same basic block (the node loop's
+// header and the idle-lane test below are written that way); the mask of a bool that was combined from several, or came from another block, is
+// still a 0 / 1 select and a compare of that with 0 (three sites are left: the switch test of the leave handler, two in the batch loop).
+  static_assert(F == 0 || !DIET_NODE, "the diet is the slim build's");
+  using BodyStack = std::conditional_t<DIET_NODE, DietStack, SlotStack>;
+#undef PT_BALLOT
+#define PT_BALLOT(p) (DIET_NODE ? __builtin_amdgcn_ballot_w64(p) : __ballot(p))
   constexpr int NS = kP * kWaves;                        // slots per pool
   __shared__ PoolLds<NS> sPool[1];                       // (an array of one, as in queuekernel.hip)
   __shared__ WavePriv<NS> sPriv[kWaves];                 // rings sized exactly (packetkernel.hip ring_wrap)
@@ -41,7 +49,7 @@
   int nDone = 0;
 
   auto q_pop = [&](int q, bool want) -> int {
-    const unsigned long long m = __ballot(want);
+    const unsigned long long m = PT_BALLOT(want);
     const int n = min((int)__popcll(m), qCount[q]);      // (int): min(long long, int) resolves to the double overload
     int slot = -1;
     if (want) { const int r = lane_rank(m); if (r < n) slot = W.queue[q][ring_wrap<NS>(qHead[q] + r)]; }
@@ -68,7 +76,7 @@
     if (lane == 0) __hip_atomic_store(&W.lock, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   auto make_stack = [&](int slot) {
-    SlotStack st;
+    BodyStack st;
     st.lds = (lds_int*)&W.stack[slot][1];
     st.ovf = ovfBase ? reinterpret_cast<int*>(reinterpret_cast<char*>(ovfBase) + (uint32_t)((uint32_t)slot * (uint32_t)a.ovfDepth * 4u)) : nullptr;      // 32-bit offset: a pool's overflow area is far below 4 GB
     return st;
@@ -173,27 +181,27 @@
   int localDone = 0;
   auto local_push = [&](int dest, int slot) {   // wave-collective; dest per lane
     {
-      const unsigned long long m = __ballot(dest == Q_NODE);
+      const unsigned long long m = PT_BALLOT(dest == Q_NODE);
       if (m != 0ull) {
         if (dest == Q_NODE) myNodeQ[ring_wrap<NS>(nqHead + nqCount + lane_rank(m))] = (unsigned short)slot;
         nqCount += __popcll(m);
       }
     }
     {
-      const unsigned long long m = __ballot(dest == Q_LEAF);
+      const unsigned long long m = PT_BALLOT(dest == Q_LEAF);
       if (m != 0ull) {
         if (dest == Q_LEAF) myLeafQ[(lqHead + lqCount + lane_rank(m)) & 255] = (unsigned short)slot;
         lqCount += __popcll(m);
       }
     }
     for (int d = 0; d < 2; d++) {
-      const unsigned long long m = __ballot(dest == Q_SHADE + d);
+      const unsigned long long m = PT_BALLOT(dest == Q_SHADE + d);
       if (m != 0ull) {
         if (dest == Q_SHADE + d) sPriv[wave].outbox[d][obCount[d] + lane_rank(m)] = (unsigned short)slot;
         obCount[d] += __popcll(m);
       }
     }
-    localDone += __popcll(__ballot(dest == DEST_DONE));
+    localDone += __popcll(PT_BALLOT(dest == DEST_DONE));
   };
 
   // ---- leaf pass: the slots popped from Q_LEAF stand at a leaf ----
@@ -202,8 +210,8 @@
     SceneView scl = a.scene; scl.shadowNearest = NEAR ? 1 : 0;
     const SceneView& sc = scl;
     const bool have = slot >= 0;
-    if (CNT) { leafPasses++; leafLanes += (uint32_t)__popcll(__ballot(have)); }
-    PT_EV(7, __popcll(__ballot(have)));
+    if (CNT) { leafPasses++; leafLanes += (uint32_t)__popcll(PT_BALLOT(have)); }
+    PT_EV(7, __popcll(PT_BALLOT(have)));
     pendSlot = slot; pendDest = DEST_NONE;
     // slot records written by earlier passes of this wave (other lanes) or published by other waves: the stores
     // of the previous pass were left in flight, so they are ordered here, where their latency has already elapsed
@@ -261,7 +269,7 @@
         } else { if (!shadow && hitValid) tv.bestPrim = kPrimUnknown; }
         const int oldPrim = tv.bestPrim;
         [[maybe_unused]] const v3 oldAtt = tv.att;
-        SlotStack st = make_stack(slot);
+        BodyStack st = make_stack(slot);
         trav_leaf_step_fetched<CNT, GLASS>(sc, ps, tv, st, ct, ch);
         int nfl = fl & ~kSpMask;
         if (!GLASS && shadow) {
@@ -320,8 +328,8 @@
     SceneView scl = a.scene; scl.shadowNearest = NEAR ? 1 : 0;
     const SceneView& sc = scl;
     const bool have = slot >= 0;
-    if (CNT) { batches++; batchLanes += (uint32_t)__popcll(__ballot(have)); }
-    PT_EV(1, __popcll(__ballot(have)));
+    if (CNT) { batches++; batchLanes += (uint32_t)__popcll(PT_BALLOT(have)); }
+    PT_EV(1, __popcll(PT_BALLOT(have)));
     PT_SUB0();
     pendSlot = slot; pendDest = DEST_NONE;
     PathState ps; Trav res;
@@ -399,13 +407,13 @@
       }
       // lanes that arrive with a finished packet go first; the lanes that only need a new work item wait for them, so
       // that begin_sample + the ray set-up run once, for all of them together
-      const bool resultFirst = __ballot(have && ps.mode == M_RESULT) != 0ull;
+      const bool resultFirst = PT_BALLOT(have && ps.mode == M_RESULT) != 0ull;
       const bool run = have && ps.mode != M_TRACE && ps.mode != M_DONE &&
                        !((shadeBatch || resultFirst) && ps.mode == M_NEW_PIXEL);
-      if (__ballot(run) == 0ull) break;
+      if (PT_BALLOT(run) == 0ull) break;
       if (CNT) {   // which state-machine stages this iteration executes (wave level)
-        if (__ballot(run && ps.mode == M_RESULT)) nIterResult++;
-        if (__ballot(run && ps.mode == M_NEW_PIXEL)) nIterGen++;
+        if (PT_BALLOT(run && ps.mode == M_RESULT)) nIterResult++;
+        if (PT_BALLOT(run && ps.mode == M_NEW_PIXEL)) nIterGen++;
       }
       if (run) {
         if (ps.mode == M_RESULT) {
@@ -519,12 +527,12 @@
       }
     }
     if constexpr (AUX) {
-    if (auxOn && __ballot(useAux) != 0ull) {                // the borrowed slots start at the root, with this wave
+    if (auxOn && PT_BALLOT(useAux) != 0ull) {                // the borrowed slots start at the root, with this wave
       for (int j = 0; j < kPacketShadows; j++) local_push((useAux && j < pk.nShadow) ? Q_NODE : DEST_NONE, (axp >> (kSlotBits * j)) & kSlotMask);
     }
     }
     PT_SUB(tBStore);
-    PT_EV(4, __popcll(__ballot(useAux)));
+    PT_EV(4, __popcll(PT_BALLOT(useAux)));
   };
 
   unsigned int guard = 0;
@@ -534,7 +542,7 @@
     // that has travelled through the pass in between (which waited for its own, later, loads).  In front of the watchdog on purpose: no switch is
     // ever pending where the loop is left, the slot of one is back on a ring like every other slot.
     if constexpr (SWITCH) {
-      const unsigned long long m = __ballot(swSlot >= 0);
+      const unsigned long long m = PT_BALLOT(swSlot >= 0);
       if (m != 0ull) {
         if (swSlot >= 0) {
           // the row goes to LDS as it was loaded and the root reference over its fourth word (same wave, same address: LDS keeps the order).
@@ -551,16 +559,16 @@
     if ((++guard & 4095u) == 0u && __builtin_amdgcn_s_memrealtime() - wdStart > a.watchdogTicks) { if (lane == 0) atomicOr(a.workCounter + 1, 1); break; }
     PT_SUB0(); if (CNT) nIter++;
     // ---- local bookkeeping (no lock): results of the last pass, swap, refill ----
-    if (__ballot(pendDest != DEST_NONE) != 0ull) { local_push(pendDest, pendSlot); pendDest = DEST_NONE; }
+    if (PT_BALLOT(pendDest != DEST_NONE) != 0ull) { local_push(pendDest, pendSlot); pendDest = DEST_NONE; }
     {
       const bool leave = ns >= 0 && !(ntv.node >= 0 && ntv.node != kTravDone);
-      if (__ballot(leave) != 0ull) {
+      if (PT_BALLOT(leave) != 0ull) {
         int dest = DEST_NONE, pushSlot = ns;
         // SWITCH: ray done, packet not -- the lane asks for the packet's next ray itself and pushes nothing; the top of the next iteration finishes it
         bool sw = false;
         if constexpr (SWITCH) {
           sw = leave && ntv.node == kTravDone && fl_more(nsFlag);
-          if (__ballot(sw) != 0ull) {
+          if (PT_BALLOT(sw) != 0ull) {
             // the row was written by another lane of this wave in an earlier batch, or published by another wave: ordered as in leaf_pass
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -589,8 +597,10 @@
         local_push(dest, pushSlot);
         if (leave) ns = -1;
       }
-      if (nqCount > 0 && __ballot(ns < 0) != 0ull) {
-        const unsigned long long m = __ballot(ns < 0);
+      [[maybe_unused]] unsigned long long mIdle = 0ull;       // DIET_NODE: one ballot, in the block of its compare (see the node loop's header)
+      if constexpr (DIET_NODE) mIdle = __builtin_amdgcn_ballot_w64(ns < 0);
+      if (nqCount > 0 && (DIET_NODE ? mIdle : PT_BALLOT(ns < 0)) != 0ull) {
+        const unsigned long long m = DIET_NODE ? mIdle : PT_BALLOT(ns < 0);
         const int n = min((int)__popcll(m), nqCount);
         if (ns < 0) {
           const int r = lane_rank(m);
@@ -609,11 +619,11 @@
         nqHead = ring_wrap<NS>(nqHead + n); nqCount -= n;
       }
     }
-    const int nActive = __popcll(__ballot(ns >= 0));
+    const int nActive = __popcll(PT_BALLOT(ns >= 0));
     const bool starving = nActive <= 64 - a.starveLanes;
     // lanes with work in flight: a pending ray switch (SWITCH) is a slot in no ring, so a wave that holds one neither idles nor leaves the loop
     int nBusy = nActive;
-    if constexpr (SWITCH) nBusy += __popcll(__ballot(swSlot >= 0));
+    if constexpr (SWITCH) nBusy += __popcll(PT_BALLOT(swSlot >= 0));
     int pass = -1;      // -1 node loop, 0 leaf, 1 shade, 2 gen, 3 idle, 4 exit
     int mySlot = -1;
     auto leaf_pop = [&]() -> int {              // up to 64 slots from this wave's own leaf ring
@@ -672,7 +682,7 @@
     // ---- node loop: until swapLanes lanes have left the node set ----
     if (CNT) { nodeRuns++; ringBacklog += (unsigned long long)nqCount; leafBacklog += (unsigned long long)lqCount; }
     {
-      SlotStack st = make_stack(ns >= 0 ? ns : 0);
+      BodyStack st = make_stack(ns >= 0 ? ns : 0);
       PT_EV(5, nActive);
 #ifdef PT_EVLOG
       int evSteps = 0;
@@ -681,8 +691,12 @@
 #ifdef PT_EVLOG
         evSteps++;
 #endif
-        const bool atNode = ns >= 0 && ntv.node >= 0 && ntv.node != kTravDone;
-        const unsigned long long m = __ballot(atNode);
+        // DIET_NODE: one compare, and the lane mask is that compare's own scalar register pair (the ballot of the three-part bool came out as a
+        // 0 / 1 select and a compare of that with 0, every step).  node >= 0 && node != kTravDone is one unsigned compare, kTravDone being the
+        // largest int; and a lane without a slot never stands at a node: ns becomes -1 only in the leave handler, which takes lanes whose node
+        // is a leaf or kTravDone (as at start-up), and the node changes only with a new slot or in a step of this loop.
+        const bool atNode = DIET_NODE ? (uint32_t)ntv.node < (uint32_t)kTravDone : (ns >= 0 && ntv.node >= 0 && ntv.node != kTravDone);
+        const unsigned long long m = PT_BALLOT(atNode);
         const int n = __popcll(m);
         if (n == 0 || nActive - n >= a.swapLanes) break;
         if (CNT) { nodeSteps++; nodeLanes += (uint32_t)n; }

@@ -11,6 +11,8 @@
 // which is what lets the kernel leave the traversal loop when too few lanes of the wave
 // are still traversing (wave-level re-fill) and come back later.
 #pragma once
+#include <type_traits>
+
 #include "pt_types.h"
 #include "pt_rng.h"
 #include "pt_geom.h"
@@ -283,6 +285,21 @@ struct ChildKey {
 #ifndef PT_STACK_ROOMY
 #define PT_STACK_ROOMY 1
 #endif
+// A stack type that declares kDiet = true (pt_sched.h LdsStack, the packet kernel's slim build) takes tmin and tbest into the slab test through
+// lean_max / lean_min: one v_max_f32 / v_min_f32 each.  llvm.maxnum / minnum on a value the compiler cannot prove canonical -- tmin is a kernel
+// argument, tbest an LDS word that stays in a register over a run of steps -- gets a canonicalising v_max_f32 x, x in front, per step (the
+// ChildKey::order story in binary32).  Neither value is a NaN; on everything else, a quiet NaN from the plane arithmetic included (both forms
+// return the other operand), the instruction is fmaxf / fminf: same values, same comparisons.  (tmin lives in a scalar register and costs a
+// v_mov_b32 per step this way.  Read as the instruction's scalar operand it costs nothing, and measured SLOWER: packetkernel.hip, DIET.)
+template <class Stack, class = void> struct stack_diet { static constexpr bool value = false; };
+template <class Stack> struct stack_diet<Stack, std::void_t<decltype(Stack::kDiet)>> { static constexpr bool value = Stack::kDiet; };
+#if defined(__HIP_DEVICE_COMPILE__)
+PT_HD float lean_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+PT_HD float lean_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+#else
+PT_HD float lean_min(float a, float b) { return fminf_(a, b); }
+PT_HD float lean_max(float a, float b) { return fmaxf_(a, b); }
+#endif
 // The slab tests, the sort and the pushes of one four-child node whose plane distances are known: tnr / tfr = distance to
 // the plane of child k's box the ray meets first / last, per axis.  needTest[k]: child k may be an unused slot.
 template <bool CNT, class Stack>
@@ -296,8 +313,14 @@ PT_HD void node_step_nearfar(const PathState& ps, Trav& tv, Stack& st, Counters&
 #pragma unroll
 #endif
   for (int c = 0; c < 4; c++) {
-    const float tn = fmaxf_(fmaxf_(nx[c], ny[c]), fmaxf_(nz[c], ps.tmin));
-    const float tf = fminf_(fminf_(fx[c], fy[c]), fminf_(fz[c], tv.tbest));
+    float tn, tf;
+    if constexpr (stack_diet<Stack>::value) {
+      tn = fmaxf_(fmaxf_(nx[c], ny[c]), lean_max(ps.tmin, nz[c]));
+      tf = fminf_(fminf_(fx[c], fy[c]), lean_min(fz[c], tv.tbest));
+    } else {
+      tn = fmaxf_(fmaxf_(nx[c], ny[c]), fmaxf_(nz[c], ps.tmin));
+      tf = fminf_(fminf_(fx[c], fy[c]), fminf_(fz[c], tv.tbest));
+    }
     const bool in = (c < 2) ? (tn <= tf * 1.0000005f) : (tn <= tf * 1.0000005f && r[c] != kEmptyRef);
     k[c] = ChildKey::make(in ? tn : kFar, r[c]);
   }

@@ -36,7 +36,8 @@ typedef __attribute__((address_space(3))) int lds_int;
 // FLAT: pt_path.h node_step_nearfar's branch-free tail -- m pushes on top of sp entries stay in LDS and entry sp exists (the dead store of a
 // step that enters nothing lands there); the entry a pop would take (sp - 1; for sp = 0 the slot's flag word, unused).  Without it the stack
 // takes the branched tail.
-template <int STACKN, bool FLAT>
+// DIET (packetkernel.hip, the slim kernels): the node step's slab test takes tmin and tbest without a canonicalising instruction (pt_path.h stack_diet).
+template <int STACKN, bool FLAT, bool DIET = false>
 struct LdsStack {
   lds_int* lds;           // &stack[slot][1]
   int* ovf;               // this slot's overflow area in HBM (or nullptr)
@@ -51,6 +52,7 @@ struct LdsStack {
   __device__ __forceinline__ bool roomy(int sp) const { return sp + 3 <= STACKN; }     // three pushes stay in LDS
   __device__ __forceinline__ void store_fast(int sp, int v) { lds[sp] = v; }
   static constexpr bool kFlat = FLAT;
+  static constexpr bool kDiet = DIET;
   __device__ __forceinline__ bool fits_fast(int sp, int m) const { return FLAT && sp + m <= STACKN && sp < STACKN; }
   __device__ __forceinline__ int peek_fast(int sp) const { if constexpr (FLAT) return lds[min(sp, STACKN) - 1]; else return 0; }
 };
