@@ -92,6 +92,11 @@ def hostsim_lib():
         sig("refitsim_update", [vp, C.c_int32, C.c_int32, f32p, f32p])
         sig("refitsim_refit", [vp])
         sig("refitsim_read", [vp, C.POINTER(RefitsimOut)])
+        # the Disney functions one call at a time, on a material record (disneysim.cpp)
+        mp = C.POINTER(K.Material)
+        sig("disneysim_sample", [mp, C.c_int64, f32p, f32p, u32p, f32p, f32p])
+        sig("disneysim_pdf", [mp, C.c_int64, f32p, f32p, f32p, f32p])
+        sig("disneysim_eval", [mp, C.c_int64, f32p, f32p, f32p, f32p, f32p])
         # the image-space mirrors (denoisesim.cpp, temporalsim.cpp, adaptivesim.cpp)
         sig("denoisesim_run", [C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_float, C.POINTER(K.DenoiseParams), f32p])
         sig("denoisesim_exp_ac", [f32p, f32p, C.c_int], None)
