@@ -797,6 +797,60 @@ int moptix_query_points_multi_device(moptix_context ctx, const float* dPoints, i
 int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n, int32_t maxNear, uint32_t flags,
                               moptix_point_hit* hits, int32_t* counts);
 
+/* ---- box queries: the primitives that meet each of the caller's axis-aligned boxes ---------------------------------------------------
+ * The range question neither the rays nor the points answer (a point query with maxDist tests a ball): voxelising a mesh into an
+ * occupancy grid, a broad phase that returns candidate faces per cell, box selection of faces, culling a region before a costlier
+ * query -- on the tree the rays walk, refitted with it.
+ * A box is six floats  lox loy loz hix hiy hiz.  Valid: all six finite and lo <= hi on every axis; lo == hi is allowed, so a box may be
+ * a point, a segment or a rectangle.  An invalid box overlaps nothing, decided before any traversal.
+ * Boxes and primitives are closed sets: touching counts.  All arithmetic is binary32 under the contract of csrc/pt_math.h, without
+ * contraction; csrc/pt_box.h states every operation in order.  S(box) is the set of primitive ids whose predicate holds; ids are the
+ * queries' (spheres, then quads, then triangles by original face id); every primitive counts, whatever its material.  S is a function of
+ * the box and the device records alone.
+ *   triangle   the record's triangle as the point queries see it (v0 = p0, v1 = p0 + e0, v2 = p0 - e1), by the 13-axis separating-axis
+ *              test in three steps, any of which may reject: (A) the per-axis min / max of the computed vertices against lo / hi, exact
+ *              comparisons; (B) with c = lo * 0.5 + hi * 0.5, h = hi * 0.5 - lo * 0.5, u_i = v_i - c and the edges f0 = u1 - u0,
+ *              f1 = u2 - u1, f2 = u0 - u2, the nine axes a = cross(e_k, f_j), each as its two-term expression: p_i = dot(a, u_i) over the
+ *              non-zero terms, r = h . |a|, reject if min p > r or max p < -r; (C) n = cross(f0, f1), d = dot(n, u0), r = dot(h, |n|),
+ *              reject if |d| > r.  Rejections are strict, so a NaN or an equality rejects nothing; a zero-area triangle needs no special
+ *              case.
+ *   sphere     the surface: dmin2 = the squared distance from the centre to the box, dmax2 = the sum over the axes of
+ *              max(|c - lo|, |hi - c|)^2, r2 = radius * radius; overlap iff dmin2 <= r2 and dmax2 >= r2.  A box wholly inside the ball
+ *              meets nothing.
+ *   quad       the four corners (anchor + E1 * a1) + E2 * a2 at a in {0, 1} of the point queries' parametrisation; the triangles
+ *              (c00, c10, c11) and (c00, c11, c01) through the triangle predicate; the quad overlaps if either does.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part, and there is no grazing exception: the walk
+ * enters a child iff its box and the query box overlap by exact comparisons, and csrc/pt_box.h proves from the builder's padding that this
+ * loses no primitive of S.
+ *   MOPTIX_BOX_ANY    one int32 per box: |S| > 0.  The walk stops at the first primitive accepted.
+ *   MOPTIX_BOX_COUNT  one int32 per box: |S|.
+ *   list              offsets: n + 1 int64 entries, non-decreasing, into prims (int32): the capacity of box i is
+ *                     offsets[i + 1] - offsets[i]; a negative capacity reads as 0.  counts[i] = |S| always.  If |S| <= capacity the slice
+ *                     holds S in ascending id, then -1 up to the capacity; otherwise the whole slice is -1 and the caller sees
+ *                     counts[i] > capacity.  Every byte of every slice is defined and nothing of the answer depends on the tree; the K
+ *                     lowest ids of a longer set are deliberately not offered.  The ids are appended to the box's own slice while they
+ *                     fit and sorted there in place: nothing else is allocated.
+ *   moptix_query_boxes_device       dBoxes: device memory, 8-byte aligned (a box is read as three 8-byte loads); dOut: device memory,
+ *                                   4-byte aligned.  Asynchronous on the context's stream.
+ *   moptix_query_boxes              host pointers, blocking: upload, query, read back (staging kept in the context)
+ *   moptix_query_boxes_list_device  dBoxes, dOffsets: 8-byte aligned; dPrims, dCounts: 4-byte aligned.  Asynchronous.  The offsets are
+ *                                   the caller's to get right: the kernel writes where they point.
+ *   moptix_query_boxes_list         host pointers, blocking; offsets are checked here: non-decreasing, offsets[0] >= 0.  prims is
+ *                                   written from offsets[0] to offsets[n].
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 boxes); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_points ("faces dirty" before a refit included).
+ * The box queries keep a stack overflow area of their own, sized like the others' by the tree's stack bound, the grid cap and
+ * "query_blocks_per_cu": allocated at the first box query on a tree, kept across refits, dropped by moptix_clear_scene, moptix_build_accel
+ * and moptix_destroy.  A box query changes nothing else in the context: moptix_debug_buffer_addresses keeps its slots, and the ray and
+ * point queries' buffers are untouched.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
+ * Not offered: oriented boxes, frusta, query triangles, filters by material or primitive kind. */
+enum { MOPTIX_BOX_ANY = 0, MOPTIX_BOX_COUNT = 1 };
+int moptix_query_boxes_device(moptix_context ctx, const float* dBoxes, int64_t n, int32_t mode, int32_t* dOut);
+int moptix_query_boxes(moptix_context ctx, const float* boxes, int64_t n, int32_t mode, int32_t* out);
+int moptix_query_boxes_list_device(moptix_context ctx, const float* dBoxes, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
+                                   int32_t* dCounts);
+int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
@@ -813,7 +867,7 @@ int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -828,7 +882,7 @@ int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray and point queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point and box queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

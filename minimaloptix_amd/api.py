@@ -76,6 +76,20 @@ def _point_rows(who, points, max_dist):
     return np.ascontiguousarray(pts, np.float32)
 
 
+def occupancy_boxes(lo, hi, dims):
+    """The cells of the regular grid of dims = (nx, ny, nz) cells between the corners lo and hi as (nx * ny * nz, 6) float32 boxes
+    lox loy loz hix hiy hiz, x slowest (row i * ny * nz + j * nz + k is cell (i, j, k)).  The cell planes come from one float32 linspace
+    per axis, so neighbouring cells share their planes exactly: a primitive on a shared plane meets both."""
+    lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError("occupancy_boxes: dims %r (three cell counts >= 1)" % (dims,))
+    planes = [np.linspace(lo[a], hi[a], dims[a] + 1, dtype=np.float32) for a in range(3)]
+    cells_lo = np.stack(np.meshgrid(*[p[:-1] for p in planes], indexing="ij"), axis=-1).reshape(-1, 3)
+    cells_hi = np.stack(np.meshgrid(*[p[1:] for p in planes], indexing="ij"), axis=-1).reshape(-1, 3)
+    return np.ascontiguousarray(np.concatenate([cells_lo, cells_hi], axis=1), np.float32)
+
+
 def _f3(v):
     return [float(v.x), float(v.y), float(v.z)]
 
@@ -737,6 +751,69 @@ class Context:
                                                            C.c_void_p(out.data_ptr()) if k else None, C.c_void_p(counts.data_ptr())))
         self.sync()
         return _record_views(out, "dist", "p"), counts
+
+    # ---- box queries (include/moptix.h "box queries") ----
+    BOX_MODES = dict(any=K.BOX_ANY, count=K.BOX_COUNT)
+
+    def query_boxes(self, boxes, mode="any", max_prims=None):
+        """The primitives that meet each of the caller's axis-aligned boxes lox loy loz hix hiy hiz (closed sets: touching counts);
+        blocking.  "any": int32, 1 where anything meets the box; "count": int32, how many primitives do; "list": which.
+        "list" with max_prims=None is two passes -- count, an int64 cumulative sum, fill -- and returns (prims, offsets), a CSR pair: the
+        ids of box i, ascending, are prims[offsets[i]:offsets[i + 1]].  "list" with max_prims=K is one pass with K slots per box and
+        returns (prims (n, K), counts): where counts[i] <= K the row holds the ids ascending and -1 behind them, else -1 throughout.
+        A numpy (n, 6) or (n, 2, 3) array takes the host path and the results are numpy arrays.  A contiguous (n, 6) float32 torch tensor
+        on this context's device is read where it is, and the results are tensors on that device."""
+        if mode not in self.BOX_MODES and mode != "list":
+            raise ValueError("query_boxes: mode %r (any, count or list)" % (mode,))
+        if max_prims is not None and (mode != "list" or int(max_prims) < 0):
+            raise ValueError("query_boxes: max_prims %r (a capacity >= 0, with mode \"list\" only)" % (max_prims,))
+        if isinstance(boxes, np.ndarray) or not hasattr(boxes, "data_ptr"):
+            b = np.asarray(boxes, np.float32)
+            if not ((b.ndim == 2 and b.shape[1] == 6) or (b.ndim == 3 and b.shape[1:] == (2, 3))):
+                raise ValueError("query_boxes: boxes must be (n, 6) or (n, 2, 3), not %r" % (b.shape,))
+            b = np.ascontiguousarray(b.reshape(-1, 6), np.float32)
+            n = len(b)
+            bp, i32p = b.ctypes.data_as(C.POINTER(C.c_float)), lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+            counts = np.zeros(n, np.int32)
+            if mode != "list" or max_prims is None:
+                self._chk(self._L.moptix_query_boxes(self._h, bp, n, self.BOX_MODES.get(mode, K.BOX_COUNT), i32p(counts)))
+                if mode != "list":
+                    return counts
+                offsets = np.zeros(n + 1, np.int64)
+                np.cumsum(counts, dtype=np.int64, out=offsets[1:])
+            else:
+                offsets = np.arange(n + 1, dtype=np.int64) * int(max_prims)
+            prims = np.zeros(int(offsets[-1]), np.int32)
+            self._chk(self._L.moptix_query_boxes_list(self._h, bp, n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), i32p(prims), i32p(counts)))
+            return (prims, offsets) if max_prims is None else (prims.reshape(n, int(max_prims)), counts)
+        import torch
+        _check_tensor("query_boxes", "boxes", boxes, ("torch.float32",), _rows(6), "shape (n, 6), lox loy loz hix hiy hiz", self.device)
+        n = boxes.shape[0]
+        dev = boxes.device
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        counts = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # the boxes are ready before the context's stream reads them
+        if mode != "list" or max_prims is None:
+            self._chk(self._L.moptix_query_boxes_device(self._h, ptr(boxes), n, self.BOX_MODES.get(mode, K.BOX_COUNT), ptr(counts)))
+            self.sync()
+            if mode != "list":
+                return counts
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        else:
+            offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * int(max_prims)
+        total = int(offsets[-1]) if n else 0
+        prims = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total]
+        torch.cuda.current_stream(dev).synchronize()      # offsets and the zeroed outputs too
+        self._chk(self._L.moptix_query_boxes_list_device(self._h, ptr(boxes), n, ptr(offsets), ptr(prims) if n else None, ptr(counts)))
+        self.sync()
+        return (prims, offsets) if max_prims is None else (prims.reshape(n, int(max_prims)), counts)
+
+    def occupancy(self, lo, hi, dims):
+        """The (nx, ny, nz) bool grid of query_boxes "any" over occupancy_boxes(lo, hi, dims): which cells of the regular grid between
+        the corners lo and hi anything of the scene meets; blocking, host path."""
+        nx, ny, nz = (int(d) for d in dims)
+        return self.query_boxes(occupancy_boxes(lo, hi, (nx, ny, nz)), "any").reshape(nx, ny, nz) != 0
 
     def sign_info(self):
         """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed

@@ -258,6 +258,16 @@ struct moptix_context_t {
     void release() { drop(); points.release(); out.release(); }
   } point;
 
+  // ---- box queries (api_box.hip): the stack overflow area of the box kernel, its own (four bytes an entry: a reference), allocated at
+  // the first box query after a build, kept across refits and dropped with the tree it was sized for, where the ray queries' is; the
+  // staging of the host-pointer entry points (boxes, offsets, prims; out: the int32 results or counts) ----
+  struct Box {
+    DevBuf<int> overflow;
+    DevBuf<float> boxes; DevBuf<long long> offsets; DevBuf<int> prims, out;
+    void drop() { overflow.release(); }
+    void release() { drop(); boxes.release(); offsets.release(); prims.release(); out.release(); }
+  } box;
+
   // ---- signed point queries (api_sign.hip) ----
   // The topology belongs to one set of uploaded faces: taken on the host at the first signed query or moptix_get_sign_info, kept across
   // moptix_update_faces*, moptix_refit_accel and moptix_build_accel, dropped by moptix_clear_scene, moptix_add_mesh and destroy.  Its
