@@ -6,6 +6,7 @@
 #   make hostsim    -> tests/hostsim/libhostsim.so              (test infrastructure: the CPU mirrors of the kernels, one library)
 #   make pointmultisim -> tests/pointmultisim/libpointmultisim.so (test infrastructure: the CPU mirror of the K-nearest point queries)
 #   make boxsim     -> tests/boxsim/libboxsim.so                (test infrastructure: the CPU mirror of the box queries)
+#   make devarith   -> tests/devarith/libdevarith.so           (test infrastructure: the contract's primitives, one kernel and one host function each)
 #   make loopback   -> tests/rccl_loopback/librccl_loopback.so  (test infrastructure: N ranks on one GPU without RCCL)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -32,7 +33,7 @@ HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(
 HOST_OBJS := $(patsubst $(HOST)/%.cpp,build/host_%.o,$(HOST_SRCS))
 HOST_HDRS := $(wildcard $(HOST)/*.h) $(wildcard $(CSRC)/pt_*.h) include/moptix.h include/moptix_host.h
 
-all: device host oracle hostsim pointmultisim boxsim loopback
+all: device host oracle hostsim pointmultisim boxsim devarith loopback
 
 device: $(LIBDIR)/$(LIBNAME)
 host: $(LIBDIR)/libmoptix_host.so $(LIBDIR)/moptix_render
@@ -44,6 +45,9 @@ pointmultisim:
 	$(MAKE) -C tests/pointmultisim -s
 boxsim:
 	$(MAKE) -C tests/boxsim -s
+# the product's flags, handed down and not restated: what these kernels pin is the arithmetic of THIS build
+devarith:
+	$(MAKE) -C tests/devarith -s HIPCC='$(HIPCC)' CXX='$(CXX)' ARCH='$(ARCH)' HIPFLAGS='$(HIPFLAGS)' CXXFLAGS='$(CXXFLAGS)'
 loopback:
 	$(MAKE) -C tests/rccl_loopback -s
 
@@ -75,6 +79,6 @@ $(LIBDIR)/moptix_render: $(HOST)/main.cpp $(LIBDIR)/libmoptix_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST)/main.cpp -L$(LIBDIR) -lmoptix_host -lmoptix -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/pointmultisim/libpointmultisim.so tests/boxsim/libboxsim.so tests/rccl_loopback/librccl_loopback.so
+	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/pointmultisim/libpointmultisim.so tests/boxsim/libboxsim.so tests/devarith/libdevarith.so tests/devarith/*.o tests/rccl_loopback/librccl_loopback.so
 
-.PHONY: all device host oracle hostsim pointmultisim boxsim loopback clean
+.PHONY: all device host oracle hostsim pointmultisim boxsim devarith loopback clean

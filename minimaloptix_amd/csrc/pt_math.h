@@ -74,14 +74,24 @@ PT_HD v3 normalize(v3 a) { float inv = 1.0f / __builtin_sqrtf(dot(a, a)); return
 PT_HD v3 ray_at(v3 o, v3 d, float t) { return mk3(fma_(t, d.x, o.x), fma_(t, d.y, o.y), fma_(t, d.z, o.z)); }  // AC7
 PT_HD float lerp(float a, float b, float t) { return a + t * (b - a); }
 PT_HD v3 lerp(v3 a, v3 b, float t) { return a + (b - a) * t; }
+// min / max: a NaN operand is MISSING, a signalling one included -- what llvm.minnum / maxnum give on the device (measured:
+// tests/test_gpu_devarith.py), while the host library's fminf / fmaxf return a NaN for a signalling one.  No operation of the contract
+// produces a signalling NaN; the host side says so explicitly so that both sides are one function on every operand.
+#if defined(__HIP_DEVICE_COMPILE__)
 PT_HD float fminf_(float a, float b) { return __builtin_fminf(a, b); }
 PT_HD float fmaxf_(float a, float b) { return __builtin_fmaxf(a, b); }
+#else
+PT_HD float fminf_(float a, float b) { return a != a ? b : b != b ? a : __builtin_fminf(a, b); }
+PT_HD float fmaxf_(float a, float b) { return a != a ? b : b != b ? a : __builtin_fmaxf(a, b); }
+#endif
 PT_HD float clampf(float x, float lo, float hi) { return fmaxf_(lo, fminf_(x, hi)); }
 PT_HD float sqr(float x) { return x * x; }
 // AC5: sin and cos as ONE specified binary32 algorithm (both sides of the parity contract evaluate exactly these
 // operations): quadrant q = floor(x*2/pi + 1/2), three-step Cody-Waite reduction r = x - q*pi/2 with fma, degree-7 /
 // degree-8 polynomials on |r| <= pi/4 (coefficients of the classic single-precision kernels), quadrant fix-up.
-// Absolute error < 2e-7 for |x| < 100; the path tracer only calls it with x in [0, 2 pi].
+// Absolute error < 2e-7 for |x| <= 100 (measured 9.3e-8 on [-100, 100], tests/test_devarith_cpu.py); the path tracer only calls it with x
+// in [0, 2 pi].  The contract ends at |x| <= 100: device and host agree on every float of [-100, 100] (tools/devarith_sweep.py); far beyond,
+// at |x| >= 3.4e9, (int)qf leaves the range of int, which is undefined in C++ (the device saturates, x86 gives INT_MIN).
 PT_HD void sincos_ac(float x, float& s, float& c) {
   const float qf = __builtin_floorf(fma_(x, 0.636619772f, 0.5f));
   float r = fma_(qf, -1.5703125f, x);

@@ -7,7 +7,9 @@
 
 namespace pt {
 
-// AC6: x^2.2 through double precision, so that host upload and device agree
+// AC6: x^2.2 through double precision, so that host upload and device agree.  The device library's pow and glibc's are different code;
+// they give the same binary32 value on every positive float, the 66 inputs within 16 binary64 ulps of a rounding boundary included
+// (tools/pow22_hard.py, tools/devarith_sweep.py, profiles/r27_devarith.txt).  Negative and NaN inputs give NaN on both sides.
 PT_HD float pow22(float x) { return (float)pow((double)x, (double)2.2f); }
 PT_HD v3 srgb2lin(v3 c) { return mk3(pow22(c.x), pow22(c.y), pow22(c.z)); }      // utils_device.h:173-175
 
@@ -25,6 +27,9 @@ PT_HD int tex_wrap(int i, int n) { i %= n; return i < 0 ? i + n : i; }
 
 // Bilinear fetch as CUDA texture units do it (OptiX 5 samplers are CUDA textures): texel centres at
 // +0.5, interpolation weights quantised to 8 fractional bits, repeat addressing of both taps.
+// The contract covers finite u, v (any magnitude: x and y lie in [-0.5, size), every cast is in range).  A non-finite coordinate makes
+// x or y a NaN and (int) of it undefined in C++ -- the device saturates, x86 gives INT_MIN, the results differ; tex_wrap still brings
+// any int into range, so nothing outside the texture is read.  tests/test_gpu_devarith.py pins the first and only calls the second.
 PT_HD v4 tex2d(const DevTexture& t, float u, float v) {
   const float x = (u - floorf(u)) * (float)t.width - 0.5f;
   const float y = (v - floorf(v)) * (float)t.height - 0.5f;

@@ -67,6 +67,7 @@ static inline void sincos_ac(float x, float* s, float* c) {
   }
 }
 void orc_sincos(float x, float* s, float* c) { sincos_ac(x, s, c); }
+void orc_sincos_n(const float* x, float* s, float* c, long n) { for (long i = 0; i < n; i++) sincos_ac(x[i], &s[i], &c[i]); }
 
 #define ORC_PI 3.14159265358979323846f  /* M_PIf */
 #define ORC_RT_DEFAULT_MAX 1e27f

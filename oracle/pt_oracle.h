@@ -160,6 +160,7 @@ void  orc_move_sphere(float center[3], float radius, float velocity[3], float ti
 /* rtTex2D<float4> restated (SURVEY A1 / CUDA linear filtering with 8-bit interpolation weights) */
 void  orc_tex2d(const OrcTexture* t, float u, float v, float out[4]);
 void  orc_sincos(float x, float* s, float* c);                /* AC5 */
+void  orc_sincos_n(const float* x, float* s, float* c, long n); /* the same over arrays (tests/test_devarith_cpu.py) */
 int   orc_num_threads(void);
 
 #ifdef __cplusplus
