@@ -851,6 +851,45 @@ int moptix_query_boxes_list_device(moptix_context ctx, const float* dBoxes, int6
                                    int32_t* dCounts);
 int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
 
+/* ---- sweep queries: the first contact of a moving sphere ---------------------------------------------------------------------------
+ * The continuous question the rays (no radius), the points (one instant) and the boxes (no time) leave open: a sphere of radius r moves
+ * from o along d; when does it first touch the scene, and where?  Continuous collision detection of particles against a mesh that is
+ * refitted every step, character and camera controllers, clearance checks of a motion, thick rays.
+ * A sweep is eight floats  ox oy oz dx dy dz radius tmax : the ray layout with radius in the tmin slot.  The centre is c(t) = o + d * t
+ * for t in [0, tmax], in units of |d|; d is used as given.  Invalid -- a miss, decided before any traversal: a non-finite component,
+ * d = 0, radius <= 0 or tmax <= 0 (a ray is the ray queries' business).
+ * All arithmetic is binary32 under the contract of csrc/pt_math.h, without contraction; csrc/pt_sweep.h states every operation in order.
+ * toi(prim) is the least t in [0, tmax] at which the sphere touches the primitive -- ids are the queries' (spheres, then quads, then
+ * triangles by original face id); every primitive counts, whatever its material:
+ *   triangle   the record's triangle as the point queries see it.  0 if the point query's d2 at o is <= radius^2, so a sweep that starts
+ *              in contact reports t = 0 exactly.  Otherwise the least of up to seven candidates: the face (the plane offset by radius
+ *              towards the origin's side, accepted by the point query's inside test), the three edges (ray against the cylinder, edge
+ *              parameter in [0, 1]) and the three vertices (ray against the sphere), each quadratic solved about the foot of the
+ *              perpendicular.  A zero-area triangle needs no special case; no NaN comes out of finite input.
+ *   sphere     from outside the ray against the surface at radius R + radius; from inside t = 0 if the surface is within radius of o, else
+ *              the root against R - radius where that is positive.
+ *   quad       the two triangles of the box queries' corners.
+ *   MOPTIX_SWEEP_CLOSEST  one moptix_sweep_hit (32 bytes) per sweep: the primitive least by (toi, prim); at exactly equal toi the lower
+ *                         id.  t = toi; p, u, v are the point query's nearest point and parameters for the centre c(t) = o + d * t on
+ *                         that primitive: the contact point.  The contact normal is (c(t) - p) / radius.  A miss: t = tmax as given,
+ *                         prim = mat = -1, u = v = p = 0.
+ *   MOPTIX_SWEEP_ANY      one int32 per sweep: 1 iff MOPTIX_SWEEP_CLOSEST reports a primitive.  The walk stops at the first contact.
+ * The answer is a function of the sweep and the device records alone: tree, leaf size, builder, node format, "query_blocks_per_cu" and
+ * scheduling play no part (csrc/pt_sweep.h derives the margins of the walk's prune from the builder's padding).
+ *   moptix_query_sweeps_device  dSweeps: device memory, 16-byte aligned; dOut: device memory, 16-byte aligned (closest) or 4-byte aligned
+ *                               (any).  Asynchronous on the context's stream.
+ *   moptix_query_sweeps         host pointers, blocking: upload, query, read back (staging kept in the context)
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 sweeps); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_points ("faces dirty" before a refit included).
+ * The sweep queries keep a stack overflow area of their own, sized like the others': allocated at the first sweep query on a tree, kept
+ * across refits, dropped by moptix_clear_scene, moptix_build_accel and moptix_destroy.  A sweep query changes nothing else in the
+ * context.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
+ * Not offered: swept boxes or capsules, rotating or growing spheres, all contacts along the path, filters by material. */
+enum { MOPTIX_SWEEP_CLOSEST = 0, MOPTIX_SWEEP_ANY = 1 };
+typedef struct { float t; int32_t prim; int32_t mat; float u, v; float p[3]; } moptix_sweep_hit;
+int moptix_query_sweeps_device(moptix_context ctx, const float* dSweeps, int64_t n, int32_t mode, void* dOut);
+int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int32_t mode, void* out);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
@@ -867,7 +906,7 @@ int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, c
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -882,7 +921,7 @@ int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, c
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray, point and box queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point, box and sweep queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

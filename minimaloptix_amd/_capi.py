@@ -174,6 +174,7 @@ POINT_CLOSEST, POINT_ANY, POINT_SIGNED = 0, 1, 2
 POINT_MULTI_COUNT_ALL = 1
 POINT_MULTI_MAX_NEAR = 64
 BOX_ANY, BOX_COUNT = 0, 1
+SWEEP_CLOSEST, SWEEP_ANY = 0, 1
 RADIANCE_CLAMP = 1
 
 
@@ -218,6 +219,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_points_device", "moptix_query_points", "moptix_query_points_signed", "moptix_get_sign_info", "moptix_debug_read_sign_table",
     "moptix_query_points_multi_device", "moptix_query_points_multi",
     "moptix_query_boxes_device", "moptix_query_boxes", "moptix_query_boxes_list_device", "moptix_query_boxes_list",
+    "moptix_query_sweeps_device", "moptix_query_sweeps",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -328,6 +330,8 @@ def device_lib():
         L.moptix_query_boxes.argtypes = [vp, f32p, C.c_int64, i32, i32p]
         L.moptix_query_boxes_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
         L.moptix_query_boxes_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
+        L.moptix_query_sweeps_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_sweeps.argtypes = [vp, f32p, C.c_int64, i32, vp]
         L.moptix_get_sign_info.argtypes = [vp, C.POINTER(SignInfo)]
         L.moptix_debug_read_sign_table.argtypes = [vp, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]

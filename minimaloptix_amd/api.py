@@ -13,6 +13,9 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), 
 assert HIT_DTYPE.itemsize == C.sizeof(K.Hit) == 32
 POINT_DTYPE = np.dtype([("dist", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("p", np.float32, (3,))])
 assert POINT_DTYPE.itemsize == C.sizeof(K.PointHit) == 32
+# moptix_sweep_hit as a numpy record (include/moptix.h "sweep queries")
+SWEEP_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("p", np.float32, (3,))])
+assert SWEEP_DTYPE.itemsize == 32
 
 
 def scenes_dir():
@@ -814,6 +817,42 @@ class Context:
         the corners lo and hi anything of the scene meets; blocking, host path."""
         nx, ny, nz = (int(d) for d in dims)
         return self.query_boxes(occupancy_boxes(lo, hi, (nx, ny, nz)), "any").reshape(nx, ny, nz) != 0
+
+    # ---- sweep queries (include/moptix.h "sweep queries") ----
+    SWEEP_MODES = dict(closest=K.SWEEP_CLOSEST, any=K.SWEEP_ANY)
+
+    def query_sweeps(self, sweeps, mode="closest"):
+        """The first contact of a sphere of radius `radius` whose centre moves from o along d, c(t) = o + d * t for t in [0, tmax]
+        ("closest"), or "does it touch anything on the way" ("any"), for the caller's sweeps ox oy oz dx dy dz radius tmax; blocking.
+        A numpy (n, 8) array takes the host path: "closest" returns a SWEEP_DTYPE record array (t, prim, mat, u, v, p: the time of
+        contact and the contact point; the contact normal is (o + d * t - p) / radius; a miss has prim -1 and t = tmax), "any" an int32
+        array.  A contiguous (n, 8) float32 torch tensor on this context's device is read where it is, and the results are tensors on
+        that device: "any" an int32 tensor; "closest" a dict of views t, prim, mat, u, v, p into "records", the (n, 8) float32 tensor of
+        the raw moptix_sweep_hit records."""
+        if mode not in self.SWEEP_MODES:
+            raise ValueError("query_sweeps: mode %r (closest or any)" % (mode,))
+        m = self.SWEEP_MODES[mode]
+        if isinstance(sweeps, np.ndarray) or not hasattr(sweeps, "data_ptr"):
+            s = np.asarray(sweeps, np.float32)
+            if s.ndim != 2 or s.shape[1] != 8:
+                raise ValueError("query_sweeps: sweeps must be (n, 8), not %r" % (s.shape,))
+            s = np.ascontiguousarray(s)
+            out = np.zeros(len(s), np.int32 if m == K.SWEEP_ANY else SWEEP_DTYPE)
+            self._chk(self._L.moptix_query_sweeps(self._h, s.ctypes.data_as(C.POINTER(C.c_float)), len(s), m, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        _check_tensor("query_sweeps", "sweeps", sweeps, ("torch.float32",), _rows(8), "shape (n, 8), ox oy oz dx dy dz radius tmax", self.device)
+        n = sweeps.shape[0]
+        if m == K.SWEEP_ANY:
+            out = torch.empty(n, dtype=torch.int32, device=sweeps.device)
+        else:
+            out = torch.empty((n, 8), dtype=torch.float32, device=sweeps.device)
+        torch.cuda.current_stream(sweeps.device).synchronize()      # the sweeps are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_sweeps_device(self._h, C.c_void_p(sweeps.data_ptr()), n, m, C.c_void_p(out.data_ptr())))
+        self.sync()
+        if m == K.SWEEP_ANY:
+            return out
+        return _record_views(out, "t", "p")
 
     def sign_info(self):
         """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed

@@ -268,6 +268,16 @@ struct moptix_context_t {
     void release() { drop(); boxes.release(); offsets.release(); prims.release(); out.release(); }
   } box;
 
+  // ---- sweep queries (api_sweep.hip): the stack overflow area of the sweep kernel, its own (eight bytes an entry: reference + entry
+  // time), allocated at the first sweep query after a build, kept across refits and dropped with the tree it was sized for, where the
+  // ray queries' is; the staging of the host-pointer entry point ----
+  struct Sweep {
+    DevBuf<unsigned long long> overflow;
+    DevBuf<float> sweeps; DevBuf<uint8_t> out;
+    void drop() { overflow.release(); }
+    void release() { drop(); sweeps.release(); out.release(); }
+  } sweep;
+
   // ---- signed point queries (api_sign.hip) ----
   // The topology belongs to one set of uploaded faces: taken on the host at the first signed query or moptix_get_sign_info, kept across
   // moptix_update_faces*, moptix_refit_accel and moptix_build_accel, dropped by moptix_clear_scene, moptix_add_mesh and destroy.  Its
