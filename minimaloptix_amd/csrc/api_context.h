@@ -124,11 +124,17 @@ struct moptix_context_t {
   double kernelMs = 0.0, reduceMs = 0.0; uint64_t nLaunches = 0;
   bool asyncPending = false;
   std::vector<int> seedStaging;
+  // Pinned staging of a batch's small uploads, the work header and the seeds (api_render.hip launch_staging): the copies from it are
+  // asynchronous, so moptix_render_async does not wait for the stream; the event behind the last copy says when it may be written again.
+  int* launchStaging = nullptr; size_t launchStagingInts = 0; hipEvent_t launchStaged = nullptr;
   DevBuf<int> dSeeds; DevBuf<int> dWork; DevBuf<unsigned long long> dCounters; DevBuf<int> dOverflow;
   DevBuf<uint8_t> dPoolCold; DevBuf<float> dSampleBuf;
   void release_render() {
     dSeeds.release(); dWork.release(); dCounters.release(); dOverflow.release(); dPoolCold.release(); dSampleBuf.release();
     tiles.release();
+    if (launchStaging) (void)hipHostFree(launchStaging);
+    if (launchStaged) (void)hipEventDestroy(launchStaged);
+    launchStaging = nullptr; launchStagingInts = 0; launchStaged = nullptr;
   }
   // which units (pixels or 8x8 tiles) had the deepest paths in earlier launches: they are handed out first (LaunchArgs::tileOrder);
   // forgotten by a new scene, partition or granularity
@@ -375,6 +381,7 @@ struct RenderLaunch {
   LaunchPlan p; LaunchArgs a;
   long long perPass;              // the plan's, after the out-of-memory halving
   int handoutDivisor, handoutSeeds;      // what the hand-out constants in front of the work counter were made for (megakernel.h handout_consts)
+  int* seedStaging;               // pinned room for the batch's nSeeds seeds, free to be written: who copies from it records c->launchStaged behind the copy
   bool counted, fast;
 };
 // What an adaptive pass hands to launch_pass instead of the defaults: its own order list (the first nWork / nSeeds entries are the

@@ -255,6 +255,20 @@ int evlog_write(moptix_context c, const DevBuf<unsigned long long>& evLog) {    
 
 namespace pt { namespace api {
 
+// The context's pinned staging, at least `ints` long and free to be written: whatever was copied from it last has left it.  That is the
+// only wait: an asynchronous render behind a busy stream does not wait for the stream.
+static int launch_staging(moptix_context c, size_t ints) {
+  if (!c->launchStaged) HIPCHK(c, hipEventCreateWithFlags(&c->launchStaged, hipEventDisableTiming), "create event");
+  else HIPCHK(c, hipEventSynchronize(c->launchStaged), "wait for the previous batch's uploads");
+  if (c->launchStagingInts < ints) {
+    if (c->launchStaging) (void)hipHostFree(c->launchStaging);
+    c->launchStaging = nullptr; c->launchStagingInts = 0;
+    HIPCHK(c, hipHostMalloc((void**)&c->launchStaging, sizeof(int) * ints, hipHostMallocDefault), "alloc launch staging");
+    c->launchStagingInts = ints;
+  }
+  return MOPTIX_OK;
+}
+
 int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelSlots, RenderLaunch& r) {
   int rc;
   if (!c->formatDecided && (rc = choose_node_format(c)) != MOPTIX_OK) return rc;
@@ -301,8 +315,12 @@ int prepare_launch(moptix_context c, int32_t nSeeds, bool counted, bool byPixelS
     struct { HandoutConsts hc; int hdr[2 + kDrainEntries]; } w = { handout_consts(p.tileMajor, a.nItems, (int)std::min<long long>(perPass, nSeeds), a.tilesX, a.nRanks),
                                                                    { 0, 0, 0, 0, 0, 0, p.nBlocks * p.drainBelow, p.drainBelow } };
     static_assert(sizeof(w) == sizeof(int) * (kHandoutWords + 2 + kDrainEntries), "the work header is packed");
-    HIPCHK(c, hipMemcpyAsync(c->dWork.p, &w, sizeof(w), hipMemcpyHostToDevice, c->stream), "init work counter");
-    HIPCHK(c, hipStreamSynchronize(c->stream), "sync");      // w lives on this stack frame
+    // through the pinned staging (the header, then room for the seeds): the copy is asynchronous and nothing here waits for the stream
+    if ((rc = launch_staging(c, sizeof(w) / sizeof(int) + (size_t)nSeeds)) != MOPTIX_OK) return rc;
+    memcpy(c->launchStaging, &w, sizeof(w));
+    r.seedStaging = c->launchStaging + sizeof(w) / sizeof(int);
+    HIPCHK(c, hipMemcpyAsync(c->dWork.p, c->launchStaging, sizeof(w), hipMemcpyHostToDevice, c->stream), "init work counter");
+    HIPCHK(c, hipEventRecord(c->launchStaged, c->stream), "event");
     r.handoutDivisor = handout_divisor(p.tileMajor, a.nItems, (int)std::min<long long>(perPass, nSeeds)); r.handoutSeeds = (int)std::min<long long>(perPass, nSeeds);
   }
   a.workCounter = c->dWork.p + kHandoutWords;
@@ -389,7 +407,11 @@ int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool count
   if (rc != MOPTIX_OK) return rc;
   if (nSeeds < 0 || (nSeeds > 0 && !seeds)) return fail(c, MOPTIX_ERR_INVALID, "bad seeds");
   if (c->ad.have) return fail(c, MOPTIX_ERR_STATE, "the accumulation buffer holds an adaptive render (per-pixel sample counts): moptix_adaptive_clear or moptix_accum_clear first");
-  if ((rc = begin_call(c, true)) != MOPTIX_OK) return rc;
+  // An asynchronous render with no batch in flight is ordered by the stream alone and does not wait for it (include/moptix.h: "non-blocking
+  // variant for stream overlap"); with one in flight that batch finishes and is timed first, as for every other call.
+  if (blocking || c->asyncPending) rc = begin_call(c, true);
+  else { HIPCHK(c, hipSetDevice(c->device), "hipSetDevice"); rc = ensure_accum(c); }
+  if (rc != MOPTIX_OK) return rc;
   if (nSeeds == 0) return MOPTIX_OK;
   RenderLaunch r;
   if ((rc = prepare_launch(c, nSeeds, counted, false, r)) != MOPTIX_OK || r.p.nItems == 0) return rc;
@@ -397,8 +419,10 @@ int do_render(moptix_context c, const int32_t* seeds, int32_t nSeeds, bool count
   DevBuf<unsigned long long> evLog;
   if ((rc = evlog_begin(c, evLog, r.a)) != MOPTIX_OK) return rc;
 #endif
-  c->seedStaging.assign(seeds, seeds + nSeeds);   // lives in the context: the copy below may still be in flight when an async render returns
-  HIPCHK(c, c->dSeeds.upload(c->seedStaging, c->stream), "upload seeds");
+  memcpy(r.seedStaging, seeds, sizeof(int) * (size_t)nSeeds);   // pinned, in the context: the copy below may still be in flight when an async render returns
+  HIPCHK(c, c->dSeeds.ensure((size_t)nSeeds), "alloc seeds");
+  HIPCHK(c, hipMemcpyAsync(c->dSeeds.p, r.seedStaging, sizeof(int) * (size_t)nSeeds, hipMemcpyHostToDevice, c->stream), "upload seeds");
+  HIPCHK(c, hipEventRecord(c->launchStaged, c->stream), "event");
   c->accumPlain = true;
 
   // ---- the launches ----
