@@ -843,13 +843,60 @@ int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n
  * "query_blocks_per_cu": allocated at the first box query on a tree, kept across refits, dropped by moptix_clear_scene, moptix_build_accel
  * and moptix_destroy.  A box query changes nothing else in the context: moptix_debug_buffer_addresses keeps its slots, and the ray and
  * point queries' buffers are untouched.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
- * Not offered: oriented boxes, frusta, query triangles, filters by material or primitive kind. */
+ * Not offered: frusta, query triangles, filters by material or primitive kind (oriented boxes: the next section). */
 enum { MOPTIX_BOX_ANY = 0, MOPTIX_BOX_COUNT = 1 };
 int moptix_query_boxes_device(moptix_context ctx, const float* dBoxes, int64_t n, int32_t mode, int32_t* dOut);
 int moptix_query_boxes(moptix_context ctx, const float* boxes, int64_t n, int32_t mode, int32_t* out);
 int moptix_query_boxes_list_device(moptix_context ctx, const float* dBoxes, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
                                    int32_t* dCounts);
 int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
+
+/* ---- oriented box queries: the primitives that meet each of the caller's rotated boxes -------------------------------------------------
+ * The box queries' question for a box with axes of its own: the broad phase of rigid bodies against a mesh that is refitted every step (a
+ * long body on a diagonal has a world box many times its own), selection of faces in a tilted region, candidate faces for a swept or
+ * rotated tool, culling a slab or a beam before a costlier query.
+ * A box is sixteen floats, 64 bytes:  cx cy cz  hx hy hz  a0.x a0.y a0.z  a1.x a1.y a1.z  a2.x a2.y a2.z  and one float that is not read:
+ * the centre, the half-extents along the box's own axes, and those axes as world-space directions (the columns of the usual
+ * local-to-world rotation).  The box is the closed set { x : |dot(a_j, x - c)| <= h_j, j = 0, 1, 2 }.  Valid: floats 0..14 finite; h_j >= 0
+ * (h_j == 0 is allowed, so a box may be a rectangle, a segment or a point); the axes orthonormal within 2^-10, |dot(a_i, a_i) - 1| <= 2^-10
+ * and |dot(a_i, a_j)| <= 2^-10 for i < j, in binary32.  An invalid box meets nothing, decided before any traversal.
+ * Touching counts.  All arithmetic is binary32 under the contract of csrc/pt_math.h, without contraction; csrc/pt_obb.h states every
+ * operation in order.  S(obb) is the set of primitive ids whose predicate holds; ids are the box queries' (spheres, then quads, then
+ * triangles by original face id); every primitive counts.  S is a function of the sixteen floats and the device records alone.
+ *   triangle   the record's triangle as the box queries see it.  (W) the per-axis min / max of the computed vertices against the query's
+ *              grown world box c -+ (E + g_w), E_k = (|a0.k| h0 + |a1.k| h1) + |a2.k| h2, g_w = max h * 2^-6 + (max |c| + max h) * 2^-16,
+ *              exact comparisons, strict rejections; (L) u_i = (dot(a_j, v_i - c))_j, then the box queries' triangle predicate on u_0, u_1,
+ *              u_2 against the box -h .. +h, unchanged.  W is there so that the walk's world-axis test is part of the predicate; g_w is
+ *              chosen so that it rejects nothing L accepts (csrc/pt_obb.h).
+ *   sphere     the surface: m = (dot(a_j, centre - c))_j, then the box queries' sphere predicate on m and -h .. +h.  A box wholly inside
+ *              the ball meets nothing.  Exact up to the axes' departure from orthonormality.
+ *   quad       the four corners of the box queries' quad as two triangles through the triangle predicate.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part: the walk enters a child iff its box meets the
+ * grown world box by exact comparisons and passes a six-axis test against the box's own axes with a margin, and csrc/pt_obb.h proves
+ * from the builder's padding and a bound on the roundings that this loses no primitive of S, in both node forms and after a refit.
+ *   mode       MOPTIX_BOX_ANY / MOPTIX_BOX_COUNT as for moptix_query_boxes.
+ *   list       the box queries' contract, word for word: offsets are n + 1 non-decreasing int64 entries into prims; counts[i] = |S|
+ *              always; if |S| <= capacity the slice holds S in ascending id, then -1 up to the capacity; otherwise the whole slice is -1
+ *              and the caller sees counts[i] > capacity.  Every byte of every slice is defined.
+ *   moptix_query_obbs_device       dObbs: device memory, 16-byte aligned (a box is read as four 16-byte loads); dOut: device memory,
+ *                                  4-byte aligned.  Asynchronous on the context's stream: no host wait, no allocation on a warm call.
+ *   moptix_query_obbs              host pointers, blocking: upload, query, read back (staging kept in the context)
+ *   moptix_query_obbs_list_device  dObbs: 16-byte aligned; dOffsets: 8-byte aligned; dPrims, dCounts: 4-byte aligned.  Asynchronous.  The
+ *                                  offsets are the caller's to get right: the kernel writes where they point.
+ *   moptix_query_obbs_list         host pointers, blocking; offsets are checked here: non-decreasing, offsets[0] >= 0.
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 boxes); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_boxes ("faces dirty" before a refit included).
+ * The oriented box queries keep a stack overflow area of their own: allocated at the first such query on a tree, kept across refits,
+ * dropped by moptix_clear_scene, moptix_build_accel and moptix_destroy.  They change nothing else in the context:
+ * moptix_debug_buffer_addresses keeps its slots, and the other queries' buffers are untouched.
+ * Not offered: frusta and general plane sets, sheared boxes (axes that are not orthonormal), exact plane sharing between neighbouring
+ * oriented cells (two cells' faces are each rounded in their own frame; moptix_query_boxes' grids share planes exactly), filters by
+ * material or primitive kind. */
+int moptix_query_obbs_device(moptix_context ctx, const float* dObbs, int64_t n, int32_t mode, int32_t* dOut);
+int moptix_query_obbs(moptix_context ctx, const float* obbs, int64_t n, int32_t mode, int32_t* out);
+int moptix_query_obbs_list_device(moptix_context ctx, const float* dObbs, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
+                                  int32_t* dCounts);
+int moptix_query_obbs_list(moptix_context ctx, const float* obbs, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
 
 /* ---- sweep queries: the first contact of a moving sphere ---------------------------------------------------------------------------
  * The continuous question the rays (no radius), the points (one instant) and the boxes (no time) leave open: a sphere of radius r moves
@@ -906,7 +953,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -921,7 +968,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray, point, box and sweep queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point, box, oriented box and sweep queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

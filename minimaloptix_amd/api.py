@@ -93,6 +93,26 @@ def occupancy_boxes(lo, hi, dims):
     return np.ascontiguousarray(np.concatenate([cells_lo, cells_hi], axis=1), np.float32)
 
 
+def oriented_boxes(centre, half, rotation):
+    """Oriented boxes as the (n, 16) float32 rows Context.query_obbs takes: centre (n, 3); half (n, 3) or (3,), the half-extents along the
+    box's own axes; rotation (n, 3, 3) or (3, 3), the usual local-to-world matrix, whose columns are the box axes as world-space
+    directions -- floats 6..14 of a row are its transpose, axis by axis.  The sixteenth float is 0 and is not read."""
+    c = np.asarray(centre, np.float32)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("oriented_boxes: centre must be (n, 3), not %r" % (c.shape,))
+    n = len(c)
+    h, r = np.asarray(half, np.float32), np.asarray(rotation, np.float32)
+    if h.shape not in ((n, 3), (3,)):
+        raise ValueError("oriented_boxes: half must be (n, 3) or (3,), not %r" % (h.shape,))
+    if r.shape not in ((n, 3, 3), (3, 3)):
+        raise ValueError("oriented_boxes: rotation must be (n, 3, 3) or (3, 3), not %r" % (r.shape,))
+    out = np.zeros((n, 16), np.float32)
+    out[:, 0:3] = c
+    out[:, 3:6] = h
+    out[:, 6:15] = np.swapaxes(np.broadcast_to(r, (n, 3, 3)), 1, 2).reshape(n, 9)
+    return out
+
+
 def _f3(v):
     return [float(v.x), float(v.y), float(v.z)]
 
@@ -766,20 +786,36 @@ class Context:
         returns (prims (n, K), counts): where counts[i] <= K the row holds the ids ascending and -1 behind them, else -1 throughout.
         A numpy (n, 6) or (n, 2, 3) array takes the host path and the results are numpy arrays.  A contiguous (n, 6) float32 torch tensor
         on this context's device is read where it is, and the results are tensors on that device."""
+        return self._query_box_family("query_boxes", "moptix_query_boxes", boxes, 6, (2, 3), "lox loy loz hix hiy hiz", mode, max_prims)
+
+    def query_obbs(self, obbs, mode="any", max_prims=None):
+        """The primitives that meet each of the caller's oriented boxes (closed sets: touching counts); blocking.  A box is the sixteen
+        floats of oriented_boxes: centre, half-extents along the box's own axes, the three axes as world-space directions, one float that
+        is not read.  A box whose axes are further than 2^-10 from orthonormal, with a negative half-extent or a non-finite float meets
+        nothing.  Modes and return values are query_boxes': "any" and "count" give int32 per box; "list" gives the CSR pair (prims,
+        offsets), or with max_prims=K (prims (n, K), counts).
+        A numpy (n, 16) array takes the host path and the results are numpy arrays.  A contiguous (n, 16) float32 torch tensor on this
+        context's device is read where it is, and the results are tensors on that device."""
+        return self._query_box_family("query_obbs", "moptix_query_obbs", obbs, 16, None, "centre, half-extents, three axes, one unused", mode, max_prims)
+
+    def _query_box_family(self, who, entry, boxes, width, folded, layout, mode, max_prims):
+        """query_boxes and query_obbs: `entry`, `entry`_device, `entry`_list and `entry`_list_device on (n, width) float32 rows; a numpy
+        array may also have the shape (n,) + folded."""
+        fn = lambda suffix: getattr(self._L, entry + suffix)      # looked up after the arguments are checked
         if mode not in self.BOX_MODES and mode != "list":
-            raise ValueError("query_boxes: mode %r (any, count or list)" % (mode,))
+            raise ValueError("%s: mode %r (any, count or list)" % (who, mode))
         if max_prims is not None and (mode != "list" or int(max_prims) < 0):
-            raise ValueError("query_boxes: max_prims %r (a capacity >= 0, with mode \"list\" only)" % (max_prims,))
+            raise ValueError("%s: max_prims %r (a capacity >= 0, with mode \"list\" only)" % (who, max_prims))
         if isinstance(boxes, np.ndarray) or not hasattr(boxes, "data_ptr"):
             b = np.asarray(boxes, np.float32)
-            if not ((b.ndim == 2 and b.shape[1] == 6) or (b.ndim == 3 and b.shape[1:] == (2, 3))):
-                raise ValueError("query_boxes: boxes must be (n, 6) or (n, 2, 3), not %r" % (b.shape,))
-            b = np.ascontiguousarray(b.reshape(-1, 6), np.float32)
+            if not ((b.ndim == 2 and b.shape[1] == width) or (folded is not None and b.ndim == 3 and b.shape[1:] == folded)):
+                raise ValueError("%s: boxes must be (n, %d)%s, not %r" % (who, width, " or (n, %d, %d)" % folded if folded else "", b.shape))
+            b = np.ascontiguousarray(b.reshape(-1, width), np.float32)
             n = len(b)
             bp, i32p = b.ctypes.data_as(C.POINTER(C.c_float)), lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
             counts = np.zeros(n, np.int32)
             if mode != "list" or max_prims is None:
-                self._chk(self._L.moptix_query_boxes(self._h, bp, n, self.BOX_MODES.get(mode, K.BOX_COUNT), i32p(counts)))
+                self._chk(fn("")(self._h, bp, n, self.BOX_MODES.get(mode, K.BOX_COUNT), i32p(counts)))
                 if mode != "list":
                     return counts
                 offsets = np.zeros(n + 1, np.int64)
@@ -787,17 +823,17 @@ class Context:
             else:
                 offsets = np.arange(n + 1, dtype=np.int64) * int(max_prims)
             prims = np.zeros(int(offsets[-1]), np.int32)
-            self._chk(self._L.moptix_query_boxes_list(self._h, bp, n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), i32p(prims), i32p(counts)))
+            self._chk(fn("_list")(self._h, bp, n, offsets.ctypes.data_as(C.POINTER(C.c_int64)), i32p(prims), i32p(counts)))
             return (prims, offsets) if max_prims is None else (prims.reshape(n, int(max_prims)), counts)
         import torch
-        _check_tensor("query_boxes", "boxes", boxes, ("torch.float32",), _rows(6), "shape (n, 6), lox loy loz hix hiy hiz", self.device)
+        _check_tensor(who, "boxes", boxes, ("torch.float32",), _rows(width), "shape (n, %d), %s" % (width, layout), self.device)
         n = boxes.shape[0]
         dev = boxes.device
         ptr = lambda t: C.c_void_p(t.data_ptr())
         counts = torch.zeros(n, dtype=torch.int32, device=dev)
         torch.cuda.current_stream(dev).synchronize()      # the boxes are ready before the context's stream reads them
         if mode != "list" or max_prims is None:
-            self._chk(self._L.moptix_query_boxes_device(self._h, ptr(boxes), n, self.BOX_MODES.get(mode, K.BOX_COUNT), ptr(counts)))
+            self._chk(fn("_device")(self._h, ptr(boxes), n, self.BOX_MODES.get(mode, K.BOX_COUNT), ptr(counts)))
             self.sync()
             if mode != "list":
                 return counts
@@ -808,7 +844,7 @@ class Context:
         total = int(offsets[-1]) if n else 0
         prims = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total]
         torch.cuda.current_stream(dev).synchronize()      # offsets and the zeroed outputs too
-        self._chk(self._L.moptix_query_boxes_list_device(self._h, ptr(boxes), n, ptr(offsets), ptr(prims) if n else None, ptr(counts)))
+        self._chk(fn("_list_device")(self._h, ptr(boxes), n, ptr(offsets), ptr(prims) if n else None, ptr(counts)))
         self.sync()
         return (prims, offsets) if max_prims is None else (prims.reshape(n, int(max_prims)), counts)
 
