@@ -843,7 +843,7 @@ int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n
  * "query_blocks_per_cu": allocated at the first box query on a tree, kept across refits, dropped by moptix_clear_scene, moptix_build_accel
  * and moptix_destroy.  A box query changes nothing else in the context: moptix_debug_buffer_addresses keeps its slots, and the ray and
  * point queries' buffers are untouched.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
- * Not offered: frusta, query triangles, filters by material or primitive kind (oriented boxes: the next section). */
+ * Not offered: query triangles, filters by material or primitive kind (oriented boxes and frusta: the next two sections). */
 enum { MOPTIX_BOX_ANY = 0, MOPTIX_BOX_COUNT = 1 };
 int moptix_query_boxes_device(moptix_context ctx, const float* dBoxes, int64_t n, int32_t mode, int32_t* dOut);
 int moptix_query_boxes(moptix_context ctx, const float* boxes, int64_t n, int32_t mode, int32_t* out);
@@ -889,7 +889,7 @@ int moptix_query_boxes_list(moptix_context ctx, const float* boxes, int64_t n, c
  * The oriented box queries keep a stack overflow area of their own: allocated at the first such query on a tree, kept across refits,
  * dropped by moptix_clear_scene, moptix_build_accel and moptix_destroy.  They change nothing else in the context:
  * moptix_debug_buffer_addresses keeps its slots, and the other queries' buffers are untouched.
- * Not offered: frusta and general plane sets, sheared boxes (axes that are not orthonormal), exact plane sharing between neighbouring
+ * Not offered: sheared boxes (axes that are not orthonormal; up to six planes of any kind: the frustum queries), exact plane sharing between neighbouring
  * oriented cells (two cells' faces are each rounded in their own frame; moptix_query_boxes' grids share planes exactly), filters by
  * material or primitive kind. */
 int moptix_query_obbs_device(moptix_context ctx, const float* dObbs, int64_t n, int32_t mode, int32_t* dOut);
@@ -897,6 +897,56 @@ int moptix_query_obbs(moptix_context ctx, const float* obbs, int64_t n, int32_t 
 int moptix_query_obbs_list_device(moptix_context ctx, const float* dObbs, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
                                   int32_t* dCounts);
 int moptix_query_obbs_list(moptix_context ctx, const float* obbs, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
+
+/* ---- frustum queries: the primitives that meet each of the caller's six-plane regions ----------------------------------------------------
+ * The box queries' question for a convex region bounded by planes: which faces a camera or a screen tile can see (view culling, marquee
+ * selection of faces, per-tile candidate lists), which faces lie in a portal, a wedge, a slab, a half-space or a k-DOP of up to six planes.
+ * A query is 24 floats, 96 bytes: six planes  nx ny nz d.  The region is the closed set { x : dot(n_j, x) + d_j >= 0, j = 0..5 }: normals
+ * point inwards (what Gribb-Hartmann extraction from a clip matrix gives) and need not be unit length.  Valid: all 24 floats finite.  An
+ * invalid query meets nothing, decided before any traversal.  A plane 0 0 0 d with d >= 0 constrains nothing, so wedges, slabs,
+ * half-spaces and unbounded pyramids need no special case; with d < 0 it empties the region; six zero planes meet every primitive.
+ * Touching counts.  All arithmetic is binary32 under the contract of csrc/pt_math.h, without contraction; csrc/pt_frustum.h states every
+ * operation in order.  S(frustum) is the set of primitive ids whose predicate holds; ids are the box queries' (spheres, then quads, then
+ * triangles by original face id); every primitive counts.  S is a function of the 24 floats and the device records alone; it does not
+ * depend on the order of the six planes, nor on a plane's four floats being multiplied by a power of two (short of overflow and underflow).
+ *   triangle   the record's triangle as the box queries see it, s_ji = dot(n_j, v_i) + d_j.  (R) reject if on some plane all three
+ *              s_ji < 0; (A) accept if some vertex has s_ji >= 0 on all six; (E) clip each edge as a parameter interval against the six
+ *              planes, t = s_a / (s_a - s_b), accept if one is left non-empty; (V) for a face that cuts through the region with all
+ *              edges outside: the crossings of the 15 pairs of plane lines in the triangle's own coordinates, accept if one lies in the
+ *              triangle and on the inner side of the other four planes.  An exact stage behind the plane test: a triangle outside no
+ *              single plane and still outside the region is not reported.
+ *   sphere     the plane rule on the BALL: s_j = dot(n_j, centre) + d_j >= -(radius * |n_j|) on all six planes, |n_j| = sqrtf(dot(n_j,
+ *              n_j)) taken once per query.  What view culling asks ("can the ball be seen"); exact for half-spaces and slabs.  Not the
+ *              surface the box queries test: a region wholly inside the ball meets it.  Conservative at the region's edges and
+ *              corners: a ball within `radius` of two planes but not of their common edge is reported.  Two contradictory planes still
+ *              report a ball that reaches across both; a plane 0 0 0 d with d < 0 reports nothing.
+ *   quad       the four corners of the box queries' quad as two triangles through the triangle predicate.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part: the walk enters a child iff the largest value
+ * of each plane's function over the child's box is at least minus a margin of 2^-16 of the magnitudes involved, and csrc/pt_frustum.h
+ * proves from the builder's padding and a bound on the roundings (the margin is sixteen times it) that this loses no primitive of S, in
+ * both node forms and after a refit.
+ *   mode       MOPTIX_BOX_ANY / MOPTIX_BOX_COUNT as for moptix_query_boxes.
+ *   list       the box queries' contract, word for word: offsets are n + 1 non-decreasing int64 entries into prims; counts[i] = |S|
+ *              always; if |S| <= capacity the slice holds S in ascending id, then -1 up to the capacity; otherwise the whole slice is -1
+ *              and the caller sees counts[i] > capacity.  Every byte of every slice is defined.
+ *   moptix_query_frusta_device       dFrusta: device memory, 16-byte aligned (a query is read as six 16-byte loads); dOut: device memory,
+ *                                    4-byte aligned.  Asynchronous on the context's stream: no host wait, no allocation on a warm call.
+ *   moptix_query_frusta              host pointers, blocking: upload, query, read back (staging kept in the context)
+ *   moptix_query_frusta_list_device  dFrusta: 16-byte aligned; dOffsets: 8-byte aligned; dPrims, dCounts: 4-byte aligned.  Asynchronous.
+ *                                    The offsets are the caller's to get right: the kernel writes where they point.
+ *   moptix_query_frusta_list         host pointers, blocking; offsets are checked here: non-decreasing, offsets[0] >= 0.
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 queries); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_boxes ("faces dirty" before a refit included).
+ * The frustum queries keep a stack overflow area of their own: allocated at the first such query on a tree, kept across refits, dropped
+ * by moptix_clear_scene, moptix_build_accel and moptix_destroy.  They change nothing else in the context:
+ * moptix_debug_buffer_addresses keeps its slots, and the other queries' buffers are untouched.
+ * Not offered: more than six planes per query, the exact ball or the sphere's surface against the region, thin-lens frusta, filters by
+ * material or primitive kind. */
+int moptix_query_frusta_device(moptix_context ctx, const float* dFrusta, int64_t n, int32_t mode, int32_t* dOut);
+int moptix_query_frusta(moptix_context ctx, const float* frusta, int64_t n, int32_t mode, int32_t* out);
+int moptix_query_frusta_list_device(moptix_context ctx, const float* dFrusta, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
+                                    int32_t* dCounts);
+int moptix_query_frusta_list(moptix_context ctx, const float* frusta, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
 
 /* ---- sweep queries: the first contact of a moving sphere ---------------------------------------------------------------------------
  * The continuous question the rays (no radius), the points (one instant) and the boxes (no time) leave open: a sphere of radius r moves
@@ -953,7 +1003,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -968,7 +1018,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray, point, box, oriented box and sweep queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point, box, oriented box, frustum and sweep queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

@@ -221,6 +221,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_boxes_device", "moptix_query_boxes", "moptix_query_boxes_list_device", "moptix_query_boxes_list",
     "moptix_query_sweeps_device", "moptix_query_sweeps",
     "moptix_query_obbs_device", "moptix_query_obbs", "moptix_query_obbs_list_device", "moptix_query_obbs_list",
+    "moptix_query_frusta_device", "moptix_query_frusta", "moptix_query_frusta_list_device", "moptix_query_frusta_list",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -337,6 +338,10 @@ def device_lib():
         L.moptix_query_obbs.argtypes = [vp, f32p, C.c_int64, i32, i32p]
         L.moptix_query_obbs_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
         L.moptix_query_obbs_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
+        L.moptix_query_frusta_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_frusta.argtypes = [vp, f32p, C.c_int64, i32, i32p]
+        L.moptix_query_frusta_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+        L.moptix_query_frusta_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
         L.moptix_get_sign_info.argtypes = [vp, C.POINTER(SignInfo)]
         L.moptix_debug_read_sign_table.argtypes = [vp, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]

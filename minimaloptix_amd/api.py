@@ -113,6 +113,58 @@ def oriented_boxes(centre, half, rotation):
     return out
 
 
+def frustum_planes(matrix, depth="gl"):
+    """The six inward planes of a clip matrix as the (n, 24) float32 rows Context.query_frusta takes (Gribb-Hartmann): matrix (4, 4) or
+    (n, 4, 4) with clip = M @ (x, y, z, 1); a single matrix gives one row.  The order is left, right, bottom, top, near, far: -w <= x <= w,
+    -w <= y <= w, and for depth="gl" -w <= z <= w, for depth="zero" 0 <= z <= w.  The planes are the sums and differences of the matrix
+    rows, computed in binary64 and rounded to binary32 once; they are not normalised (the queries do not need it)."""
+    if depth not in ("gl", "zero"):
+        raise ValueError("frustum_planes: depth %r (\"gl\" or \"zero\")" % (depth,))
+    m = np.asarray(matrix, np.float64)
+    if m.shape[-2:] != (4, 4) or m.ndim not in (2, 3):
+        raise ValueError("frustum_planes: matrix must be (4, 4) or (n, 4, 4), not %r" % (m.shape,))
+    m = m.reshape(-1, 4, 4)
+    x, y, z, w = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    planes = np.stack([w + x, w - x, w + y, w - y, w + z if depth == "gl" else z, w - z], axis=1)
+    return np.ascontiguousarray(planes.reshape(-1, 24), np.float32)
+
+
+def camera_frusta(cam, rects, near=0.0, far=float("inf")):
+    """The regions the renderer's own camera sees through rectangles of its screen, as (n, 24) float32 rows for Context.query_frusta.
+    cam: a moptix_cam_params (HostScene.params.cam) or the mapping HostScene.to_dict()["cam"] gives; rects (n, 4) x0 y0 x1 y1 in screen
+    fractions [0, 1] -- the xy that the renderer multiplies `horizontal` and `vertical` by, so (0, 0, 1, 1) is the whole frame and pixel
+    (i, j) of a W x H frame is (i / W, j / H, (i + 1) / W, (j + 1) / H).  The order is left, right, bottom, top, near, far.  The four
+    side planes go through `origin` and the corner directions (scrLowerLeftCorner + horizontal x + vertical y) - origin; near and far are
+    perpendicular to the view axis (the screen's normal) at those distances from the origin: near = 0 is the plane through the origin,
+    far = inf a zero plane, which constrains nothing.  Planes are computed in binary64 with unit normals, oriented inwards and rounded to
+    binary32 once.  lensRadius plays no part: this is the pinhole camera's region, and rays of a thin lens leave it near the camera."""
+    get = (lambda k: cam[k]) if isinstance(cam, dict) or hasattr(cam, "keys") else (lambda k: _f3(getattr(cam, k)))
+    o, h, v, ll = (np.asarray(get(k), np.float64).reshape(3) for k in ("origin", "horizontal", "vertical", "scrLowerLeftCorner"))
+    r = np.asarray(rects, np.float64)
+    if r.ndim != 2 or r.shape[1] != 4:
+        raise ValueError("camera_frusta: rects must be (n, 4) x0 y0 x1 y1, not %r" % (r.shape,))
+    near, far = float(near), float(far)
+    if not (np.isfinite(r).all() and (r[:, 0] <= r[:, 2]).all() and (r[:, 1] <= r[:, 3]).all() and 0.0 <= near <= far):
+        raise ValueError("camera_frusta: rects need finite x0 <= x1 and y0 <= y1, and 0 <= near <= far")
+    corner = lambda x, y: (ll - o)[None, :] + x[:, None] * h[None, :] + y[:, None] * v[None, :]
+    c00, c01, c10, c11 = corner(r[:, 0], r[:, 1]), corner(r[:, 0], r[:, 3]), corner(r[:, 2], r[:, 1]), corner(r[:, 2], r[:, 3])
+
+    def side(a, b, inward, sign):
+        n = np.cross(a, b)
+        n /= np.linalg.norm(n, axis=1, keepdims=True)
+        n *= np.where(sign * (n @ inward) >= 0, 1.0, -1.0)[:, None]
+        return np.concatenate([n, -(n @ o)[:, None]], axis=1)
+    axis = np.cross(h, v)
+    axis /= np.linalg.norm(axis)
+    if axis @ (ll + 0.5 * h + 0.5 * v - o) < 0:
+        axis = -axis
+    n = len(r)
+    near_p = np.broadcast_to(np.concatenate([axis, [-(axis @ o) - near]]), (n, 4))
+    far_p = np.broadcast_to(np.concatenate([-axis, [(axis @ o) + far]]) if np.isfinite(far) else np.zeros(4), (n, 4))
+    planes = np.stack([side(c00, c01, h, 1.0), side(c10, c11, h, -1.0), side(c00, c10, v, 1.0), side(c01, c11, v, -1.0), near_p, far_p], axis=1)
+    return np.ascontiguousarray(planes.reshape(n, 24), np.float32)
+
+
 def _f3(v):
     return [float(v.x), float(v.y), float(v.z)]
 
@@ -798,8 +850,20 @@ class Context:
         context's device is read where it is, and the results are tensors on that device."""
         return self._query_box_family("query_obbs", "moptix_query_obbs", obbs, 16, None, "centre, half-extents, three axes, one unused", mode, max_prims)
 
+    def query_frusta(self, frusta, mode="any", max_prims=None):
+        """The primitives that meet each of the caller's six-plane regions (closed sets: touching counts); blocking.  A query is 24 floats,
+        six planes nx ny nz d with the normals pointing inwards: the region is { x : dot(n_j, x) + d_j >= 0 for all six }.  Normals need
+        not be unit length; a plane 0 0 0 d with d >= 0 constrains nothing, so fewer planes (a wedge, a slab, a half-space) are padded
+        with zeros; a query with a non-finite float meets nothing.  frustum_planes makes the rows from a clip matrix, camera_frusta from
+        the renderer's camera and screen rectangles.  Triangles and quads are tested exactly up to rounding; a sphere by the plane rule
+        on its ball (conservative at the region's edges and corners).  Modes and return values are query_boxes': "any" and "count" give
+        int32 per query; "list" gives the CSR pair (prims, offsets), or with max_prims=K (prims (n, K), counts).
+        A numpy (n, 24) or (n, 6, 4) array takes the host path and the results are numpy arrays.  A contiguous (n, 24) float32 torch
+        tensor on this context's device is read where it is, and the results are tensors on that device."""
+        return self._query_box_family("query_frusta", "moptix_query_frusta", frusta, 24, (6, 4), "six planes nx ny nz d", mode, max_prims)
+
     def _query_box_family(self, who, entry, boxes, width, folded, layout, mode, max_prims):
-        """query_boxes and query_obbs: `entry`, `entry`_device, `entry`_list and `entry`_list_device on (n, width) float32 rows; a numpy
+        """query_boxes, query_obbs and query_frusta: `entry`, `entry`_device, `entry`_list and `entry`_list_device on (n, width) float32 rows; a numpy
         array may also have the shape (n,) + folded."""
         fn = lambda suffix: getattr(self._L, entry + suffix)      # looked up after the arguments are checked
         if mode not in self.BOX_MODES and mode != "list":
@@ -842,9 +906,10 @@ class Context:
         else:
             offsets = torch.arange(n + 1, dtype=torch.int64, device=dev) * int(max_prims)
         total = int(offsets[-1]) if n else 0
-        prims = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total]
+        room = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)      # an empty list still needs an address: an empty view has none
+        prims = room[:total]
         torch.cuda.current_stream(dev).synchronize()      # offsets and the zeroed outputs too
-        self._chk(fn("_list_device")(self._h, ptr(boxes), n, ptr(offsets), ptr(prims) if n else None, ptr(counts)))
+        self._chk(fn("_list_device")(self._h, ptr(boxes), n, ptr(offsets), ptr(room) if n else None, ptr(counts)))
         self.sync()
         return (prims, offsets) if max_prims is None else (prims.reshape(n, int(max_prims)), counts)
 

@@ -294,6 +294,16 @@ struct moptix_context_t {
     void release() { drop(); obbs.release(); offsets.release(); prims.release(); out.release(); }
   } obb;
 
+  // ---- frustum queries (api_frustum.hip): the stack overflow area of the frustum kernel, its own (four bytes an entry: a reference),
+  // allocated at the first such query after a build, kept across refits and dropped with the tree it was sized for, where the box
+  // queries' is; the staging of the host-pointer entry points (frusta, offsets, prims; out: the int32 results or counts) ----
+  struct FrustumQuery {
+    DevBuf<int> overflow;
+    DevBuf<float> frusta; DevBuf<long long> offsets; DevBuf<int> prims, out;
+    void drop() { overflow.release(); }
+    void release() { drop(); frusta.release(); offsets.release(); prims.release(); out.release(); }
+  } frustum;
+
   // ---- signed point queries (api_sign.hip) ----
   // The topology belongs to one set of uploaded faces: taken on the host at the first signed query or moptix_get_sign_info, kept across
   // moptix_update_faces*, moptix_refit_accel and moptix_build_accel, dropped by moptix_clear_scene, moptix_add_mesh and destroy.  Its

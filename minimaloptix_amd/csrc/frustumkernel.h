@@ -1,0 +1,23 @@
+// frustumkernel.h -- launch interface of frustumkernel.hip (frustum queries, pt_frustum.h)
+#pragma once
+#include <hip/hip_runtime.h>
+#include "pt_frustum.h"
+
+namespace pt {
+
+struct FrustumArgs {
+  SceneView scene;                // nodes64 set = walk the 64-byte nodes
+  const float* frusta;            // n x 24 floats (pt_frustum.h), 16-byte aligned (device)
+  int* out;                       // any: n x int32 |S| > 0; count and list: n x int32 |S| (device)
+  const long long* offsets;       // list: n + 1 entries of this launch into prims, 8-byte aligned (device); else null
+  int* prims;                     // list: the caller's whole prims array (the offsets are absolute); else null
+  int n;                          // queries of this launch (the host cuts longer batches: indices stay 32-bit)
+  int* stackOverflow;             // per-thread spill area (one reference per entry) for trees deeper than the LDS stack, or null
+};
+constexpr int kFrustumMaxLaunch = 1 << 30;      // queries per launch
+
+size_t frustumkernel_overflow_ints(int nBlocks, int stackBound);      // 0 = the tree fits the LDS stack
+// mode: BOX_ANY / BOX_COUNT / BOX_LIST (pt_box.h).  Launches min(nBlocks, ceil(n / 256)) workgroups on `stream`.
+hipError_t launch_frustumquery(hipStream_t stream, const FrustumArgs& a, int nBlocks, int mode);
+
+}  // namespace pt
