@@ -948,6 +948,54 @@ int moptix_query_frusta_list_device(moptix_context ctx, const float* dFrusta, in
                                     int32_t* dCounts);
 int moptix_query_frusta_list(moptix_context ctx, const float* frusta, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
 
+/* ---- winding-number queries: inside / outside for the meshes users actually have ----------------------------------------------------
+ * MOPTIX_POINT_SIGNED takes its sign from pseudonormals, which is right only for a closed, consistently wound mesh.  The generalised
+ * winding number w(q) (Jacobson et al. 2013) is the sum of the signed solid angles of all primitives seen from q over 4 pi: 1 inside and
+ * 0 outside a closed mesh wound outwards (-1 inside one wound inwards), and a smooth function of q across holes, flipped and duplicated
+ * faces; w > 0.5 classifies.  Summed over every face it costs O(faces) a point; with the order-1 far field over the tree (Barill et al.
+ * 2018) O(log faces).
+ * A query is 16 bytes x y z beta, the point queries' row with beta in the maxDist slot.  beta is +inf (exact: no cluster is ever
+ * approximated) or finite >= 1 (2 is the usual choice; larger is more exact and slower).  A non-finite coordinate, beta < 1 or a NaN beta
+ * gives the quiet NaN 0x7fc00000.  The result is one float per point.  All per-term arithmetic is binary32 under the contract of
+ * csrc/pt_math.h, without contraction; the sum is binary64; csrc/pt_winding.h states every operation in order:
+ *   triangle   a, b, c = the vertices minus q, scaled by the exact power of two 2^-floor(log2 of their largest |component|);
+ *              det = dot(a, cross(b, c)), den = |a||b||c| + dot(a,b)|c| + dot(b,c)|a| + dot(c,a)|b|, omega = copysign(2 atan2_ac(|det|,
+ *              den), det).  det == 0 gives exactly 0: a point in a face's plane gets nothing from that face.
+ *   quad       the two triangles of the box queries' split; an open surface.
+ *   sphere     4 pi when dot(w, w) < radius * radius, w = q - centre (the signed query's inside test), else 0.
+ *   cluster    each child reference of a node carries A (sum of face areas), p (area-weighted centroid), N (sum of the area vectors
+ *              1/2 cross(p1 - p0, p2 - p0)) and a radius r that is not smaller than the distance from the stored p to the farthest corner
+ *              of the child's stored box.  With d = p - q, l2 = dot(d, d): the child is approximated iff l2 > (beta r)(beta r), by the
+ *              dipole dot(N, d) / (l2 sqrt(l2)).
+ *   sum        binary64, in a fixed order: spheres by id, quads by id, the tree depth first with children in slot order and a leaf's
+ *              triangles in record order; w = (float)(sum * (1 / 4 pi)).
+ * TREE DEPENDENCE.  Unlike every other query here, the value depends on the tree.  For a finite beta it does so through the
+ * approximation: leaf size and builder decide which clusters exist.  For beta = +inf it depends on the tree only through the order of
+ * a binary64 sum of the same binary32 terms.  The node format plays no part (references and moments are read, never a box), nor do
+ * "query_blocks_per_cu" and scheduling.  Stated range: differences p - q finite; distances from q to a cluster between about 1e-12 and
+ * 1e12 units (l2 sqrt(l2) finite and normal); edges between about 1e-9 and 1e9 units, as for the signed queries.
+ * The moments table holds 128 bytes per node.  It is computed on the device, one launch per level of the tree, deepest first, over the
+ * refit's plan, and is stale after moptix_update_faces*, moptix_refit_accel and moptix_build_accel; the next winding query enqueues the pass in
+ * front of its kernel.  A context that never asks for a winding number allocates and launches nothing of this.
+ *   moptix_query_winding_device  dPoints: device memory, 16-byte aligned; dOut: device memory, 4-byte aligned.  Asynchronous on the context's
+ *                                stream: no host wait and no allocation on a warm call.  The first call after moptix_build_accel makes
+ *                                the refit's plan where no refit has (that reads the nodes back: one host synchronisation per built tree).
+ *   moptix_query_winding         host pointers, blocking: upload, query, read back (staging kept in the context)
+ *   moptix_get_winding_info      tableBuilds: moments passes enqueued by this context so far; nodes: nodes of the built tree; tableBytes: bytes
+ *                                of the table as allocated (0 before the first query on a tree); stale: 1 if the next query will run the pass
+ *   moptix_debug_read_winding_table  a test aid, not an interface to build on: the table (computed first if stale, which counts as a build)
+ *                                copied to the host, 128 bytes per node (per child slot: A, p.xyz, N.xyz, r); state errors as a query.
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 points); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0; state errors as moptix_query_points ("faces dirty" before a refit included).  An empty scene gives 0.
+ * The winding queries keep a stack overflow area of their own beside the table; both are dropped by moptix_clear_scene, moptix_build_accel
+ * and moptix_destroy.  They change nothing else in the context.
+ * Not offered: second- and third-order expansions, a signed distance fused into the same kernel, multi-GPU splitting of the points. */
+typedef struct { uint32_t tableBuilds, nodes; uint64_t tableBytes; uint32_t stale, pad; } moptix_winding_info;
+int moptix_query_winding_device(moptix_context ctx, const float* dPoints, int64_t n, float* dOut);
+int moptix_query_winding(moptix_context ctx, const float* points, int64_t n, float* out);
+int moptix_get_winding_info(moptix_context ctx, moptix_winding_info* out);
+int moptix_debug_read_winding_table(moptix_context ctx, void* table);
+
 /* ---- sweep queries: the first contact of a moving sphere ---------------------------------------------------------------------------
  * The continuous question the rays (no radius), the points (one instant) and the boxes (no time) leave open: a sphere of radius r moves
  * from o along d; when does it first touch the scene, and where?  Continuous collision detection of particles against a mesh that is
@@ -1003,7 +1051,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_winding*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class

@@ -197,6 +197,14 @@ class SignInfo(C.Structure):
         return d
 
 
+class WindingInfo(C.Structure):
+    """moptix_winding_info: what moptix_get_winding_info reports of the winding queries' moments table."""
+    _fields_ = [("tableBuilds", C.c_uint32), ("nodes", C.c_uint32), ("tableBytes", C.c_uint64), ("stale", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(tableBuilds=int(self.tableBuilds), nodes=int(self.nodes), tableBytes=int(self.tableBytes), stale=int(self.stale))
+
+
 # every symbol include/moptix.h declares (tests check that the library exports all of them)
 DEVICE_SYMBOLS = [
     "moptix_create", "moptix_destroy", "moptix_last_error", "moptix_version", "moptix_set_stream",
@@ -222,6 +230,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_sweeps_device", "moptix_query_sweeps",
     "moptix_query_obbs_device", "moptix_query_obbs", "moptix_query_obbs_list_device", "moptix_query_obbs_list",
     "moptix_query_frusta_device", "moptix_query_frusta", "moptix_query_frusta_list_device", "moptix_query_frusta_list",
+    "moptix_query_winding_device", "moptix_query_winding", "moptix_get_winding_info", "moptix_debug_read_winding_table",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
 HOST_SYMBOLS = [
@@ -342,6 +351,10 @@ def device_lib():
         L.moptix_query_frusta.argtypes = [vp, f32p, C.c_int64, i32, i32p]
         L.moptix_query_frusta_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
         L.moptix_query_frusta_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
+        L.moptix_query_winding_device.argtypes = [vp, vp, C.c_int64, vp]
+        L.moptix_query_winding.argtypes = [vp, f32p, C.c_int64, f32p]
+        L.moptix_get_winding_info.argtypes = [vp, C.POINTER(WindingInfo)]
+        L.moptix_debug_read_winding_table.argtypes = [vp, vp]
         L.moptix_get_sign_info.argtypes = [vp, C.POINTER(SignInfo)]
         L.moptix_debug_read_sign_table.argtypes = [vp, vp]
         L.moptix_update_faces.argtypes = [vp, i32, i32, f32p, f32p]

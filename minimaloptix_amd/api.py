@@ -408,6 +408,7 @@ class Context:
 
     def set_stream(self, hip_stream):
         self._chk(self._L.moptix_set_stream(self._h, C.c_void_p(hip_stream)))
+        self._stream = int(hip_stream or 0)      # query_winding: a tensor call on this very stream needs no wait on either side
 
     def resolve_rgb8(self, n_accumulation, clear=False):
         out, p = self._frame(3, np.uint8)
@@ -954,6 +955,59 @@ class Context:
         if m == K.SWEEP_ANY:
             return out
         return _record_views(out, "t", "p")
+
+    # ---- winding-number queries (include/moptix.h "winding-number queries") ----
+    def query_winding(self, points, beta=2.0):
+        """The generalised winding number of the caller's points: 1 inside and 0 outside a closed mesh wound outwards, and a smooth
+        function across holes, flipped and duplicated faces (inside() thresholds it at 0.5).  beta is +inf (exact: every
+        primitive's solid angle is summed) or >= 1: a cluster of the tree further away than beta times its radius is replaced by its
+        dipole.  For a finite beta the value depends on the tree (leaf size, builder), not on the node format.
+        A numpy array takes the host path: (n, 3) positions with beta a scalar or an (n,) array, or (n, 4) rows x y z beta (beta is then
+        not consulted); the result is a float32 array.  A float32 torch tensor on this context's device, (n, 3) with beta a scalar or an
+        (n,) tensor, or a contiguous (n, 4) one that is read where it is, gives a float32 tensor on that device -- asynchronously, with
+        no wait on the host, when torch's current stream is the stream this context was given (set_stream): the call is then ordered
+        like any torch operation.  On any other stream the call waits for the points before and for the result after, as query_points
+        does.  A row with a non-finite coordinate or a beta below 1 gives NaN.  The numpy path is blocking."""
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            pts = _point_rows("query_winding", points, beta)
+            out = np.zeros(len(pts), np.float32)
+            self._chk(self._L.moptix_query_winding(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), out.ctypes.data_as(C.POINTER(C.c_float))))
+            return out
+        import torch
+        if points.dim() == 2 and points.shape[1] == 3:
+            b = torch.as_tensor(beta, dtype=torch.float32, device=points.device)
+            if b.dim() > 1 or (b.dim() == 1 and b.shape[0] != points.shape[0]):
+                raise ValueError("query_winding: beta must be a scalar or one value per point")
+            points = torch.cat([points, b.reshape(-1, 1).expand(points.shape[0], 1)], dim=1).contiguous()
+        _check_tensor("query_winding", "points", points, ("torch.float32",), _rows(4), "shape (n, 3), or (n, 4) rows x y z beta", self.device)
+        n = points.shape[0]
+        out = torch.empty(n, dtype=torch.float32, device=points.device)
+        cur = torch.cuda.current_stream(points.device)
+        same = getattr(self, "_stream", 0) != 0 and self._stream == cur.cuda_stream
+        if not same:
+            cur.synchronize()                                       # the points are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_winding_device(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        if not same:
+            self.sync()
+        return out
+
+    def inside(self, points, beta=2.0):
+        """query_winding(points, beta) > 0.5, on the same side: a bool numpy array for numpy input, a bool tensor for a tensor."""
+        return self.query_winding(points, beta) > 0.5
+
+    def winding_info(self):
+        """dict of the winding queries' table of cluster moments: tableBuilds (moments passes this context has enqueued), nodes (of the
+        built tree), tableBytes (as allocated; 0 before the first winding query on a tree), stale (1: the next query runs the pass)."""
+        r = K.WindingInfo()
+        self._chk(self._L.moptix_get_winding_info(self._h, C.byref(r)))
+        return r.as_dict()
+
+    def winding_table_read(self):
+        """A test aid: the device's table of cluster moments, (nNodes, 4, 8) float32 -- per child slot A, p.xyz, N.xyz, r."""
+        n = self.winding_info()["nodes"]
+        out = np.zeros((max(1, n), 4, 8), np.float32)
+        self._chk(self._L.moptix_debug_read_winding_table(self._h, C.c_void_p(out.ctypes.data)))
+        return out[:n]
 
     def sign_info(self):
         """dict of what the signed mode rests on: weldedVerts, edges, boundaryEdges, nonManifoldEdges, flippedEdges, degenerateFaces, closed

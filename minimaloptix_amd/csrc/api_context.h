@@ -12,6 +12,7 @@
 #include "refitkernel.h"
 #include "pt_signtopo.h"
 
+namespace pt { struct WindingNode; }      // pt_winding.h (api_winding.hip is the only file that needs its size)
 struct ncclComm;      // RCCL's communicator (api_comm.hip is the only file that sees RCCL's declarations)
 
 namespace pt { namespace api {
@@ -304,6 +305,21 @@ struct moptix_context_t {
     void release() { drop(); frusta.release(); offsets.release(); prims.release(); out.release(); }
   } frustum;
 
+  // ---- winding-number queries (api_winding.hip): nothing of this exists in a context that never asks for a winding number.  The stack
+  // overflow area of the winding kernel, its own (four bytes an entry), and the table of cluster moments (128 bytes per node) are
+  // allocated at the first such query after a build and dropped with the tree they were sized for, where the box queries' area is.
+  // stale: the faces may have moved or the boxes changed since the table was computed (set by moptix_update_faces*, moptix_refit_accel
+  // and moptix_build_accel); the next winding query enqueues the moments pass in front of its kernel.  The staging of the host-pointer
+  // entry point ----
+  struct Winding {
+    DevBuf<int> overflow;
+    DevBuf<pt::WindingNode> table; bool stale = true;
+    uint32_t tableBuilds = 0;          // moments passes enqueued by this context so far (moptix_get_winding_info)
+    DevBuf<float> points, out;
+    void drop() { overflow.release(); table.release(); stale = true; }
+    void release() { drop(); points.release(); out.release(); }
+  } winding;
+
   // ---- signed point queries (api_sign.hip) ----
   // The topology belongs to one set of uploaded faces: taken on the host at the first signed query or moptix_get_sign_info, kept across
   // moptix_update_faces*, moptix_refit_accel and moptix_build_accel, dropped by moptix_clear_scene, moptix_add_mesh and destroy.  Its
@@ -362,6 +378,8 @@ int fetch_faces(moptix_context c);                   // api_refit.hip: the host 
 // the table build are enqueued on the context's stream where they are missing or stale); null in a scene without triangles
 int sign_table_for_query(moptix_context c, const SignRecord*& table);
 void sign_release(moptix_context c);                 // the topology goes (a query in flight finishes first)
+void winding_release(moptix_context c);              // api_winding.hip: the moments table and the overflow area go (a query in flight finishes first)
+int refit_plan(moptix_context c);                    // api_refit.hip: the refit's plan of the built tree (c->refit.levelOrder, levelFirst), made where it is missing
 float* accum_ptr(moptix_context c);
 int ensure_accum(moptix_context c);
 // What a call that uses the device starts with: hipSetDevice, the batch in flight finishes (moptix_sync: timed, watchdog flag read) and,

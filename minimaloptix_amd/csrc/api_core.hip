@@ -144,7 +144,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->radiance.release(); c->point.release(); c->box.release(); c->sweep.release(); c->obb.release(); c->frustum.release(); c->refit.drop();
+  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->radiance.release(); c->point.release(); c->box.release(); c->sweep.release(); c->obb.release(); c->frustum.release(); c->winding.release(); c->refit.drop();
   c->sign.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -200,6 +200,7 @@ int moptix_clear_scene(moptix_context c) {
   }
   c->refit.drop(); c->refit.facesDirty = false; c->refit.hostStale = false; c->refit.facesOnDevice = 0;      // the faces are gone, and the plan with their tree
   sign_release(c);                                             // and the signed queries' topology of them
+  winding_release(c);                                          // and the winding queries' table of their tree
   return MOPTIX_OK;
 }
 
@@ -332,6 +333,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
     if (rc != MOPTIX_OK) return rc;
   }
   c->refit.drop();                                // the plan describes the tree that is about to go
+  winding_release(c);                             // and so do the winding queries' moments and overflow area
   if ((c->query.overflow.p || c->radiance.overflow.p || c->point.overflow.p || c->box.overflow.p || c->sweep.overflow.p || c->obb.overflow.p || c->frustum.overflow.p) && !c->poisoned) {      // an asynchronous query in flight still walks the old tree; the area was sized for its depth
     HIPCHK(c, hipStreamSynchronize(c->stream), "sync before the build");
     c->query.drop(); c->radiance.drop(); c->point.drop(); c->box.drop(); c->sweep.drop(); c->obb.drop(); c->frustum.drop();
@@ -380,6 +382,7 @@ int moptix_build_accel(moptix_context c, const char* kind) {
   c->formatDecided = false;            // choose_node_format at the next render: it needs the camera
   c->sceneDirty = false; c->accelBuilt = true; c->refit.facesDirty = false;
   c->tp.faces.changed = true;   // the device copy of the faces was uploaded afresh (the snapshot stays: the faces keep their upload order)
+  c->winding.stale = true;      // the winding queries' moments are computed again for the new tree
   c->sign.stale = true;         // the signed queries' topology stays, their table is computed again from what was uploaded
   c->tiles.forget();            // new scene: forget which tiles had deep paths
   return MOPTIX_OK;

@@ -69,6 +69,8 @@ int ensure_plan(moptix_context c) {
 
 namespace pt { namespace api {
 
+int refit_plan(moptix_context c) { return ensure_plan(c); }
+
 // The device copy holds the faces the last moptix_build_accel uploaded: the first facesOnDevice of the staging.  moptix_add_mesh may have
 // appended faces since (they exist in the staging only and are left alone); nothing but moptix_clear_scene removes faces, and that
 // clears hostStale.
@@ -96,7 +98,7 @@ int moptix_update_faces(moptix_context c, int32_t first, int32_t n, const float*
     if (!std::isfinite(pos9[i]) || (nrm9 && !std::isfinite(nrm9[i]))) return fail(c, MOPTIX_ERR_INVALID, "non-finite face position or normal");
   if ((rc = fetch_faces(c)) != MOPTIX_OK) return rc;          // a partial host update must not be overwritten by a later fetch of older data
   memcpy(c->facePos.data() + 9 * (size_t)first, pos9, sizeof(float) * 9 * (size_t)n);
-  c->sign.stale = true;
+  c->sign.stale = true; c->winding.stale = true;
   if (nrm9)
     for (int32_t f = 0; f < n; f++)
       if (c->faceHasNrm[first + f]) memcpy(c->faceNrm.data() + 9 * (size_t)(first + f), nrm9 + 9 * (size_t)f, sizeof(float) * 9);
@@ -116,7 +118,7 @@ int moptix_update_faces_device(moptix_context c, int32_t first, int32_t n, const
     return fail(c, MOPTIX_ERR_INVALID, "misaligned device pointer");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   const size_t bytes = sizeof(float) * 9 * (size_t)n;
-  c->sign.stale = true;
+  c->sign.stale = true; c->winding.stale = true;
   if (!c->accelBuilt) {                                       // no device copy of the faces yet: into the staging, now
     if ((rc = fetch_faces(c)) != MOPTIX_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream), "sync");
@@ -166,7 +168,7 @@ int moptix_refit_accel(moptix_context c) {
     c->formatDecided = false; c->nodeFormatUsed = 128;
   }
   r.info.has64 = c->bvh.nodes64 != nullptr && a.nNodes > 0 ? 1u : 0u;
-  r.facesDirty = false; c->sign.stale = true;
+  r.facesDirty = false; c->sign.stale = true; c->winding.stale = true;
   return MOPTIX_OK;
 }
 
