@@ -575,3 +575,50 @@ def tree_containment_errors(nodes, tris, root, nodes64=None):
             nlo = np.minimum(nlo, clo); nhi = np.maximum(nhi, chi)
         lo[n], hi[n] = nlo, nhi
     return bad
+
+
+def tree_containment_errors_exact(nodes, tris, root, face_pos, nodes64=None):
+    """tree_containment_errors without its slack: the vertices come from face_pos [nFaces, 9] float32, the positions as they were handed to
+    the builder or to moptix_update_faces, indexed through the records' prim word (Tri48 word 7), not from the records' rounded edges.
+    Padding only ever moves a bound outwards and min / max are exact, so a child box (the 128-byte form, and the decoded 64-byte form when
+    given) contains every binary32 vertex below it exactly: include/moptix.h promises no less.  Returns the number of (node, child) pairs
+    of either form whose box does not."""
+    nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 32); tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 12)
+    if root < 0:
+        return 0
+    fp = np.asarray(face_pos, np.float32).reshape(-1, 3, 3)
+    assert np.isfinite(fp).all()
+    v = fp[tris[:, 7].view(np.int32)].astype(np.float64)                                # [slot, vertex, axis]: binary32 values, held exactly
+    tlo, thi = v.min(axis=1), v.max(axis=1)
+    box128 = nodes.view(np.float32)[:, 0:24].reshape(-1, 6, 4)                          # lox loy loz hix hiy hiz x child
+    refs = nodes[:, 24:28].view(np.int32); count = nodes[:, 28].view(np.int32)
+    box64 = node64_boxes(nodes64)[0] if nodes64 is not None else None
+    bad = 0
+    lo = {}; hi = {}
+    stack = [(int(root), False)]
+    while stack:
+        n, done = stack.pop()
+        if not done:
+            stack.append((n, True))
+            for k in range(int(count[n])):
+                r = int(refs[n, k])
+                if r >= 0:
+                    stack.append((r, False))
+            continue
+        nlo = np.full(3, np.inf); nhi = np.full(3, -np.inf)
+        for k in range(int(count[n])):
+            r = int(refs[n, k])
+            if r >= 0:
+                clo, chi = lo[r], hi[r]
+            else:
+                first, cnt = (~r) >> 3, ((~r) & 7) + 1
+                clo, chi = tlo[first:first + cnt].min(axis=0), thi[first:first + cnt].max(axis=0)
+            for boxes in (box128, box64):
+                if boxes is None:
+                    continue
+                b = boxes[n, :, k].astype(np.float64)
+                if not ((b[0:3] <= clo).all() and (b[3:6] >= chi).all()):                # a NaN bound contains nothing
+                    bad += 1
+            nlo = np.minimum(nlo, clo); nhi = np.maximum(nhi, chi)
+        lo[n], hi[n] = nlo, nhi
+    return bad

@@ -7,7 +7,7 @@ Not covered, on purpose: the kSahLevels = 40 cut-off (see tests/test_lbvh_cases_
 import numpy as np
 import pytest
 
-from common import HostsimHandle, M, hostsim_bvh, oracle_scene, rmse, tree_containment_errors
+from common import HostsimHandle, M, hostsim_bvh, oracle_scene, rmse, tree_containment_errors, tree_containment_errors_exact
 from aov_helpers import AOV_NAMES, aovsim_render
 from lbvh_cases import BUILDERS, CASE_NAMES, LEAVES, RENDER_CASES, case_faces, case_rays, case_scene, tree_structure_errors
 from query_helpers import querysim, same_bits
@@ -71,6 +71,7 @@ def test_device_tree_is_the_mirrors_and_valid(gpu_ctx, name, leaf, builder):
     errors, measured = tree_structure_errors(nodes, tris, prim, root, leaf, n)
     assert errors == 0 and measured == info.treeDepth
     assert tree_containment_errors(nodes, tris, root if len(nodes) else -1, n64) == 0
+    assert tree_containment_errors_exact(nodes, tris, root if len(nodes) else -1, case_faces(name), n64) == 0      # no slack, the positions as handed in
 
 
 def _assert_traversal(ctx, name, sim):

@@ -9,7 +9,7 @@ float32: no finite input reaches it."""
 import numpy as np
 import pytest
 
-from common import HostsimHandle, M, hostsim_bvh, hostsim_sah_levels, oracle_scene, tree_containment_errors
+from common import HostsimHandle, M, hostsim_bvh, hostsim_sah_levels, oracle_scene, tree_containment_errors, tree_containment_errors_exact
 from aov_helpers import aovsim_render
 from lbvh_cases import (BIG_FIRST, CASE_NAMES, LEAVES, BUILDERS, PLANE_AXIS, RENDER_CASES, case_faces, case_rays, case_scene, middle_split_levels,
                         tree_structure_errors)
@@ -36,6 +36,8 @@ def test_mirror_tree_is_a_valid_tree(name, leaf, builder):
     assert depth == t["depth"]
     assert (len(t["nodes"]) == 0) == (n <= leaf)
     assert tree_containment_errors(t["nodes"], t["tris"], t["root"] if len(t["nodes"]) else -1, t["nodes64"]) == 0
+    # and with no slack at all, from the positions as the builder was handed them: the slack above is wider than all of `geometric`
+    assert tree_containment_errors_exact(t["nodes"], t["tris"], t["root"] if len(t["nodes"]) else -1, case_faces(name), t["nodes64"]) == 0
 
 
 @pytest.mark.parametrize("name", CASE_NAMES)
