@@ -843,7 +843,7 @@ int moptix_query_points_multi(moptix_context ctx, const float* points, int64_t n
  * "query_blocks_per_cu": allocated at the first box query on a tree, kept across refits, dropped by moptix_clear_scene, moptix_build_accel
  * and moptix_destroy.  A box query changes nothing else in the context: moptix_debug_buffer_addresses keeps its slots, and the ray and
  * point queries' buffers are untouched.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
- * Not offered: query triangles, filters by material or primitive kind (oriented boxes and frusta: the next two sections). */
+ * Not offered: filters by material or primitive kind (oriented boxes, frusta and query triangles: the next three sections). */
 enum { MOPTIX_BOX_ANY = 0, MOPTIX_BOX_COUNT = 1 };
 int moptix_query_boxes_device(moptix_context ctx, const float* dBoxes, int64_t n, int32_t mode, int32_t* dOut);
 int moptix_query_boxes(moptix_context ctx, const float* boxes, int64_t n, int32_t mode, int32_t* out);
@@ -948,6 +948,57 @@ int moptix_query_frusta_list_device(moptix_context ctx, const float* dFrusta, in
                                     int32_t* dCounts);
 int moptix_query_frusta_list(moptix_context ctx, const float* frusta, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
 
+/* ---- triangle queries: the primitives that meet each of the caller's triangles ------------------------------------------------------------
+ * The box queries' question for another triangle: the narrow phase of mesh against mesh.  The self-collision test of a mesh that
+ * moptix_update_faces / moptix_refit_accel deform every step, the candidate pairs of intersection curves and booleans, a tool against a
+ * part, the exact answer behind a box or oriented box broad phase.
+ * A query is nine floats, 36 bytes:  ax ay az  bx by bz  cx cy cz, the three vertices -- a row of a contiguous (n, 3, 3) array
+ * vertices[faces].  Valid: all nine finite.  An invalid query meets nothing, decided before any traversal.  A zero-area query (a segment,
+ * a point) is valid.  Triangles are closed sets: touching counts.  All arithmetic is binary32 under the contract of csrc/pt_math.h, without
+ * contraction; csrc/pt_tri.h states every operation in order.  S(query) is the set of primitive ids whose predicate holds; ids are the box
+ * queries' (spheres, then quads, then triangles by original face id); every primitive counts.  S is a function of the nine floats and the
+ * device records alone.
+ *   triangle   the record's triangle as the box queries see it.  (A) the per-axis min / max of its computed vertices against the exact
+ *              min / max box of the query's vertices, strict rejections -- the box queries' own first step; (B) both triangles in the
+ *              frame at the query's first vertex (a is subtracted from all six vertices), then a separating-axis test over 23 axes in a
+ *              fixed order: the two normals n1, n2; the nine cross(e_i, f_j) of the query's edges e and the primitive's f; cross(n1, e_i),
+ *              cross(n1, f_j), cross(n2, e_i), cross(n2, f_j).  On each axis both triangles' three vertices are projected and the pair is
+ *              rejected if one interval lies strictly beyond the other: a NaN, an equality or a zero axis rejects nothing.  The
+ *              cross-normal axes decide coplanar pairs and a segment or point against a triangle of non-zero area.
+ *              Two zero-area triangles against each other are decided by no finite axis list: for such a pair the predicate is still
+ *              this fixed function, but only a superset of the geometric answer (it misses no pair that meets).
+ *   sphere     the surface: dmin2 = the squared distance from the centre to the query triangle (the point queries' triangle function),
+ *              dmax2 = the largest squared distance to a vertex; overlap iff dmin2 <= radius^2 <= dmax2.  A triangle wholly inside the
+ *              ball meets nothing.
+ *   quad       the four corners of the box queries' quad as two triangles through the triangle predicate.
+ * Tree, leaf size, builder, node format, "query_blocks_per_cu" and scheduling play no part: the walk is the box queries' own against the
+ * query's box, step A makes that test part of the predicate, and csrc/pt_tri.h carries the box queries' proof over: the answer is the loop's
+ * over every primitive, with no margin, in both node forms and after a refit.
+ *   mode       MOPTIX_BOX_ANY / MOPTIX_BOX_COUNT as for moptix_query_boxes.
+ *   list       the box queries' contract, word for word: offsets are n + 1 non-decreasing int64 entries into prims; counts[i] = |S|
+ *              always; if |S| <= capacity the slice holds S in ascending id, then -1 up to the capacity; otherwise the whole slice is -1
+ *              and the caller sees counts[i] > capacity.  Every byte of every slice is defined.
+ *   moptix_query_tris_device       dTris: device memory, 4-byte aligned (a query is read as nine 4-byte loads); dOut: device memory,
+ *                                  4-byte aligned.  Asynchronous on the context's stream: no host wait, no allocation on a warm call.
+ *   moptix_query_tris              host pointers, blocking: upload, query, read back (staging kept in the context)
+ *   moptix_query_tris_list_device  dTris: 4-byte aligned; dOffsets: 8-byte aligned; dPrims, dCounts: 4-byte aligned.  Asynchronous.  The
+ *                                  offsets are the caller's to get right: the kernel writes where they point.
+ *   moptix_query_tris_list         host pointers, blocking; offsets are checked here: non-decreasing, offsets[0] >= 0.
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 queries); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_boxes ("faces dirty" before a refit included).
+ * The triangle queries keep a stack overflow area of their own: allocated at the first such query on a tree, kept across refits, dropped
+ * by moptix_clear_scene, moptix_build_accel and moptix_destroy.  They change nothing else in the context:
+ * moptix_debug_buffer_addresses keeps its slots, and the other queries' buffers are untouched.
+ * A query equal to a face of the mesh finds that face and its neighbours (they touch); Context.self_intersections of the Python layer
+ * drops the pairs that share a vertex index.
+ * Not offered: the intersection segment of a pair, signed penetration depth, time-continuous triangle-triangle contact, a device-side
+ * pairing kernel, an exact answer for two zero-area triangles, filters by material or primitive kind. */
+int moptix_query_tris_device(moptix_context ctx, const float* dTris, int64_t n, int32_t mode, int32_t* dOut);
+int moptix_query_tris(moptix_context ctx, const float* tris, int64_t n, int32_t mode, int32_t* out);
+int moptix_query_tris_list_device(moptix_context ctx, const float* dTris, int64_t n, const int64_t* dOffsets, int32_t* dPrims,
+                                  int32_t* dCounts);
+int moptix_query_tris_list(moptix_context ctx, const float* tris, int64_t n, const int64_t* offsets, int32_t* prims, int32_t* counts);
+
 /* ---- winding-number queries: inside / outside for the meshes users actually have ----------------------------------------------------
  * MOPTIX_POINT_SIGNED takes its sign from pseudonormals, which is right only for a closed, consistently wound mesh.  The generalised
  * winding number w(q) (Jacobson et al. 2013) is the sum of the signed solid angles of all primitives seen from q over 4 pi: 1 inside and
@@ -1051,7 +1102,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_winding*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_tris*, moptix_query_winding*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -1066,7 +1117,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray, point, box, oriented box, frustum and sweep queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point, box, oriented box, frustum, triangle and sweep queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

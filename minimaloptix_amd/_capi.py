@@ -230,6 +230,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_sweeps_device", "moptix_query_sweeps",
     "moptix_query_obbs_device", "moptix_query_obbs", "moptix_query_obbs_list_device", "moptix_query_obbs_list",
     "moptix_query_frusta_device", "moptix_query_frusta", "moptix_query_frusta_list_device", "moptix_query_frusta_list",
+    "moptix_query_tris_device", "moptix_query_tris", "moptix_query_tris_list_device", "moptix_query_tris_list",
     "moptix_query_winding_device", "moptix_query_winding", "moptix_get_winding_info", "moptix_debug_read_winding_table",
     "moptix_update_faces", "moptix_update_faces_device", "moptix_refit_accel", "moptix_get_refit_info", "moptix_debug_buffer_addresses",
 ]
@@ -351,6 +352,10 @@ def device_lib():
         L.moptix_query_frusta.argtypes = [vp, f32p, C.c_int64, i32, i32p]
         L.moptix_query_frusta_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
         L.moptix_query_frusta_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
+        L.moptix_query_tris_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_tris.argtypes = [vp, f32p, C.c_int64, i32, i32p]
+        L.moptix_query_tris_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+        L.moptix_query_tris_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
         L.moptix_query_winding_device.argtypes = [vp, vp, C.c_int64, vp]
         L.moptix_query_winding.argtypes = [vp, f32p, C.c_int64, f32p]
         L.moptix_get_winding_info.argtypes = [vp, C.POINTER(WindingInfo)]

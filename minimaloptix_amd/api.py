@@ -863,8 +863,81 @@ class Context:
         tensor on this context's device is read where it is, and the results are tensors on that device."""
         return self._query_box_family("query_frusta", "moptix_query_frusta", frusta, 24, (6, 4), "six planes nx ny nz d", mode, max_prims)
 
+    def query_tris(self, tris, mode="any", max_prims=None):
+        """The primitives that meet each of the caller's triangles (closed sets: touching counts); blocking.  A query is nine floats, the
+        three vertices ax ay az bx by bz cx cy cz -- a row of vertices[faces].  A zero-area query (a segment, a point) is valid; a query
+        with a non-finite float meets nothing.  Triangles and quads are tested exactly up to rounding wherever one of the two triangles
+        has non-zero area (two zero-area triangles: a superset); a sphere by its surface.  Modes and return values are query_boxes':
+        "any" and "count" give int32 per query; "list" gives the CSR pair (prims, offsets), or with max_prims=K (prims (n, K), counts).
+        A numpy (n, 9) or (n, 3, 3) array takes the host path and the results are numpy arrays.  A contiguous (n, 9) or (n, 3, 3) float32
+        torch tensor on this context's device is read where it is, and the results are tensors on that device."""
+        if hasattr(tris, "data_ptr") and tris.dim() == 3 and tuple(tris.shape[1:]) == (3, 3) and tris.is_contiguous():
+            tris = tris.view(-1, 9)                                  # the same memory, read in place
+        return self._query_box_family("query_tris", "moptix_query_tris", tris, 9, (3, 3), "ax ay az bx by bz cx cy cz", mode, max_prims)
+
+    def _first_face_id(self, n_faces):
+        """The primitive id of face 0, nSpheres + nQuads: what a box holding every scene within 1e30 units counts, less the triangles."""
+        n_tris = int(self.accel_info().nTriangles)
+        if n_faces != n_tris:
+            raise ValueError("self_intersections: %d faces, but the tree was built on %d" % (n_faces, n_tris))
+        everything = np.array([[-1e30, -1e30, -1e30, 1e30, 1e30, 1e30]], np.float32)
+        return int(self.query_boxes(everything, "count")[0]) - n_tris
+
+    def self_intersections(self, vertices, faces, max_prims=None):
+        """The pairs of faces of the uploaded mesh that meet without sharing a vertex: vertices (V, 3) float32 and faces (F, 3) integer
+        are the mesh as uploaded (and as last updated), whose face f is primitive nSpheres + nQuads + f; blocking.  Runs the list form of
+        query_tris on vertices[faces] and returns the sorted unique pairs (i, j), i < j, of face ids as a (P, 2) int64 array -- numpy for
+        numpy input, a tensor on the device for tensors on this context's device.  A pair is reported if either direction reports it:
+        the uploaded record's second and third vertex are two roundings away from the caller's, so one direction alone may not be
+        symmetric in the last bit.  Pairs with a common vertex index touch by construction and are left out, a face against itself too.
+        max_prims=K: one pass with K slots per face instead of two passes; ValueError if a face meets more than K primitives."""
+        on_device = hasattr(vertices, "data_ptr")
+        if on_device:
+            import torch
+            if not hasattr(faces, "data_ptr"):
+                faces = torch.as_tensor(np.asarray(faces), device=vertices.device)
+            if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or vertices.dtype != torch.float32:
+                raise ValueError("self_intersections: vertices must be (V, 3) float32 and faces (F, 3) integer")
+            f = faces.to(torch.int64)
+            tris = vertices[f].contiguous()
+        else:
+            v, f = np.asarray(vertices, np.float32), np.asarray(faces)
+            if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+                raise ValueError("self_intersections: vertices must be (V, 3) float32 and faces (F, 3) integer")
+            f = f.astype(np.int64)
+            tris = np.ascontiguousarray(v[f])
+        n = int(f.shape[0])
+        if n == 0:
+            return torch.zeros((0, 2), dtype=torch.int64, device=vertices.device) if on_device else np.zeros((0, 2), np.int64)
+        base = self._first_face_id(n)
+        if max_prims is None:
+            prims, offsets = self.query_tris(tris, "list")
+            counts = offsets[1:] - offsets[:-1]
+        else:
+            rows, counts = self.query_tris(tris, "list", max_prims=max_prims)
+            if int(counts.max()) > int(max_prims):
+                raise ValueError("self_intersections: a face meets %d primitives, more than max_prims = %d" % (int(counts.max()), int(max_prims)))
+            prims = rows[rows >= 0]                                  # row-major: face by face, ascending within a face
+        if on_device:
+            i = torch.repeat_interleave(torch.arange(n, device=f.device), counts.to(torch.int64))
+            j = prims.to(torch.int64) - base
+            keep = j >= 0
+            i, j = i[keep], j[keep]
+            keep = ~(f[i][:, :, None] == f[j][:, None, :]).any(dim=2).any(dim=1)
+            i, j = i[keep], j[keep]
+            pairs = torch.stack([torch.minimum(i, j), torch.maximum(i, j)], dim=1)
+            return torch.unique(pairs, dim=0) if len(pairs) else pairs
+        i = np.repeat(np.arange(n, dtype=np.int64), np.asarray(counts, np.int64))
+        j = prims.astype(np.int64) - base
+        keep = j >= 0
+        i, j = i[keep], j[keep]
+        keep = ~(f[i][:, :, None] == f[j][:, None, :]).any(axis=(1, 2))
+        i, j = i[keep], j[keep]
+        pairs = np.stack([np.minimum(i, j), np.maximum(i, j)], axis=1)
+        return np.unique(pairs, axis=0) if len(pairs) else pairs.reshape(0, 2)
+
     def _query_box_family(self, who, entry, boxes, width, folded, layout, mode, max_prims):
-        """query_boxes, query_obbs and query_frusta: `entry`, `entry`_device, `entry`_list and `entry`_list_device on (n, width) float32 rows; a numpy
+        """query_boxes, query_obbs, query_frusta and query_tris: `entry`, `entry`_device, `entry`_list and `entry`_list_device on (n, width) float32 rows; a numpy
         array may also have the shape (n,) + folded."""
         fn = lambda suffix: getattr(self._L, entry + suffix)      # looked up after the arguments are checked
         if mode not in self.BOX_MODES and mode != "list":

@@ -295,6 +295,16 @@ struct moptix_context_t {
     void release() { drop(); obbs.release(); offsets.release(); prims.release(); out.release(); }
   } obb;
 
+  // ---- triangle queries (api_tri.hip): the stack overflow area of the triangle query kernel, its own (four bytes an entry: a reference),
+  // allocated at the first such query after a build, kept across refits and dropped with the tree it was sized for, where the box
+  // queries' is; the staging of the host-pointer entry points (tris, offsets, prims; out: the int32 results or counts) ----
+  struct TriQuery {
+    DevBuf<int> overflow;
+    DevBuf<float> tris; DevBuf<long long> offsets; DevBuf<int> prims, out;
+    void drop() { overflow.release(); }
+    void release() { drop(); tris.release(); offsets.release(); prims.release(); out.release(); }
+  } tri;
+
   // ---- frustum queries (api_frustum.hip): the stack overflow area of the frustum kernel, its own (four bytes an entry: a reference),
   // allocated at the first such query after a build, kept across refits and dropped with the tree it was sized for, where the box
   // queries' is; the staging of the host-pointer entry points (frusta, offsets, prims; out: the int32 results or counts) ----
