@@ -7,6 +7,7 @@
 #   make pointmultisim -> tests/pointmultisim/libpointmultisim.so (test infrastructure: the CPU mirror of the K-nearest point queries)
 #   make boxsim     -> tests/boxsim/libboxsim.so tests/sweepsim/libsweepsim.so                (test infrastructure: the CPU mirror of the box queries)
 #   make sweepsim   -> tests/sweepsim/libsweepsim.so            (test infrastructure: the CPU mirror of the sweep queries)
+#   make segmentsim -> tests/segmentsim/libsegmentsim.so        (test infrastructure: the CPU mirror of the segment queries)
 #   make obbsim     -> tests/obbsim/libobbsim.so                (test infrastructure: the CPU mirror of the oriented box queries)
 #   make frustumsim -> tests/frustumsim/libfrustumsim.so        (test infrastructure: the CPU mirror of the frustum queries)
 #   make trisim     -> tests/trisim/libtrisim.so                (test infrastructure: the CPU mirror of the triangle queries)
@@ -30,7 +31,7 @@ BUILD    ?= build
 HIPFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -fno-slp-vectorize -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -include cstring
 CXXFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -fno-math-errno -mavx2 -mfma -Wall -Wno-unused-function -Wno-unknown-pragmas
 
-DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_radiance.hip $(CSRC)/api_point.hip $(CSRC)/api_box.hip $(CSRC)/api_obb.hip $(CSRC)/api_frustum.hip $(CSRC)/api_tri.hip $(CSRC)/api_winding.hip $(CSRC)/api_sweep.hip $(CSRC)/api_sign.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/facemotionkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/radiancekernel.hip $(CSRC)/pointkernel.hip $(CSRC)/boxkernel.hip $(CSRC)/obbkernel.hip $(CSRC)/frustumkernel.hip $(CSRC)/trikernel.hip $(CSRC)/windingkernel.hip $(CSRC)/sweepkernel.hip $(CSRC)/signkernel.hip $(CSRC)/refitkernel.hip
+DEV_SRCS := $(CSRC)/api_core.hip $(CSRC)/api_options.hip $(CSRC)/api_render.hip $(CSRC)/api_aov.hip $(CSRC)/api_denoise.hip $(CSRC)/api_temporal.hip $(CSRC)/api_adaptive.hip $(CSRC)/api_query.hip $(CSRC)/api_radiance.hip $(CSRC)/api_point.hip $(CSRC)/api_box.hip $(CSRC)/api_obb.hip $(CSRC)/api_frustum.hip $(CSRC)/api_tri.hip $(CSRC)/api_winding.hip $(CSRC)/api_sweep.hip $(CSRC)/api_segment.hip $(CSRC)/api_sign.hip $(CSRC)/api_refit.hip $(CSRC)/api_comm.hip $(CSRC)/megakernel.hip $(CSRC)/queuekernel.hip $(CSRC)/queuekernel_lean.hip $(CSRC)/packetkernel.hip $(CSRC)/packetkernel_n128.hip $(CSRC)/drainkernel.hip $(CSRC)/lbvh.hip $(CSRC)/aovkernel.hip $(CSRC)/denoisekernel.hip $(CSRC)/temporalkernel.hip $(CSRC)/facemotionkernel.hip $(CSRC)/adaptivekernel.hip $(CSRC)/querykernel.hip $(CSRC)/radiancekernel.hip $(CSRC)/pointkernel.hip $(CSRC)/boxkernel.hip $(CSRC)/obbkernel.hip $(CSRC)/frustumkernel.hip $(CSRC)/trikernel.hip $(CSRC)/windingkernel.hip $(CSRC)/sweepkernel.hip $(CSRC)/segmentkernel.hip $(CSRC)/signkernel.hip $(CSRC)/refitkernel.hip
 DEV_OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(DEV_SRCS))
 DEV_HDRS := $(wildcard $(CSRC)/*.h) include/moptix.h
 HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(HOST)/standin_scenes.cpp $(HOST)/image_read.cpp $(HOST)/jpeg_read.cpp \
@@ -38,7 +39,7 @@ HOST_SRCS := $(HOST)/obj_loader.cpp $(HOST)/scene_file.cpp $(HOST)/scenes.cpp $(
 HOST_OBJS := $(patsubst $(HOST)/%.cpp,build/host_%.o,$(HOST_SRCS))
 HOST_HDRS := $(wildcard $(HOST)/*.h) $(wildcard $(CSRC)/pt_*.h) include/moptix.h include/moptix_host.h
 
-all: device host oracle hostsim pointmultisim boxsim sweepsim obbsim frustumsim trisim windingsim devarith loopback
+all: device host oracle hostsim pointmultisim boxsim sweepsim segmentsim obbsim frustumsim trisim windingsim devarith loopback
 
 device: $(LIBDIR)/$(LIBNAME)
 host: $(LIBDIR)/libmoptix_host.so $(LIBDIR)/moptix_render
@@ -52,6 +53,8 @@ boxsim:
 	$(MAKE) -C tests/boxsim -s
 sweepsim:
 	$(MAKE) -C tests/sweepsim -s
+segmentsim:
+	$(MAKE) -C tests/segmentsim -s
 obbsim:
 	$(MAKE) -C tests/obbsim -s
 frustumsim:
@@ -94,6 +97,6 @@ $(LIBDIR)/moptix_render: $(HOST)/main.cpp $(LIBDIR)/libmoptix_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST)/main.cpp -L$(LIBDIR) -lmoptix_host -lmoptix -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
 clean:
-	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/pointmultisim/libpointmultisim.so tests/boxsim/libboxsim.so tests/sweepsim/libsweepsim.so tests/obbsim/libobbsim.so tests/frustumsim/libfrustumsim.so tests/trisim/libtrisim.so tests/windingsim/libwindingsim.so tests/devarith/libdevarith.so tests/devarith/*.o tests/rccl_loopback/librccl_loopback.so
+	rm -rf build $(LIBDIR)/*.so $(LIBDIR)/moptix_render oracle/liboracle.so tests/hostsim/libhostsim.so tests/pointmultisim/libpointmultisim.so tests/boxsim/libboxsim.so tests/sweepsim/libsweepsim.so tests/segmentsim/libsegmentsim.so tests/obbsim/libobbsim.so tests/frustumsim/libfrustumsim.so tests/trisim/libtrisim.so tests/windingsim/libwindingsim.so tests/devarith/libdevarith.so tests/devarith/*.o tests/rccl_loopback/librccl_loopback.so
 
-.PHONY: all device host oracle hostsim pointmultisim boxsim sweepsim obbsim frustumsim trisim windingsim devarith loopback clean
+.PHONY: all device host oracle hostsim pointmultisim boxsim sweepsim segmentsim obbsim frustumsim trisim windingsim devarith loopback clean

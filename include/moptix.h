@@ -1086,6 +1086,55 @@ typedef struct { float t; int32_t prim; int32_t mat; float u, v; float p[3]; } m
 int moptix_query_sweeps_device(moptix_context ctx, const float* dSweeps, int64_t n, int32_t mode, void* dOut);
 int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int32_t mode, void* out);
 
+/* ---- segment queries: the nearest surface point to each segment ---------------------------------------------------------------------
+ * The question the point queries answer for a point, asked for a segment: how far is it from the scene, and where.  The edge-edge half
+ * of a proximity narrow phase (moptix_query_points is the vertex-face half), clearance and contact of a capsule -- a segment with a
+ * radius -- against a mesh that is refitted every step, cables, rods, tool shafts.
+ * A segment is eight floats  ax ay az bx by bz maxDist pad , read as two 16-byte loads; pad is ignored.  r2 = maxDist * maxDist, +inf =
+ * no limit, exactly as for the point queries.  Invalid -- a miss, decided before any traversal: any of the six coordinates non-finite,
+ * maxDist NaN or maxDist <= 0.  a == b is valid: against a triangle or a sphere it is the point query's function, so in a scene without
+ * quads the record's dist, prim, mat and p are the point query's bit for bit.  A quad is measured as its two triangles here and by its
+ * clamped coordinates there: in a scene with quads the two queries can name different primitives for the same point.
+ * All arithmetic is binary32 under the contract of csrc/pt_math.h, without contraction; csrc/pt_segment.h states every operation in order.
+ * d2(prim) -- ids are the queries' (spheres, then quads, then triangles by original face id); every primitive counts, whatever its material:
+ *   triangle   the record's triangle as the point queries see it.  The least of six candidates, the first of equal ones: the point query's
+ *              answer at a (feature 0, s = 0) and at b (1, s = 1); the closest pair between the segment and each edge, in the point query's
+ *              edge order (2, 3, 4), by one segment-segment routine that is clamps and comparisons only; and the crossing (5): the ray
+ *              queries' own triangle test on (a, b - a) over (0, 1) accepts at t, then d2 = 0, s = t, p = a + (b - a) * t.  "Distance 0" is
+ *              "the closest ray query on that ray can report this triangle".  A zero-area triangle needs no special case; no NaN comes
+ *              out of finite input.
+ *   sphere     the surface.  With dmin the centre's distance to the segment and dmax the larger of the ends' distances to it:
+ *              dmin > R: dmin - R, at the segment's point nearest the centre (feature 0 or 1 at an end, 2 in between); dmax < R: R - dmax,
+ *              at that end (0 or 1); otherwise 0, at the first point of the segment on the surface (5).
+ *   quad       the two triangles of the box queries' corners; the second triangle's edges report feature 6, 7, 8.
+ *   MOPTIX_SEGMENT_CLOSEST  one moptix_segment_hit (32 bytes, two 16-byte stores) per segment: the primitive least by (d2, prim) among
+ *                           those with d2 < r2; at exactly equal d2 the lower id.  dist = sqrt(d2); s in [0, 1] the parameter of the
+ *                           nearest point a + (b - a) * s on the segment; p the nearest point on the primitive; feature the candidate
+ *                           that won.  A miss: dist = maxDist as given, prim = mat = -1, s = p = feature = 0.
+ *   MOPTIX_SEGMENT_ANY      one int32 per segment: 1 iff MOPTIX_SEGMENT_CLOSEST reports a primitive.  The walk stops at the first
+ *                           primitive it accepts.
+ * The answer is a function of the segment and the device records alone: tree, leaf size, builder, node format, "query_blocks_per_cu" and
+ * scheduling play no part (csrc/pt_segment.h derives the margin of the walk's prune).
+ *   moptix_query_segments_device  dSegments: device memory, 16-byte aligned; dOut: device memory, 16-byte aligned (closest) or 4-byte
+ *                                 aligned (any).  Asynchronous on the context's stream.
+ *   moptix_query_segments         host pointers, blocking: upload, query, read back (staging kept in the context)
+ * n may be any int64 >= 0 (longer batches are cut into launches of 2^30 segments); n == 0 -> MOPTIX_OK.  MOPTIX_ERR_INVALID: null or
+ * misaligned pointers, n < 0, an unknown mode; state errors as moptix_query_points ("faces dirty" before a refit included).
+ * The segment queries keep a stack overflow area of their own, sized like the others': allocated at the first segment query on a tree,
+ * kept across refits, dropped by moptix_clear_scene, moptix_build_accel and moptix_destroy.  A segment query changes nothing else in the
+ * context.  Sphere and quad tables are read as they are when the kernel runs (moptix_update_spheres).
+ * WARNING, segments in a primitive's plane.  "Distance 0" is the ray queries' triangle test, which is exact to
+ * nu / sin(angle between the segment and the plane), nu = 2^-19 (|b - a| + the largest |vertex - a|), for a segment that comes within nu
+ * of the plane, and undefined for a segment IN the plane: such a segment can be reported as crossing (dist = 0, feature = 5) a triangle
+ * or quad of that plane that lies beside it, at any distance, and there the answer may depend on the tree.  Edges of a flat region
+ * queried against the region's own non-incident faces are this case (edge_proximity on a planar patch): lift them off the plane by more
+ * than nu, or ignore feature 5 on faces coplanar with the edge.  Every other feature is a distance, good to 1e-7 of the scene's extent.
+ * Not offered: a radius per segment (subtract it from dist; it belongs in maxDist), all primitives within maxDist, swept capsules. */
+enum { MOPTIX_SEGMENT_CLOSEST = 0, MOPTIX_SEGMENT_ANY = 1 };
+typedef struct { float dist; int32_t prim; int32_t mat; float s; float p[3]; int32_t feature; } moptix_segment_hit;
+int moptix_query_segments_device(moptix_context ctx, const float* dSegments, int64_t n, int32_t mode, void* dOut);
+int moptix_query_segments(moptix_context ctx, const float* segments, int64_t n, int32_t mode, void* out);
+
 /* ---- mesh updates and refit ------------------------------------------------- */
 /* Moves the vertices of uploaded faces and fits the built tree to them in place, without a rebuild.
  * Faces are numbered in upload order across all moptix_add_mesh calls: the prim a triangle reports (moptix_hit, the AOVs' primId)
@@ -1102,7 +1151,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  * pointer, a non-finite value (host form).  nFaces == 0 changes nothing.
  * Before moptix_build_accel an update only edits the staging.  On a built scene it leaves the context "faces dirty": the tree no
  * longer bounds the triangles, so every entry point that traces (moptix_launch / render*, moptix_render_aovs, moptix_render_adaptive,
- * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_tris*, moptix_query_winding*, moptix_query_sweeps*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
+ * moptix_query_rays*, moptix_query_radiance*, moptix_query_points*, moptix_query_boxes*, moptix_query_obbs*, moptix_query_frusta*, moptix_query_tris*, moptix_query_winding*, moptix_query_sweeps*, moptix_query_segments*, moptix_debug_trace, moptix_validate) returns MOPTIX_ERR_STATE until moptix_refit_accel or moptix_build_accel has
  * run.  The denoiser entries do not trace and are not affected.
  *   moptix_refit_accel          blocking, on the context's stream.  Keeps the tree's topology and the order of the triangle records and
  *                               rewrites every triangle record (p0, e0 = p1 - p0, e1 = p0 - p2; material, face id and shadow class
@@ -1117,7 +1166,7 @@ int moptix_query_sweeps(moptix_context ctx, const float* sweeps, int64_t n, int3
  *                               If a refitted node is too wide for the 64-byte form, that form is dropped as at build (has64 = 0, the
  *                               node format is decided again at the next render); a tree built without it does not gain one.
  *                               Unlike a rebuild it keeps the depth history of the beauty launches, the node-format verdict (while the
- *                               64-byte form survives), the ray, point, box, oriented box, frustum, triangle and sweep queries' stack overflow areas (the tree's depth cannot change), the
+ *                               64-byte form survives), the ray, point, box, oriented box, frustum, triangle, sweep and segment queries' stack overflow areas (the tree's depth cannot change), the
  *                               AOVs, the denoiser's, temporal and adaptive state, and allocates nothing after the first refit on a
  *                               tree.  A tree whose root is a leaf refits its records only; a scene without triangles: MOPTIX_OK,
  *                               nothing done.  MOPTIX_ERR_STATE before moptix_build_accel.

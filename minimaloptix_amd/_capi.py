@@ -170,11 +170,17 @@ class PointHit(C.Structure):
     _fields_ = [("dist", C.c_float), ("prim", C.c_int32), ("mat", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("p", C.c_float * 3)]
 
 
+class SegmentHit(C.Structure):
+    """moptix_segment_hit: the record of a closest segment query (32 bytes)."""
+    _fields_ = [("dist", C.c_float), ("prim", C.c_int32), ("mat", C.c_int32), ("s", C.c_float), ("p", C.c_float * 3), ("feature", C.c_int32)]
+
+
 POINT_CLOSEST, POINT_ANY, POINT_SIGNED = 0, 1, 2
 POINT_MULTI_COUNT_ALL = 1
 POINT_MULTI_MAX_NEAR = 64
 BOX_ANY, BOX_COUNT = 0, 1
 SWEEP_CLOSEST, SWEEP_ANY = 0, 1
+SEGMENT_CLOSEST, SEGMENT_ANY = 0, 1
 RADIANCE_CLAMP = 1
 
 
@@ -228,6 +234,7 @@ DEVICE_SYMBOLS = [
     "moptix_query_points_multi_device", "moptix_query_points_multi",
     "moptix_query_boxes_device", "moptix_query_boxes", "moptix_query_boxes_list_device", "moptix_query_boxes_list",
     "moptix_query_sweeps_device", "moptix_query_sweeps",
+    "moptix_query_segments_device", "moptix_query_segments",
     "moptix_query_obbs_device", "moptix_query_obbs", "moptix_query_obbs_list_device", "moptix_query_obbs_list",
     "moptix_query_frusta_device", "moptix_query_frusta", "moptix_query_frusta_list_device", "moptix_query_frusta_list",
     "moptix_query_tris_device", "moptix_query_tris", "moptix_query_tris_list_device", "moptix_query_tris_list",
@@ -344,6 +351,8 @@ def device_lib():
         L.moptix_query_boxes_list.argtypes = [vp, f32p, C.c_int64, i64p, i32p, i32p]
         L.moptix_query_sweeps_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_sweeps.argtypes = [vp, f32p, C.c_int64, i32, vp]
+        L.moptix_query_segments_device.argtypes = [vp, vp, C.c_int64, i32, vp]
+        L.moptix_query_segments.argtypes = [vp, f32p, C.c_int64, i32, vp]
         L.moptix_query_obbs_device.argtypes = [vp, vp, C.c_int64, i32, vp]
         L.moptix_query_obbs.argtypes = [vp, f32p, C.c_int64, i32, i32p]
         L.moptix_query_obbs_list_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]

@@ -16,6 +16,8 @@ assert POINT_DTYPE.itemsize == C.sizeof(K.PointHit) == 32
 # moptix_sweep_hit as a numpy record (include/moptix.h "sweep queries")
 SWEEP_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("mat", np.int32), ("u", np.float32), ("v", np.float32), ("p", np.float32, (3,))])
 assert SWEEP_DTYPE.itemsize == 32
+SEGMENT_DTYPE = np.dtype([("dist", np.float32), ("prim", np.int32), ("mat", np.int32), ("s", np.float32), ("p", np.float32, (3,)), ("feature", np.int32)])
+assert SEGMENT_DTYPE.itemsize == 32
 
 
 def scenes_dir():
@@ -1028,6 +1030,81 @@ class Context:
         if m == K.SWEEP_ANY:
             return out
         return _record_views(out, "t", "p")
+
+    # ---- segment queries (include/moptix.h "segment queries") ----
+    SEGMENT_MODES = dict(closest=K.SEGMENT_CLOSEST, any=K.SEGMENT_ANY)
+
+    def query_segments(self, segments, mode="closest", max_dist=None):
+        """The nearest surface point to each of the caller's segments ("closest"), or "is anything within maxDist of it" ("any");
+        blocking.  segments: (n, 8) rows ax ay az bx by bz maxDist pad (max_dist is then not consulted), or the end points alone as
+        (n, 2, 3) or (n, 6) together with max_dist, a scalar or one value per segment (+inf = no limit).
+        A numpy array takes the host path: "closest" returns a SEGMENT_DTYPE record array (dist; prim, mat; s, the parameter of the
+        nearest point a + (b - a) * s on the segment; p, the nearest point on the primitive; feature, what was nearest: 0 end a, 1 end b,
+        2-4 an edge of the triangle, 5 the segment crosses the primitive; a miss has prim -1 and dist = maxDist), "any" an int32 array.
+        A float32 torch tensor on this context's device -- a contiguous (n, 8) one is read where it is -- gives tensors on that device:
+        "any" an int32 tensor; "closest" a dict of views dist, prim, mat, s, p, feature into "records", the (n, 8) float32 tensor of the
+        raw moptix_segment_hit records."""
+        if mode not in self.SEGMENT_MODES:
+            raise ValueError("query_segments: mode %r (closest or any)" % (mode,))
+        m = self.SEGMENT_MODES[mode]
+        if isinstance(segments, np.ndarray) or not hasattr(segments, "data_ptr"):
+            s = np.asarray(segments, np.float32)
+            if s.ndim == 3 and s.shape[1:] == (2, 3):
+                s = s.reshape(-1, 6)
+            if s.ndim != 2 or s.shape[1] not in (6, 8):
+                raise ValueError("query_segments: segments must be (n, 8), or (n, 2, 3) / (n, 6) with max_dist, not %r" % (s.shape,))
+            if s.shape[1] == 6:
+                if max_dist is None:
+                    raise ValueError("query_segments: end points alone need max_dist")
+                md = np.asarray(max_dist, np.float32)
+                if md.ndim > 1 or (md.ndim == 1 and len(md) != len(s)):
+                    raise ValueError("query_segments: max_dist must be a scalar or one value per segment")
+                s = np.concatenate([s, np.broadcast_to(md.reshape(-1, 1) if md.ndim else md, (len(s), 1)), np.zeros((len(s), 1), np.float32)], axis=1)
+            s = np.ascontiguousarray(s, np.float32)
+            out = np.zeros(len(s), np.int32 if m == K.SEGMENT_ANY else SEGMENT_DTYPE)
+            self._chk(self._L.moptix_query_segments(self._h, s.ctypes.data_as(C.POINTER(C.c_float)), len(s), m, C.c_void_p(out.ctypes.data)))
+            return out
+        import torch
+        if segments.dim() == 3 and tuple(segments.shape[1:]) == (2, 3):
+            segments = segments.reshape(-1, 6)
+        if segments.dim() == 2 and segments.shape[1] == 6:
+            if max_dist is None:
+                raise ValueError("query_segments: end points alone need max_dist")
+            md = torch.as_tensor(max_dist, dtype=torch.float32, device=segments.device)
+            if md.dim() > 1 or (md.dim() == 1 and md.shape[0] != segments.shape[0]):
+                raise ValueError("query_segments: max_dist must be a scalar or one value per segment")
+            n = segments.shape[0]
+            segments = torch.cat([segments, md.reshape(-1, 1).expand(n, 1), torch.zeros((n, 1), dtype=segments.dtype, device=segments.device)], dim=1).contiguous()
+        _check_tensor("query_segments", "segments", segments, ("torch.float32",), _rows(8), "shape (n, 8), ax ay az bx by bz maxDist pad, or (n, 2, 3) / (n, 6) with max_dist", self.device)
+        n = segments.shape[0]
+        if m == K.SEGMENT_ANY:
+            out = torch.empty(n, dtype=torch.int32, device=segments.device)
+        else:
+            out = torch.empty((n, 8), dtype=torch.float32, device=segments.device)
+        torch.cuda.current_stream(segments.device).synchronize()      # the segments are ready before the context's stream reads them
+        self._chk(self._L.moptix_query_segments_device(self._h, C.c_void_p(segments.data_ptr()), n, m, C.c_void_p(out.data_ptr())))
+        self.sync()
+        if m == K.SEGMENT_ANY:
+            return out
+        ints = out.view(torch.int32)
+        return {"records": out, "dist": out[:, 0], "prim": ints[:, 1], "mat": ints[:, 2], "s": out[:, 3], "p": out[:, 4:7], "feature": ints[:, 7]}
+
+    def edge_proximity(self, vertices, edges, max_dist):
+        """The nearest surface point to every edge of a mesh: vertices (V, 3) float32 and edges (E, 2) integer, max_dist a scalar or one
+        value per edge; the closest records of query_segments on the segments vertices[edges] -- numpy for numpy input, the dict of
+        tensors for tensors on this context's device.  The edge-edge half of a proximity narrow phase beside query_points, the
+        vertex-face half.  An edge of the uploaded mesh itself is at distance 0 from the faces it belongs to."""
+        if hasattr(vertices, "data_ptr"):
+            import torch
+            if not hasattr(edges, "data_ptr"):
+                edges = torch.as_tensor(np.asarray(edges), device=vertices.device)
+            if vertices.dim() != 2 or vertices.shape[1] != 3 or edges.dim() != 2 or edges.shape[1] != 2 or vertices.dtype != torch.float32:
+                raise ValueError("edge_proximity: vertices must be (V, 3) float32 and edges (E, 2) integer")
+            return self.query_segments(vertices[edges.to(torch.int64)].contiguous(), "closest", max_dist)
+        v, e = np.asarray(vertices, np.float32), np.asarray(edges)
+        if v.ndim != 2 or v.shape[1] != 3 or e.ndim != 2 or e.shape[1] != 2 or e.dtype.kind not in "iu":
+            raise ValueError("edge_proximity: vertices must be (V, 3) float32 and edges (E, 2) integer")
+        return self.query_segments(v[e.astype(np.int64)], "closest", max_dist)
 
     # ---- winding-number queries (include/moptix.h "winding-number queries") ----
     def query_winding(self, points, beta=2.0):

@@ -285,6 +285,16 @@ struct moptix_context_t {
     void release() { drop(); sweeps.release(); out.release(); }
   } sweep;
 
+  // ---- segment queries (api_segment.hip): the stack overflow area of the segment kernel, its own (eight bytes an entry: reference +
+  // box distance), allocated at the first segment query after a build, kept across refits and dropped with the tree it was sized for,
+  // where the ray queries' is; the staging of the host-pointer entry point ----
+  struct Segment {
+    DevBuf<unsigned long long> overflow;
+    DevBuf<float> segments; DevBuf<uint8_t> out;
+    void drop() { overflow.release(); }
+    void release() { drop(); segments.release(); out.release(); }
+  } segment;
+
   // ---- oriented box queries (api_obb.hip): the stack overflow area of the oriented box kernel, its own (four bytes an entry: a
   // reference), allocated at the first such query after a build, kept across refits and dropped with the tree it was sized for, where the
   // box queries' is; the staging of the host-pointer entry points (obbs, offsets, prims; out: the int32 results or counts) ----

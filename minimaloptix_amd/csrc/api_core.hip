@@ -144,7 +144,7 @@ int moptix_destroy(moptix_context c) {
   (void)hipStreamSynchronize(c->stream);
   c->release_scene(); c->release_render();
   c->dAccum.release(); c->dRgb8.release();
-  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->radiance.release(); c->point.release(); c->box.release(); c->sweep.release(); c->obb.release(); c->frustum.release(); c->tri.release(); c->winding.release(); c->refit.drop();
+  c->aov.release(); c->dn.release(); c->tp.release(); c->ad.release(); c->query.release(); c->radiance.release(); c->point.release(); c->box.release(); c->sweep.release(); c->segment.release(); c->obb.release(); c->frustum.release(); c->tri.release(); c->winding.release(); c->refit.drop();
   c->sign.release();
   comm_release(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -192,10 +192,10 @@ int moptix_clear_scene(moptix_context c) {
   c->sceneDirty = true; c->accelBuilt = false;
   c->tp.drop();                                                // the temporal history belongs to the scene that made it
   c->tp.faces.changed = true;
-  if ((c->query.overflow.p || c->radiance.overflow.p || c->point.overflow.p || c->box.overflow.p || c->sweep.overflow.p || c->obb.overflow.p || c->frustum.overflow.p || c->tri.overflow.p || c->refit.planned || c->tp.faces.prev.p) && !c->poisoned) {      // a query in flight still uses what is dropped here
+  if ((c->query.overflow.p || c->radiance.overflow.p || c->point.overflow.p || c->box.overflow.p || c->sweep.overflow.p || c->segment.overflow.p || c->obb.overflow.p || c->frustum.overflow.p || c->tri.overflow.p || c->refit.planned || c->tp.faces.prev.p) && !c->poisoned) {      // a query in flight still uses what is dropped here
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->query.drop(); c->radiance.drop(); c->point.drop(); c->box.drop(); c->sweep.drop(); c->obb.drop(); c->frustum.drop(); c->tri.drop();
+    c->query.drop(); c->radiance.drop(); c->point.drop(); c->box.drop(); c->sweep.drop(); c->segment.drop(); c->obb.drop(); c->frustum.drop(); c->tri.drop();
     c->tp.faces.release();                                     // the face snapshot too
   }
   c->refit.drop(); c->refit.facesDirty = false; c->refit.hostStale = false; c->refit.facesOnDevice = 0;      // the faces are gone, and the plan with their tree
@@ -334,9 +334,9 @@ int moptix_build_accel(moptix_context c, const char* kind) {
   }
   c->refit.drop();                                // the plan describes the tree that is about to go
   winding_release(c);                             // and so do the winding queries' moments and overflow area
-  if ((c->query.overflow.p || c->radiance.overflow.p || c->point.overflow.p || c->box.overflow.p || c->sweep.overflow.p || c->obb.overflow.p || c->frustum.overflow.p || c->tri.overflow.p) && !c->poisoned) {      // an asynchronous query in flight still walks the old tree; the area was sized for its depth
+  if ((c->query.overflow.p || c->radiance.overflow.p || c->point.overflow.p || c->box.overflow.p || c->sweep.overflow.p || c->segment.overflow.p || c->obb.overflow.p || c->frustum.overflow.p || c->tri.overflow.p) && !c->poisoned) {      // an asynchronous query in flight still walks the old tree; the area was sized for its depth
     HIPCHK(c, hipStreamSynchronize(c->stream), "sync before the build");
-    c->query.drop(); c->radiance.drop(); c->point.drop(); c->box.drop(); c->sweep.drop(); c->obb.drop(); c->frustum.drop(); c->tri.drop();
+    c->query.drop(); c->radiance.drop(); c->point.drop(); c->box.drop(); c->sweep.drop(); c->segment.drop(); c->obb.drop(); c->frustum.drop(); c->tri.drop();
   }
   HIPCHK(c, c->dMats.upload(c->mats, c->stream), "upload materials");
   HIPCHK(c, c->dSpheres.upload(c->spheres, c->stream), "upload spheres");
